@@ -1,8 +1,8 @@
 """
 bench.py - BASELINE metric: M evals/s on the 10 M-point bicubic (order 4x4, nCoef 64x64,
-nDep 3, fp64) surface (BASELINE.json configs[1]) at 1/2/4/8 GPUs, with the CPU path beside it.
+nDep 3, fp64) surface (BASELINE.json configs[1]) at 1/2/4/8 GPUs; with --full, the CPU path beside it.
 
-    python bench.py --gpus 1 --steps 200 --warmup 5
+    python bench.py --gpus 1 --steps 200 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,19 +10,28 @@ One step = one pass of the hot path (Spline.evaluate: span search + Cox-de Boor 
 tensor-product contraction, fused in one HIP kernel) over the 10 M synthetic (u, v) points of the
 metric, inputs and outputs resident in HBM.  Multi-GPU: STRONG scaling - the same 10 M points are
 sharded contiguously over the ranks (one process per GPU, no data-path collective in the timed
-region; results stay sharded), value = 10 M / max-over-ranks time.  Beside the headline, N > 1 lines
+region; results stay sharded), value = 10 M / max-over-ranks time.  With --full, N > 1 lines also
 carry "weak" (10 M points per rank) and "with_allgather" (the RCCL all-gather of results included).
 
 Prints ONE JSON line (rank 0).  roofline.achieved uses the ALGORITHMIC bytes of SURVEY.md 8(d):
 40 B per eval (2 x 8 B in + 3 x 8 B out) against 8 TB/s HBM3E, over the average launch duration
 measured with HIP events on the launch stream inside the timed region.
 
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.
+--full adds every measurement that takes runs of its own: N = 1: the per-launch median, the measured
+stream floor, the other BASELINE configs, the host end-to-end path and the CPU baseline; N > 1: weak
+scaling and the all-gather; --config 5: the per-kernel times of the pipeline.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (DIR/<name>_rank<r>.npy for
+N > 1), in the path's own dtype; an output larger than its share of DUMP_BYTES keeps a fixed, seeded
+sample of its points (the same one from run to run, like the inputs).
+
 `--config {2,3,4,5}` selects the BASELINE config the job runs (default 2 = the metric's; the others are the
 parity-test configs, runnable sharded so that an 8-GPU node can drive each of them):
     3  same bicubic: derivative([1,1]) + fused jacobian per step (104 B per point), all-gather of (3,N) and (3,2,N)
     4  Utah teapot, 32 bicubic fp32 patches on a 2048 x 2048 grid each, sharded BY PATCH (12 B per grid point)
-    5  trivariate order 5, 40^3 x 4, fp32, 50 M points (28 B per point): the cell-order pipeline, with its per-kernel
-       times (sort_ms / eval_ms), and the fp32-ALU / MFMA fractions next to the HBM one
+    5  trivariate order 5, 40^3 x 4, fp32, 50 M points (28 B per point): the cell-order pipeline, with (--full)
+       its per-kernel times (sort_ms / eval_ms), and the fp32-ALU / MFMA fractions next to the HBM one
 """
 import argparse
 import ctypes
@@ -45,6 +54,7 @@ FP32_PEAK_TFLOPS = 157.3       # MI355X fp32 vector peak = fp32 MFMA peak (MI355
 CFG5_FLOP_PER_POINT = 1450     # algorithmic fp32 flop per cfg5 point
 CFG5_MFMA_FLOP_PER_POINT = 1000  # the part of them the 4x4x1 MFMAs carry: 125 control points x 4 dependents x 2
 PROFILE_DIR = "profiles/r03_eval_uni"    # rocprofv3 summaries of this command (kernel trace + PMC passes)
+DUMP_BYTES = 48 << 20          # --dump-outputs: result bytes written in all, over every array and rank (limit 64 MB)
 
 
 def cpu_model():
@@ -127,6 +137,26 @@ def timed(torch, f, steps, spin_s=0.06):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / steps * 1e-3
+
+
+def dump_outputs(path, arrays, world, rank):
+    """--dump-outputs: write each device array of `arrays` ({name: tensor, points on the last axis}) as
+    path/<name>.npy (path/<name>_rank<r>.npy for N > 1).  An array over its share of DUMP_BYTES keeps the
+    points of one fixed sample (seed 0, sorted indices), so two builds of the project compare point for point."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        n = t.shape[-1]
+        if n == 0:
+            continue
+        keep = min(n, share // (t.element_size() * (t.numel() // n)))
+        if keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            t = t.index_select(t.dim() - 1, torch.as_tensor(idx, device=t.device))
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), a.dtype
+        np.save(os.path.join(path, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a)
 
 
 def row(sec, evals, bytes_per_eval):
@@ -382,9 +412,17 @@ def run_other_config(args, torch, dist, dev, world, rank):
     if status is not None:
         status.domain_status()
     kernel = tables.last_kernel() if tables is not None else ""
+    if args.dump_outputs:
+        if cfg == 3:
+            dumped = {"derivative_1_1": outs[0], "jacobian": outs[1].reshape(ndep, nind, n_local)}
+        elif cfg == 5:
+            dumped = {"evaluate": outs[0]}
+        else:
+            dumped = {"tessellate_positions": pos.reshape(npl, 3, side * side)}
+        dump_outputs(args.dump_outputs, dumped, world, rank)
 
     extra = {}
-    if cfg == 5 and units_local > 0:
+    if args.full and cfg == 5 and units_local > 0:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         from cfg5_stages import stage_times
         st_ms = stage_times(tables, step, reps=max(3, min(args.steps, 10)))
@@ -401,7 +439,7 @@ def run_other_config(args, torch, dist, dev, world, rank):
                      "from LDS); mfma_frac = the 1000 flop per point the v_mfma_f32_4x4x1 instructions carry against the fp32 "
                      "matrix peak (also 157.3), over the evaluation kernel's own time"),
         }
-    if dist is not None:
+    if args.full and dist is not None:
         blocks = gather_blocks()
         bufs = []
         for (t, rows, width, valid) in blocks:
@@ -456,10 +494,14 @@ def main():
     ap.add_argument("--config", type=int, choices=[2, 3, 4, 5], default=2,
                     help="BASELINE config of the job: 2 = the metric's (default), 3 = derivative + jacobian, 4 = teapot tessellation, 5 = trivariate fp32")
     ap.add_argument("--points", type=int, default=N_POINTS, help="points of the whole job (sharded over the ranks; config 5 defaults to 50 M)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline and host end-to-end legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs (reported beside the headline, N=1 only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline and host end-to-end legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other BASELINE configs (reported beside the headline, N=1 only)")
     ap.add_argument("--cpu-sample", type=int, default=10_000_000)
     ap.add_argument("--spinup", type=int, default=300, help="untimed launches before warm-up (clock ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: per-launch median, stream floor, other configs, "
+                         "host path and CPU baseline (N = 1), weak scaling and all-gather (N > 1), cfg5 per-kernel times")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -551,13 +593,13 @@ def main():
                 nv.check(st)
         torch.cuda.synchronize()
 
-    def measure(step, per_launch):
+    def measure(step):
         """W warm-up steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks.
-        Returns (wall seconds for K steps, mean launch ms from HIP events, median launch ms or None).
+        Returns (wall seconds for K steps, mean launch ms from HIP events).
         The timed region holds the K launches and ONE event at either end, on the stream the kernel is launched on.
         (Round 2 recorded an event after every launch inside it, for the median: each record costs the device ~3 us
         between two launches - 0.0899-0.0911 ms per step against 0.0871-0.0875 without, same box, same build.  The
-        median now comes from a second, untimed pass.)"""
+        median now comes from a second, untimed pass: median_launch_ms.)"""
         for _ in range(args.warmup):
             step()
         barrier()
@@ -575,20 +617,22 @@ def main():
         elapsed = t1 - t0                   # the figure that includes it is reported beside it for N > 1)
         measure.incl_barrier = t2 - t0
         kernel_ms = evs[0].elapsed_time(evs[1]) / k
-        median_ms = None
-        if per_launch:                      # untimed diagnostic pass: an event after every launch
-            pe = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
-            pe[0].record()
-            for i in range(k):
-                step()
-                pe[i + 1].record()
-            torch.cuda.synchronize()
-            median_ms = statistics.median(pe[i].elapsed_time(pe[i + 1]) for i in range(k))
         if dist is not None:
             tt = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed, kernel_ms = float(tt[0]), float(tt[1])
-        return elapsed, kernel_ms, median_ms
+        return elapsed, kernel_ms
+
+    def median_launch_ms(step):
+        """Untimed diagnostic pass (--full): K steps with an event after every launch."""
+        k = args.steps
+        pe = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
+        pe[0].record()
+        for i in range(k):
+            step()
+            pe[i + 1].record()
+        torch.cuda.synchronize()
+        return statistics.median(pe[i].elapsed_time(pe[i + 1]) for i in range(k))
 
     # ---- headline: the 10 M points of the metric, sharded over the ranks (N = 1: all of them)
     start, stop = shard_bounds(n_total, world, rank)
@@ -596,13 +640,17 @@ def main():
     uv, u, v, out, ptrs, step = make_workload(n_local, 1000 + rank)
     barrier()                       # first use of the communicator (lazy RCCL init) happens here, untimed
     spin(ptrs, n_local)
-    elapsed, kernel_ms, median_ms = measure(step, per_launch=(world == 1 and n_local >= 5_000_000))
+    elapsed, kernel_ms = measure(step)
     tables.domain_status()                                # the in-kernel domain check found nothing
     kernel = tables.last_kernel()
     incl_barrier = measure.incl_barrier
+    if args.dump_outputs:
+        res_out = out.reshape(ndep, nind, n_local) if args.op == "jacobian" else out
+        dump_outputs(args.dump_outputs, {args.op: res_out}, world, rank)
+    median_ms = median_launch_ms(step) if (args.full and world == 1 and n_local >= 5_000_000) else None
 
     extra = {}
-    if dist is not None:
+    if args.full and dist is not None:
         # results replicated on every rank: one all-gather of every rank's (rows, chunk) block per step
         chunk = -(-n_total // world)
         full = torch.empty((world * rows, chunk), dtype=torch.float64, device=dev)
@@ -612,7 +660,7 @@ def main():
             step()
             send[:, :n_local].copy_(out)
             dist.all_gather_into_tensor(full, send)
-        gel, _, _ = measure(gstep, per_launch=False)
+        gel, _ = measure(gstep)
         gsec = gel / args.steps
         extra["with_allgather"] = {"value": round(n_total / gsec / 1e6, 1), "unit": "M evals/s", "ms_per_step": round(gsec * 1e3, 4),
                                    "allgather_bytes_per_rank_in": (world - 1) * rows * chunk * 8,
@@ -620,7 +668,7 @@ def main():
         del full, send
         # weak scaling: 10 M points on every rank
         wuv, wu, wv, wout, wptrs, wstep = make_workload(n_total, 2000 + rank)
-        wel, wk, _ = measure(wstep, per_launch=False)
+        wel, wk = measure(wstep)
         extra["weak"] = {"value": round(world * n_total / (wel / args.steps) / 1e6, 1), "unit": "M evals/s",
                          "points_per_gpu": n_total, "ms_per_step": round(wel / args.steps * 1e3, 5)}
         tables.domain_status()
@@ -649,7 +697,7 @@ def main():
         if dist is not None:
             res["ms_per_step_incl_closing_barrier"] = round(incl_barrier / args.steps * 1e3, 5)
         res.update(extra)
-        if world == 1:
+        if args.full and world == 1:
             res["roofline"]["measured_stream_floor_GBs"] = stream_floor(torch, tables, u, v, n_local)
             if not args.no_extra and args.op == "evaluate":
                 res["other_configs"] = other_configs(torch, tables, u, v, n_local)

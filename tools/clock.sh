@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/clock_$1; shift
 mkdir -p $out
-rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $out/p -- python3 bench.py --no-cpu --steps 5 --warmup 1 "$@" > $out/log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $out/p -- python3 bench.py --full --no-cpu --steps 5 --warmup 1 "$@" > $out/log 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob('$out/p/*/*_counter_collection.csv')[0]
