@@ -18,6 +18,7 @@ BSK_F32, BSK_F64 = 0, 1
 BSK_HOST, BSK_DEVICE = 0, 1
 BSK_OK, BSK_ERR_INVALID, BSK_ERR_DOMAIN, BSK_ERR_HIP, BSK_ERR_NO_DEVICE, BSK_ERR_UNSUPPORTED = range(6)
 BSK_MAX_NIND, BSK_MAX_ORDER = 8, 16
+BSK_INTEGRAL_MEASURE, BSK_INTEGRAL_NODES = 0, 1
 
 # every symbol of the product ABI in include/bspy_amd.h (tests check the library exports them all) ...
 PRODUCT_SYMBOLS = (
@@ -26,7 +27,7 @@ PRODUCT_SYMBOLS = (
     "bsk_evaluate", "bsk_jacobian", "bsk_normal", "bsk_curvature", "bsk_evaluate_grid", "bsk_tessellate",
     "bsk_domain_status", "bsk_bspline_values", "bsk_last_kernel",
     "bsk_multi_create", "bsk_multi_destroy", "bsk_multi_shard_plan", "bsk_multi_stream", "bsk_multi_evaluate",
-    "bsk_multi_jacobian",
+    "bsk_multi_jacobian", "bsk_integral",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times")
@@ -108,6 +109,7 @@ def lib():
     L.bsk_multi_stream.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_vp)]
     L.bsk_multi_evaluate.argtypes = [_vp, _ip, _vpp, _i64, ctypes.c_int, _vpp, ctypes.c_int, _i64p]
     L.bsk_multi_jacobian.argtypes = [_vp, _vpp, _i64, ctypes.c_int, _vpp, ctypes.c_int, _i64p]
+    L.bsk_integral.argtypes = [_vp, ctypes.c_int, _vp, _i32p, _i64, _vp, _vp]
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]

@@ -227,6 +227,24 @@ class DeviceSpline:
         nv.check(st, bad)
         return out
 
+    def integral_regions(self, lo_hi, span, nodes=False):
+        """One Gauss-Kronrod 7/15 round (C ABI ``bsk_integral``; driver: bspy_amd/integral.py).
+        lo_hi: (R, nInd, 2) region bounds, span: (R, nInd) span indices of the cells the regions lie in.
+        Returns fp64 (R, 2) = Kronrod and Gauss sums of the measure per region, or with ``nodes``
+        (R, 15**nInd, nDep + 2) = point x, wK * measure, wG * measure per node."""
+        lh = np.ascontiguousarray(lo_hi, self.dtype)
+        sp = np.ascontiguousarray(span, np.int32)
+        nreg = lh.shape[0]
+        if lh.shape != (nreg, self.nInd, 2) or sp.shape != (nreg, self.nInd):
+            raise ValueError("lo_hi must be (R, nInd, 2) and span (R, nInd)")
+        shape = (nreg, 15 ** self.nInd, self.nDep + 2) if nodes else (nreg, 2)
+        out = np.empty(shape, np.float64)
+        mode = nv.BSK_INTEGRAL_NODES if nodes else nv.BSK_INTEGRAL_MEASURE
+        st = nv.lib().bsk_integral(self._handle, mode, lh.ctypes.data, sp.ctypes.data_as(nv._i32p), nreg,
+                                   out.ctypes.data, None)
+        nv.check(st)
+        return out
+
     # ------------------------------------------------------------------ device (torch) calls
     def _torch_params(self, points):
         import torch

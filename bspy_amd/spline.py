@@ -9,6 +9,7 @@ error messages for
     s.jacobian(uvw) / s.tangent_space(uvw)                        spline.py:1354-1377, :2238-2252
     s.domain()                                                    spline.py:794-808
     s.normal(uvw, normalize=True, indices=None)                   spline.py:1648-1682
+    s.integral(integrand=None, domain=None)                       spline.py:1249 (nInd 1 - 3)
     Spline.bspline_values(knot, knots, splineOrder, u, ...)       spline.py:207-252
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
@@ -193,6 +194,21 @@ class Spline:
         (reference spline.py `curvature` -> _spline_evaluation.py:80-107); arrays of points
         give an array of curvatures."""
         return _ev.curvature(self, uv)
+
+    def integral(self, integrand=None, domain=None):
+        """Integral over ``domain`` (nInd x 2, default the spline's domain) of integrand(x) dA, where dA is the
+        measure of the map (product of the singular values of the jacobian): arc length, area or volume when
+        ``integrand`` is None, moments with e.g. ``lambda x: x[0]`` (reference spline.py:1249).  Returns a float.
+
+        Every knot cell inside the domain is integrated by a tensor Gauss-Kronrod 7/15 rule on the GPU, split
+        adaptively until each region's Kronrod / Gauss difference is within its share of max(tol, tol |I|),
+        tol = 1e-13 / nInd (the reference's request); float32 splines evaluate their nodes in float32 (sums in
+        float64) with tol = 1e-6.  A callable integrand is called once per quadrature node with x (ndarray, nDep)
+        and must return a scalar.  After 40 rounds or 2^22 regions the current sum is returned with a
+        RuntimeWarning that gives the estimated error.  Results are bitwise reproducible.
+        nInd 1 to 3 only: nInd >= 4 raises NotImplementedError (deliberate scope)."""
+        from . import integral as _integral
+        return _integral.integral(self, integrand, domain)
 
     def tangent_space(self, uvw):
         """Same as jacobian (reference spline.py:2238-2252)."""

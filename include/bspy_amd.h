@@ -158,6 +158,27 @@ bsk_status bsk_tessellate(const bsk_spline *splines, int count, const void *cons
                           int64_t *first_bad);
 
 /*
+ * One round of the adaptive quadrature behind Spline.integral: a tensor-product Gauss-Kronrod 7/15 rule over each
+ * of nreg boxes ("regions"), each inside one knot cell.  The adaptive driver (which regions to split) is the caller's.
+ * Replaces: the nested scipy.integrate.quad of composed_integral, bspy/_spline_evaluation.py:29-73 (bspy/spline.py:1249).
+ *   The integrated measure is mu(u) = product of the singular values of the nDep x nInd jacobian:
+ *   |det J| (nDep == nInd), sqrt(det(J^T J)) (nDep > nInd), sqrt(det(J J^T)) (nDep < nInd), determinants clamped at 0.
+ *   mode    : BSK_INTEGRAL_MEASURE - out[2 r] = Kronrod sum K_r of mu, out[2 r + 1] = embedded Gauss sum G_r;
+ *             BSK_INTEGRAL_NODES   - per node q of region r (15^nInd nodes, first variable slowest):
+ *               out[(r * 15^nInd + q) * (nDep + 2) + d] = x_d (d < nDep), then wK * mu and wG * mu, the node's
+ *               Kronrod / Gauss weight (box volume included, wG = 0 off the Gauss nodes) times the measure
+ *   lo_hi   : nreg * nInd * 2 values in the spline's dtype, lo_hi[(r * nInd + iv) * 2 + {0, 1}] = bounds of region r
+ *   span    : nreg * nInd span indices of the cell each region lies in ("rightmost knot of the segment":
+ *             knots[iv][span - 1] <= lo < hi <= knots[iv][span], order <= span <= nCoef)
+ *   out     : fp64 for both dtypes (fp32 splines evaluate their nodes in fp32 and sum in fp64)
+ * Host buffers; the call synchronises `stream`.  Sums run in a fixed order (no atomics): bitwise reproducible.
+ * nInd outside 1 - 3 returns BSK_ERR_UNSUPPORTED.
+ */
+typedef enum { BSK_INTEGRAL_MEASURE = 0, BSK_INTEGRAL_NODES = 1 } bsk_integral_mode;
+bsk_status bsk_integral(bsk_spline s, int mode, const void *lo_hi, const int32_t *span, int64_t nreg, void *out,
+                        void *stream);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
