@@ -30,7 +30,7 @@ PRODUCT_SYMBOLS = (
     "bsk_multi_jacobian", "bsk_integral",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
-INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times")
+INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
 SYMBOLS = PRODUCT_SYMBOLS + INTERNAL_SYMBOLS
 
 
@@ -115,6 +115,7 @@ def lib():
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
     L.bsk_debug_stage_times.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, _ip]
+    L.bsk_debug_fill_lds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _i64p, _vp]
     for name in SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel"):
             getattr(L, name).restype = ctypes.c_int

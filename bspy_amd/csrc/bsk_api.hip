@@ -1924,6 +1924,7 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
             hipLaunchKernelGGL((grid_rows<T, O, true>), dim3(gridx), dim3(256), rowc_bytes, st, d, coef, g, ixs, rows,  \
                                outside, dout, s->bad, vec_ok);                                                 \
         launched = true;                                                                                       \
+        s->last_kernel = "grid_rows";                                                                          \
         break;
         switch (omax2) {
             GRID_ROWS(1) GRID_ROWS(2) GRID_ROWS(3) GRID_ROWS(4) GRID_ROWS(5) GRID_ROWS(6)
@@ -1939,6 +1940,7 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
         hipLaunchKernelGGL((grid_surface<T, O>), dim3(gx, (unsigned)g.n[0]), dim3(block), 0, st, d, coef, g,   \
                            ixs, rows, outside, dout, s->bad);                                                  \
         launched = true;                                                                                       \
+        s->last_kernel = "grid_surface";                                                                       \
         break;
         switch (s->order[0]) {
             GRID_SURF(1) GRID_SURF(2) GRID_SURF(3) GRID_SURF(4) GRID_SURF(5) GRID_SURF(6)
@@ -1952,6 +1954,7 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
         const int gridx = (int)std::max<long long>(1, std::min<long long>(blocks, (long long)s->num_cu * 8));
         hipLaunchKernelGGL((grid_generic<T>), dim3(gridx), dim3(block), 0, st, d, coef, g, ixs, rows, outside, total,
                            dout, s->bad);
+        s->last_kernel = "grid_generic";
     }
     HIPCHK(hipGetLastError());
     if (mem == BSK_HOST) {
@@ -2074,6 +2077,9 @@ static bsk_status run_tessellate(const bsk_spline *sp, int count, const void *co
             TESS(1) TESS(2) TESS(3) TESS(4) TESS(5) TESS(6)
             default: return fail(BSK_ERR_UNSUPPORTED, "bsk_tessellate: orders 1..6");
         }
+        // the form launched, on the first patch's handle
+        s->last_kernel = !s->same_order ? "tess_rows mixed" : normals ? "tess_rows normals" : wide ? "tess_rows hoisted 512"
+                       : hoist ? "tess_rows hoisted 256" : "tess_rows columns";
 #undef TESS
 #undef TESS_LAUNCH
 #undef TESS_LAUNCH_WIDE
@@ -2283,5 +2289,41 @@ extern "C" bsk_status bsk_debug_probe(bsk_spline s, int mode, int blocks_per_cu,
                            static_cast<const double *>(v), (long long)n, static_cast<double *>(out), (long long)n);
     }
     HIPCHK(hipGetLastError());
+    return BSK_OK;
+}
+
+// Writes (mode 0) or checks (mode 1) `pattern` over the whole LDS of every CU: 8 * num_cu workgroups of 1024 lanes with
+// lds_max bytes each, so a CU holds one at a time.  Synchronises `stream` before it returns, so that a following call on
+// any stream of the device runs after it.  Used by the stale-LDS tests; not an evaluation call.
+extern "C" bsk_status bsk_debug_fill_lds(bsk_spline s, uint32_t pattern, int mode, int64_t *mismatches, void *stream)
+{
+    if (!s) return fail(BSK_ERR_INVALID, "spline is NULL");
+    if (mode != 0 && mode != 1) return fail(BSK_ERR_INVALID, "bsk_debug_fill_lds: mode 0 (fill) or 1 (check)");
+    if (mode == 1 && !mismatches) return fail(BSK_ERR_INVALID, "bsk_debug_fill_lds: mode 1 needs `mismatches`");
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bytes = s->lds_max & ~(size_t)3;
+    unsigned long long *cnt = nullptr;
+    if (mode == 1) {
+        HIPCHK(hipMalloc(&cnt, sizeof(unsigned long long)));
+        if (hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st) != hipSuccess) {
+            (void)hipFree(cnt);
+            return fail(BSK_ERR_HIP, "bsk_debug_fill_lds: hipMemsetAsync failed");
+        }
+    }
+    hipError_t e = allow_lds(debug_fill_lds, bytes);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(debug_fill_lds, dim3(8 * s->num_cu), dim3(1024), bytes, st, (unsigned)pattern, mode,
+                           (unsigned)(bytes / 4), cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (cnt) {
+        unsigned long long h = 0;
+        if (e == hipSuccess) e = hipMemcpy(&h, cnt, sizeof(h), hipMemcpyDeviceToHost);
+        (void)hipFree(cnt);
+        *mismatches = (int64_t)h;
+    }
+    HIPCHK(e);
     return BSK_OK;
 }

@@ -645,6 +645,7 @@ __global__ __launch_bounds__(HIT == 1 ? 512 : 256) void tess_rows(const Desc<T> 
     T hb1[HIT][VEC][O], hdb1[NORMALS ? HIT : 1][NORMALS ? VEC : 1][O];
     int hix1[HIT][VEC];
     bool hbad[HIT][VEC];
+    bool hone[HIT];                                           // all VEC columns of the step in one span (any axis order)
     if (hoist) {
 #pragma unroll
         for (int it = 0; it < HIT; ++it) {
@@ -660,6 +661,9 @@ __global__ __launch_bounds__(HIT == 1 ? 512 : 256) void tess_rows(const Desc<T> 
                     if constexpr (NORMALS) hdb1[it][v][k] = drows[g.roff[1] + c * O + k];
                 }
             }
+            hone[it] = true;
+#pragma unroll
+            for (int v = 1; v < VEC; ++v) hone[it] &= hix1[it][v] == hix1[it][0];
         }
     }
     if (hoist) {
@@ -698,9 +702,11 @@ __global__ __launch_bounds__(HIT == 1 ? 512 : 256) void tess_rows(const Desc<T> 
 #pragma unroll
                         for (int v = 0; v < VEC; ++v)
                             if (blockIdx.y == 0 && (bad0 | hbad[it][v])) record_bad(bad, i0 * n1 + c0 + v);
-                        if (hix1[it][0] == hix1[it][VEC - 1]) {
+                        if (hone[it]) {
                             // the lane's columns lie in one span (always, for Bezier patches): its 3 x O contracted control
-                            // points are read once for the VEC columns (LDS instructions per point: 3 O -> 3 O / VEC)
+                            // points are read once for the VEC columns (LDS instructions per point: 3 O -> 3 O / VEC).
+                            // (All VEC of them: on an axis that is not monotonic, equal first and last spans say nothing
+                            // about the columns between.)
                             T rcv[3][O];
 #pragma unroll
                             for (int dep = 0; dep < 3; ++dep)

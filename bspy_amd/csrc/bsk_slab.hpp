@@ -20,7 +20,7 @@
 // L2 -> LDS traffic: table bytes per chunk (238 KB per 8192 points = 29 B per point).  Used when the table is
 // <= SLAB_MAX_TABLE bytes and at most SLAB_MAX_PASS passes cover it.
 // LDS: [axis table of variable 1][bucket tables][wave counts: SLAB_WAVES x SLAB_MAX_PASS][pass starts]
-//      [slice of variable 0's axis table: order0 rows x snk][slab]
+//      [slice of variable 0's axis table: order0 rows x snk][slab][zero tail: (O - 1) x nDep values]
 #pragma once
 #include "bsk_gather.hpp"
 #include "bsk_binned.hpp"
@@ -41,7 +41,7 @@ struct SlabPlan {
     int chunk;      // points per chunk: SLAB_CHUNK, or less for a one-slab table on a batch that would not fill the CUs
     int rows;         // rows of a slab (spp + order0 - 1)
     int snk;          // entries per row of the axis-table slice (spp + order0)
-    unsigned off_lut, off_wcnt, off_pstart, off_tab0, off_slab, total;   // byte offsets in LDS
+    unsigned off_lut, off_wcnt, off_pstart, off_tab0, off_slab, off_tail, total;   // byte offsets in LDS (tail: zeros behind the slab)
 };
 
 template <typename T>
@@ -83,7 +83,9 @@ __device__ __forceinline__ void slab_shift(const T (&b)[O], T (&bs)[O])
 // MIXED: a second variable of lower order uses the LAST order1 columns of the O-wide window.  Testing `k >= pad1` per
 // term made hipcc select every accumulator update (120 of the 527 vector instructions per point of the fp64 order-5
 // loop were v_cndmask); instead the row reads START at column pad1 and the weights are shifted left by pad1 once: the
-// trailing columns carry weight zero and read finite values (the next control points of the slab; zero past its end).
+// trailing pad1 columns carry weight zero.  They read the next control points of the slab - or, for the last span of
+// the second variable on a slab's last row, up to pad1 control points PAST the slab: the tail of (O - 1) x ND zeros
+// that eval_slab2 writes behind it at kernel start (0 x a stale NaN in LDS would be NaN).
 template <typename T, int O, int ND, bool MIXED>
 __device__ __forceinline__ void slab_window(unsigned w_addr, unsigned rstride, const int (&pad)[2], const T (&b)[2][O], T (&r)[ND])
 {
@@ -178,6 +180,8 @@ __global__ __launch_bounds__(SLAB_BLOCK) void eval_slab2(const Desc<T> d, const 
     const int nk0 = d.nk[0], nk1 = d.nk[1], O0 = d.order[0];
     for (int i = threadIdx.x; i < nk1 * d.order[1]; i += blockDim.x) stab1[i] = gtab[d.off[1] + i];
     for (int i = threadIdx.x; i < td.lut_len; i += blockDim.x) slut[i] = glut[i];
+    // the zero tail behind the slab (slab_window's reads past a full slab's last row land here; no pass writes it)
+    for (unsigned i = sp.off_tail / 4u + threadIdx.x; i < sp.total / 4u; i += blockDim.x) reinterpret_cast<unsigned *>(smem)[i] = 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nc1 = d.ncoef[1];
     const int rowlen = nc1 * ND;                             // elements per table row (one control-point index of variable 0)

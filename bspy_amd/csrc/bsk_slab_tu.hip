@@ -46,7 +46,10 @@ static bsk_status launch_eval_slab2(bsk_spline s, const Params<T> &prm, long lon
     sp.rows = spp + s->order[0] - 1;
     sp.snk = spp + s->order[0];
     sp.off_slab = (unsigned)(off + up16((size_t)sp.snk * slicebytes));
-    sp.total = (unsigned)(sp.off_slab + up16((size_t)sp.rows * rowbytes));
+    // behind the slab: O - 1 control points of zeros (a mixed-order window row reads up to pad1 of them past the slab's
+    // last row; eval_slab2 zeroes them at kernel start).  At most 160 bytes: inside the 256 bytes `room` keeps free.
+    sp.off_tail = (unsigned)(sp.off_slab + (size_t)sp.rows * rowbytes);
+    sp.total = (unsigned)(sp.off_slab + up16((size_t)sp.rows * rowbytes + (size_t)(O - 1) * s->nDep * sizeof(T)));
     if (sp.total > lds_wg) return BSK_ERR_UNSUPPORTED;
     // chunk-private scratch of the order: batch position | span of every point
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;

@@ -578,4 +578,25 @@ __global__ __launch_bounds__(TILE) void probe_stream(const double *__restrict__ 
     }
 }
 
+// -------------------------------------------------------------------------------------
+// debug_fill_lds: LDS contents for the stale-LDS tests (bsk_debug_fill_lds).  Every workgroup takes
+// `words` 32-bit words of dynamic LDS.  MODE 0 writes `pattern` over all of them; MODE 1 (positive
+// control) reads them WITHOUT writing first and adds the number of words that differ from `pattern`
+// to *mismatches - zero when a later dispatch sees what an earlier one left in LDS.  Plain C++
+// accesses.  Diagnostic only.
+// -------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void debug_fill_lds(const unsigned pattern, const int mode, const unsigned words,
+                                                       unsigned long long *__restrict__ mismatches)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned *w = reinterpret_cast<unsigned *>(smem);
+    if (mode == 0) {
+        for (unsigned i = threadIdx.x; i < words; i += blockDim.x) w[i] = pattern;
+        return;
+    }
+    unsigned long long miss = 0;
+    for (unsigned i = threadIdx.x; i < words; i += blockDim.x) miss += w[i] != pattern ? 1ull : 0ull;
+    if (miss) atomicAdd(mismatches, miss);
+}
+
 }  // namespace bsk

@@ -234,7 +234,10 @@ bsk_status bsk_multi_jacobian(bsk_multi m, const void *const *uvw, int64_t n, bs
  * Diagnostics (no reference counterpart; used by bench.py, tools/ and the tests).
  *   bsk_last_kernel : family name of the kernel the most recent point call on this handle launched
  *                     ("eval_uni", "eval_rowrot", "eval_stream", "cell-order pipeline (...)", ...), so
- *                     that measurements and tests name the kernel that actually ran.
+ *                     that measurements and tests name the kernel that actually ran.  bsk_evaluate_grid records its
+ *                     grid kernel ("grid_rows", "grid_surface", "grid_generic"); bsk_tessellate records the form of
+ *                     tess_rows it launched on the first patch's handle ("tess_rows hoisted 512", "tess_rows hoisted
+ *                     256", "tess_rows normals", "tess_rows mixed", "tess_rows columns").
  */
 const char *bsk_last_kernel(bsk_spline s);
 
@@ -250,11 +253,16 @@ const char *bsk_last_kernel(bsk_spline s);
  *                           call's stream).  enable != 0 records the FOLLOWING calls on this handle; a call with
  *                           ms / names / count returns the stages of the last recorded call (names are static
  *                           strings, at most `cap` entries).
+ *   bsk_debug_fill_lds    : LDS contents for the stale-LDS tests: 8 workgroups per CU of 1024 lanes, each with the whole
+ *                           LDS of a CU.  mode 0 writes `pattern` over it; mode 1 (positive control) reads it without
+ *                           writing it and adds the words that differ from `pattern` to *mismatches.  Synchronises
+ *                           `stream` before it returns.
  */
 #ifdef BSK_INTERNAL
 bsk_status bsk_debug_probe(bsk_spline s, int mode, int blocks_per_cu, int threads, int64_t lds_bytes,
                            const void *u, const void *v, int64_t n, void *out, void *stream);
 bsk_status bsk_debug_stage_times(bsk_spline s, int enable, float *ms, const char **names, int cap, int *count);
+bsk_status bsk_debug_fill_lds(bsk_spline s, uint32_t pattern, int mode, int64_t *mismatches, void *stream);
 #endif
 
 #ifdef __cplusplus

@@ -359,6 +359,31 @@ def test_full_size_properties():
     d1 = t.evaluate([uv[0][:m], uv[1][:m]], [0, 1])
     assert np.abs(jac[:, 0] - d0).max() <= 1e-11 * _scale(d0)
     assert np.abs(jac[:, 1] - d1).max() <= 1e-11 * _scale(d1)
+    # (g) the benchmarked cfg3 calls at their full size against the oracle on the sample: derivative([1, 1]) and the
+    # jacobian of all 10 M points
+    d11 = t.evaluate([uv[0], uv[1]], [1, 1])
+    od11, bad = oracle.c_evaluate(order, ncoef, knots, coefs, [1, 1], [uv[0][idx], uv[1][idx]])
+    assert bad == -1
+    observe("cfg3 full size: derivative (1, 1) vs oracle, fp64", np.abs(d11[:, idx] - od11).max() / _scale(od11), 1e-12)
+    del d11
+    jac = t.jacobian([uv[0], uv[1]])
+    ojac, bad = oracle.c_jacobian(order, ncoef, knots, coefs, [uv[0][idx], uv[1][idx]])
+    assert bad == -1
+    observe("cfg3 full size: jacobian vs oracle, fp64", np.abs(jac[:, :, idx] - ojac).max() / _scale(ojac), 1e-12)
+
+
+def test_cfg1_bench_size():
+    """BASELINE configs[0] at its benchmarked size: the cubic curve (nCoef 32, fp64) on 100 k uniform parameters, both
+    ends of the domain included, value and every derivative up to 4 through Spline, against the oracle."""
+    nind, ndep, order, ncoef, knots, coefs, dt = cases.bench_spline(1)
+    s = Spline(nind, ndep, order, ncoef, knots, coefs)
+    u = np.linspace(knots[0][order[0] - 1], knots[0][ncoef[0]], 100_000)
+    for w in range(5):
+        out = np.asarray(s.derivative([w], u))                   # nDep 1: one array of N values
+        ref, bad = oracle.c_evaluate(order, ncoef, knots, coefs, [w], [u])
+        assert bad == -1 and out.shape == (100_000,) and ref.shape == (1, 100_000)
+        out = out[None, :]
+        observe(f"cfg1 bench size: derivative {w} vs oracle, fp64", np.abs(out - ref).max() / _scale(ref), 1e-12)
 
 
 @pytest.mark.parametrize("n", [50_000_000, 6_250_000, 70_000_000])
