@@ -19,6 +19,7 @@ from .device_spline import DeviceSpline, MultiDeviceSpline, bspline_values_batch
 from .device_spline import tessellate as tessellate_tables
 from .spline import Spline
 from .collocation import collocation_matrix
+from .fitting import least_squares
 from .spline_block import SplineBlock
 
 
@@ -36,6 +37,6 @@ def tessellate(splines, u, v, normals=True, normalize=True):
     tables = [_se.device_tables(s, dev) for s in splines]
     return tessellate_tables(tables, (u, v), normals=normals, normalize=normalize, negate=neg.pop() if neg else False)
 
-__all__ = ["Spline", "SplineBlock", "DeviceSpline", "MultiDeviceSpline", "tessellate", "collocation_matrix", "bspline_values_batch", "set_device", "get_device",
+__all__ = ["Spline", "SplineBlock", "DeviceSpline", "MultiDeviceSpline", "tessellate", "collocation_matrix", "least_squares", "bspline_values_batch", "set_device", "get_device",
            "BskError", "DomainError", "NativeLibraryError"]
 __version__ = "0.1.0"

@@ -1,0 +1,304 @@
+"""
+``Spline.least_squares`` (reference bspy/spline.py:1402 -> bspy/_spline_fitting.py:647-792): fit a tensor-product
+spline to gridded data, one independent variable at a time.
+
+For variable i the collocation matrix A (nRows x nCols, ``order`` non-zeros per row, ``collocation_matrix``) is the
+same for every line of the data along that variable; the lines are the right-hand sides.  The reference builds A
+densely and calls ``numpy.linalg.lstsq``.  Here the band of A is factored once on the host by row-sequential Givens
+rotations (the "plan", ``bsk_fit_create``; no normal equations) and the plan is applied to all lines at once:
+
+    device path   ``bsk_fit_sweep`` (fit_sweep: one lane per line) and ``bsk_fit_residual``; data, intermediate results
+                  and residuals stay on the device, only the nRows row norms come back per tolerance iteration
+    host plan     ``bsk_fit_solve_host``: the same plan applied on the CPU, for few lines (a curve has nDep lines)
+                  and for orders above 8
+    fallback      NumPy on the host, the reference's algebra: ``fixEnds=True`` (SVD null-space step) and
+                  rank-deficient systems (``lstsq`` minimum-norm solution).  Rare and small: correct, not fast.
+
+``least_squares(..., _path="device" | "host")`` (or ``fitting.FORCE_PATH``) pins the path of the plain solves;
+``fitting.LAST_PATHS`` lists what every solve of the last call ran ("fit_sweep", "fit_sweep turned", "host plan",
+"fallback").
+"""
+import ctypes
+
+import numpy as np
+
+from . import _native as nv
+from .collocation import collocation_matrix
+from .device_spline import _is_torch
+
+# Lines (right-hand sides) from which the device path is taken: the measured crossover of DESIGN.md section 12 (the
+# kernel's time does not depend on the line count up to ~16 k lines; the host plan costs ~5.5 us per line of 1024 rows).
+DEVICE_MIN_LINES = 48
+DEVICE_MAX_ORDER = 8
+FORCE_PATH = None          # None, "device" or "host"
+LAST_PATHS = []
+
+
+class Plan:
+    """Banded QR of one collocation matrix (``bsk_fit`` handle)."""
+
+    def __init__(self, first, values, ncols):
+        first = np.ascontiguousarray(first, np.int32)
+        values = np.ascontiguousarray(values, np.float64)
+        self.nrows, self.order = values.shape
+        self.ncols = int(ncols)
+        self.first, self.values = first, values
+        handle = ctypes.c_void_p()
+        nv.check(nv.lib().bsk_fit_create(self.nrows, self.ncols, self.order, first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                         values.ctypes.data, ctypes.byref(handle)))
+        self._handle = handle
+
+    def close(self):
+        if self._handle is not None:
+            nv.lib().bsk_fit_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rank_indicator(self):
+        """min |R_jj| / max |R_jj|."""
+        r = ctypes.c_double(0.0)
+        nv.check(nv.lib().bsk_fit_info(self._handle, None, ctypes.byref(r), None))
+        return r.value
+
+    def deficient(self):
+        return self.rank_indicator() < self.ncols * np.finfo(np.float64).eps
+
+    def r_band(self):
+        """(ncols, order): R[j, j + t]."""
+        band = np.empty((self.ncols, self.order), np.float64)
+        nv.check(nv.lib().bsk_fit_info(self._handle, None, None, band.ctypes.data))
+        return band
+
+    def last_kernel(self):
+        return nv.lib().bsk_fit_last_kernel(self._handle).decode()
+
+    def solve_host(self, b, outer, inner):
+        """b: NumPy (outer, nrows, inner) float32 / float64 -> (outer, ncols, inner) float64."""
+        b = np.ascontiguousarray(b)
+        if b.dtype != np.float32:
+            b = np.ascontiguousarray(b, np.float64)
+        x = np.empty((outer, self.ncols, inner), np.float64)
+        nv.check(nv.lib().bsk_fit_solve_host(self._handle, nv.dtype_code(b.dtype), b.ctypes.data, outer, inner, x.ctypes.data))
+        return x
+
+    def sweep(self, b, outer, inner):
+        """b: contiguous torch CUDA tensor of outer * nrows * inner float32 / float64 -> (outer, ncols, inner) float64."""
+        import torch
+        with torch.cuda.device(b.device):
+            x = torch.empty((outer, self.ncols, inner), dtype=torch.float64, device=b.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            nv.check(nv.lib().bsk_fit_sweep(self._handle, _torch_code(b), b.data_ptr(), outer, inner, x.data_ptr(), stream))
+        return x
+
+    def residual_rows(self, b, x, outer, inner):
+        """Sum over all lines of (b - A x)^2 for every row (NumPy, nrows), from device b and x."""
+        import torch
+        sumsq = np.empty(self.nrows, np.float64)
+        with torch.cuda.device(b.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            nv.check(nv.lib().bsk_fit_residual(self._handle, _torch_code(b), b.data_ptr(), x.data_ptr(), outer, inner,
+                                               sumsq.ctypes.data, stream))
+        return sumsq
+
+
+def _torch_code(t):
+    import torch
+    return nv.BSK_F32 if t.dtype == torch.float32 else nv.BSK_F64
+
+
+def residual_rows_host(first, values, b, x):
+    """Sum over all lines of (b - A x)^2 per row from the band of A; b (outer, nrows, inner), x (outer, ncols, inner)."""
+    r = np.array(b, np.float64)
+    for t in range(values.shape[1]):
+        r -= values[None, :, t, None] * x[:, first + t, :]
+    return np.einsum("orl,orl->r", r, r)
+
+
+def dense_matrix(first, values, ncols):
+    A = np.zeros((len(first), ncols), np.float64)
+    A[np.arange(len(first))[:, None], first[:, None] + np.arange(values.shape[1])[None, :]] = values
+    return A
+
+
+def fallback_solve(A, b, fixed_rows=()):
+    """The reference's dense algebra (bspy/_spline_fitting.py:753-771) for b of shape (nrows, lines): rows listed in
+    ``fixed_rows`` are interpolated (their part of the solution comes from the SVD of those rows, the rest is fitted
+    in their null space); everything else is the minimum-norm least-squares solution.  Returns (x, residual)."""
+    fixed_rows = list(fixed_rows)
+    if fixed_rows:
+        m = len(fixed_rows)
+        constraint, target = A[fixed_rows], b[fixed_rows]
+        free_A, free_b = np.delete(A, fixed_rows, 0), np.delete(b, fixed_rows, 0)
+        U, sigma, VT = np.linalg.svd(constraint)
+        scaled = (U.T @ target) / sigma[:m, None]
+        V = VT.T
+        particular = V[:, :m] @ scaled
+        null = V[:, m:]
+        inside, _, _, _ = np.linalg.lstsq(free_A @ null, free_b - free_A @ particular, rcond=None)
+        x = particular + null @ inside
+    else:
+        x, _, _, _ = np.linalg.lstsq(A, b, rcond=None)
+    return x, b - A @ x
+
+
+def auto_knots(u, order, compression):
+    """Knots of one variable when none are given (the reference's rule, :711-721): clamped ends at the first and last
+    parameter value, and int((n - order)(1 - compression) + 0.9999999999) interior knots at equally spaced fractional
+    positions of the parameter sequence, interpolated linearly between neighbouring parameter values."""
+    u = np.asarray(u, np.float64)
+    n = len(u)
+    lo, hi = np.min(u), np.max(u)
+    ends = np.array(order * [lo] + order * [hi])
+    count = int((n - order) * (1.0 - compression) + 0.9999999999)
+    spots = np.linspace(0.0, n - 1.0, count + 2)[1:-1]
+    interior = []
+    for spot in spots:
+        i = int(spot)
+        alpha = spot - i
+        interior.append((1.0 - alpha) * u[i] + alpha * u[i + 1])
+    return np.sort(np.append(ends, interior))
+
+
+def _is_spline_input(data):
+    flat = np.ravel(data)
+    return flat.dtype == object and flat.size > 0 and all(hasattr(flat[0], a) for a in ("nInd", "nDep", "knots", "coefs"))
+
+
+def _to_device(a):
+    import torch
+    if _is_torch(a):
+        return a
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _to_host(a):
+    if _is_torch(a):
+        return a.detach().cpu().numpy()
+    return a
+
+
+def _solve_variable(first, values, ncols, data, outer, nrows, inner, want_norms, fix_rows, path):
+    """One solve of one variable: data viewed as (outer, nrows, inner) -> ((outer, ncols, inner), row sums of squares or None)."""
+    lines = outer * inner
+    order = values.shape[1]
+    plan = Plan(first, values, ncols)
+    try:
+        if fix_rows or plan.deficient():
+            b = np.asarray(_to_host(data), np.float64).reshape(outer, nrows, inner)
+            flat = np.moveaxis(b, 1, 0).reshape(nrows, lines)
+            x, resid = fallback_solve(dense_matrix(first, values, ncols), flat, fix_rows)
+            LAST_PATHS.append("fallback")
+            x = np.ascontiguousarray(np.moveaxis(x.reshape(ncols, outer, inner), 0, 1))
+            return x, (np.einsum("rl,rl->r", resid, resid) if want_norms else None)
+        if path is None:
+            path = "device" if order <= DEVICE_MAX_ORDER and lines >= DEVICE_MIN_LINES else "host"
+        if path == "device":
+            if order > DEVICE_MAX_ORDER:
+                raise ValueError(f"the device path covers orders up to {DEVICE_MAX_ORDER}")
+            b = _to_device(data).contiguous()
+            x = plan.sweep(b, outer, inner)
+            LAST_PATHS.append(plan.last_kernel())
+            return x, (plan.residual_rows(b, x, outer, inner) if want_norms else None)
+        b = _to_host(data).reshape(outer, nrows, inner)
+        x = plan.solve_host(b, outer, inner)
+        LAST_PATHS.append(plan.last_kernel())
+        return x, (residual_rows_host(first, values, b, x) if want_norms else None)
+    finally:
+        plan.close()
+
+
+def least_squares(uValues, dataPoints, order=None, knots=None, compression=0.0, tolerance=None, fixEnds=False,
+                  metadata={}, _path=None):
+    from .spline import Spline
+
+    path = _path if _path is not None else FORCE_PATH
+    if path not in (None, "device", "host"):
+        raise ValueError("_path must be None, 'device' or 'host'")
+    del LAST_PATHS[:]
+
+    if _is_torch(dataPoints):
+        import torch
+        data = dataPoints
+        if data.dtype not in (torch.float32, torch.float64):
+            data = data.to(torch.float64)
+        if not data.is_cuda:
+            data = data.numpy()
+    else:
+        data = np.array(dataPoints)
+        if _is_spline_input(data):
+            raise NotImplementedError("least_squares of Spline-valued dataPoints is not implemented by bspy_amd "
+                                      "(it needs common_basis / fold / unfold)")
+        if data.dtype != np.float32:
+            data = data.astype(np.float64)
+
+    # parameter values (reference :674-685)
+    if np.isscalar(uValues[0]):
+        uValues = [uValues]
+    nInd = len(uValues)
+    uValues = [np.asarray(_to_host(u), np.float64) for u in uValues]
+    domain = []
+    for u in uValues:
+        domain.append((np.min(u), np.max(u)))
+        if np.any(u[:-1] > u[1:]):
+            raise ValueError("Independent variable values are out of order")
+
+    # data points (:689-695)
+    if len(data.shape) != nInd + 1:
+        raise ValueError("dataPoints has the wrong shape")
+    nDep = int(data.shape[0])
+    extents = [int(n) for n in data.shape[1:]]
+    for n, u in zip(extents, uValues):
+        if n != len(u):
+            raise ValueError("Wrong number of parameter values in one or more directions")
+
+    # order (:699-702)
+    if order is None:
+        order = [min(4, n) for n in extents]
+    order = [int(o) for o in order]
+    for n, o in zip(extents, order):
+        if n < o:
+            raise ValueError("Not enough points in one or more directions")
+
+    # knots (:706-726)
+    if not (0.0 <= compression <= 1.0):
+        raise ValueError("compression not between 0.0 and 1.0")
+    if tolerance is not None:
+        compression = 1.0
+    if knots is None:
+        knots = [auto_knots(u, o, compression) for u, o in zip(uValues, order)]
+    else:
+        knots = [np.array(k, np.float64) for k in knots]
+    for (lo, hi), k, o in zip(domain, knots, order):
+        if lo < k[o - 1] or hi > k[-o]:
+            raise ValueError("One or more dataPoints are outside the domain of the spline")
+
+    shape = [nDep] + extents
+    for iInd in range(nInd):
+        u, o = uValues[iInd], order[iInd]
+        nrows = shape[iInd + 1]
+        outer = int(np.prod(shape[:iInd + 1], dtype=np.int64))
+        inner = int(np.prod(shape[iInd + 2:], dtype=np.int64))
+        fix_rows = [r for r in range(nrows) if u[r] == u[0] or u[r] == u[-1]] if fixEnds else []
+        while True:
+            ncols = len(knots[iInd]) - o
+            first, values = collocation_matrix(knots[iInd], o, u, dense=False)
+            x, sumsq = _solve_variable(first, np.asarray(values, np.float64), ncols, data, outer, nrows, inner,
+                                       tolerance is not None, fix_rows, path)
+            if tolerance is None:
+                break
+            norms = np.sqrt(sumsq)
+            worst = int(np.argmax(norms))           # first of the largest, as the reference's strict comparison
+            if norms[worst] <= tolerance / nInd:
+                break
+            k = knots[iInd]
+            ix = min(int(np.searchsorted(k, u[worst], "right")), ncols)
+            knots[iInd] = np.sort(np.append(k, 0.5 * (k[ix - 1] + k[ix])))
+        data = x
+        shape[iInd + 1] = ncols
+    coefs = np.ascontiguousarray(np.asarray(_to_host(data), np.float64).reshape(shape))
+    return Spline(nInd, nDep, order, shape[1:], knots, coefs, metadata=metadata)

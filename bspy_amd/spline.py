@@ -11,10 +11,12 @@ error messages for
     s.normal(uvw, normalize=True, indices=None)                   spline.py:1648-1682
     s.integral(integrand=None, domain=None)                       spline.py:1249 (nInd 1 - 3)
     Spline.bspline_values(knot, knots, splineOrder, u, ...)       spline.py:207-252
+    Spline.least_squares(uValues, dataPoints, order, knots, ...)  spline.py:1402 (gridded data; not Spline-valued data)
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
-rest of the reference's Spline API (fitting, intersection, CSG, viewer) is out of scope.
+rest of the reference's Spline API (the other fitting calls - fit, contour, solve_ode, ... -, intersection, CSG,
+viewer) is out of scope.
 
 Documented deviations from the reference:
   * all-integer knots / coefs are promoted to float64 (the reference keeps int64 and
@@ -209,6 +211,28 @@ class Spline:
         nInd 1 to 3 only: nInd >= 4 raises NotImplementedError (deliberate scope)."""
         from . import integral as _integral
         return _integral.integral(self, integrand, domain)
+
+    @staticmethod
+    def least_squares(uValues, dataPoints, order=None, knots=None, compression=0.0, tolerance=None, fixEnds=False,
+                      metadata={}, **kwargs):
+        """Least-squares fit of a spline to gridded data (reference spline.py:1402, its signature, defaults, checks
+        and ValueError messages).  Returns a Spline with float64 knots and coefficients.
+
+        uValues: the parameter values, one array (nInd 1) or nInd arrays, each non-decreasing; a repeated value
+        means the next derivative at that parameter (Hermite data).  dataPoints: shape (nDep, N0, ..., N_{nInd-1}),
+        NumPy float32 / float64 or a torch CUDA tensor of those types, which is used where it is (float32 is read
+        as float32 and computed in float64).  order defaults to min(4, N_i) per variable; knots default to the
+        reference's rule: clamped ends and int((N_i - order)(1 - compression) + 0.9999999999) interior knots.
+        tolerance: fit to tolerance - start without interior knots, and while the largest 2-norm of a residual
+        row exceeds tolerance / nInd insert the midpoint knot of that row's span and solve again.
+
+        Each variable is one banded Givens QR (no normal equations), factored once on the host and applied to all
+        lines of the data by a GPU kernel; few lines (curves) and orders above 8 apply it on the host.  Results are
+        bitwise reproducible.  Deliberate scope: fixEnds=True and rank-deficient systems are solved on the host with
+        the reference's dense algebra (correct, not fast); dataPoints made of Spline objects raises
+        NotImplementedError.  ``_path="device"`` / ``"host"`` pins the path (tests, measurements)."""
+        from . import fitting as _fitting
+        return _fitting.least_squares(uValues, dataPoints, order, knots, compression, tolerance, fixEnds, metadata, **kwargs)
 
     def tangent_space(self, uvw):
         """Same as jacobian (reference spline.py:2238-2252)."""

@@ -179,6 +179,40 @@ bsk_status bsk_integral(bsk_spline s, int mode, const void *lo_hi, const int32_t
                         void *stream);
 
 /*
+ * Least-squares fit of gridded data, one variable at a time (Spline.least_squares, bspy_amd/fitting.py).
+ * Replaces: the dense matrix + numpy.linalg.lstsq of least_squares, bspy/_spline_fitting.py:736-770 (bspy/spline.py:1402).
+ * A bsk_fit handle, the "plan", holds the banded QR of one collocation matrix A (nrows x ncols, `order` non-zeros per row):
+ * row-sequential Givens rotations, recorded once on the host, then applied to any number of right-hand sides.
+ *   first[r]   : column of the first non-zero of row r, non-decreasing, 0 <= first[r] <= ncols - order
+ *   values     : nrows * order matrix entries, values[r * order + t] = A[r][first[r] + t]
+ * bsk_fit_create makes no HIP call.  bsk_fit_info reports ncols, the rank indicator min |R_jj| / max |R_jj| (0 when R is
+ * singular: the solve calls then return BSK_ERR_INVALID) and, when r_band is not NULL, the ncols * order band of R,
+ * r_band[j * order + t] = R[j][j + t].  Any of the three pointers may be NULL.
+ * The data of a solve is viewed as b[outer][nrows][inner] (dtype BSK_F32 or BSK_F64, computed in fp64); the result is
+ * x[outer][ncols][inner], fp64: one "line" per (outer, inner) pair.
+ *   bsk_fit_solve_host : host buffers, the plan applied on the CPU (few lines; also the statement of what the kernel
+ *                        computes).  Any order up to BSK_MAX_ORDER.
+ *   bsk_fit_sweep      : device buffers on the current device, kernels enqueued on `stream` (fit_sweep: one lane per
+ *                        line; lines that are contiguous in memory, inner == 1, are turned through an LDS tile first).
+ *                        Orders above 8 return BSK_ERR_UNSUPPORTED.  The plan's tables are uploaded by the first device
+ *                        call; a workspace of the plan grows when a call needs more than any call before it.
+ *   bsk_fit_residual   : device b and x as above; sumsq (host, nrows values) receives for every row the sum over all
+ *                        lines of (b - A x)^2, summed in a fixed order (no atomics).  Synchronises `stream`.
+ *   bsk_fit_last_kernel: "fit_sweep", "fit_sweep turned", "fit_residual", "fit_residual turned" or "host plan": the
+ *                        path the most recent solve / residual call on this plan took.
+ * A plan is used from one thread and one stream at a time.
+ */
+typedef struct bsk_fit_s *bsk_fit;
+bsk_status bsk_fit_create(int nrows, int ncols, int order, const int32_t *first, const double *values, bsk_fit *out);
+bsk_status bsk_fit_destroy(bsk_fit p);
+bsk_status bsk_fit_info(bsk_fit p, int *ncols, double *rank_indicator, double *r_band);
+bsk_status bsk_fit_solve_host(bsk_fit p, bsk_dtype dtype, const void *b, int64_t outer, int64_t inner, double *x);
+bsk_status bsk_fit_sweep(bsk_fit p, bsk_dtype dtype, const void *b, int64_t outer, int64_t inner, double *x, void *stream);
+bsk_status bsk_fit_residual(bsk_fit p, bsk_dtype dtype, const void *b, const double *x, int64_t outer, int64_t inner,
+                            double *sumsq, void *stream);
+const char *bsk_fit_last_kernel(bsk_fit p);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
