@@ -344,36 +344,30 @@ static Plan make_plan(bsk_spline s, long long n)
     else if (p.lds_bytes > limit / 4) { p.block = 1024; per_cu = 2; }
     else if (p.lds_bytes > limit / 8) { p.block = 512; per_cu = 4; }
     else { p.block = 256; per_cu = 8; }
-    long long blocks = (n + p.block - 1) / p.block;
-    p.grid = (int)std::max<long long>(1, std::min<long long>(blocks, (long long)s->num_cu * per_cu));
+    p.grid = persistent_grid(s, (n + p.block - 1) / p.block, per_cu);
     return p;
+}
+
+template <typename T>
+static bsk_status launch_eval_generic(bsk_spline s, const Params<T> &prm, long long n, T *out, long long ostride,
+                                      const Wrt &w, hipStream_t st)
+{
+    const int block = 256;
+    return launch(s, "eval_generic", eval_generic<T>, dim3(persistent_grid(s, (n + block - 1) / block, 8)), dim3(block), 0, st,
+                  desc_of<T>(s),
+                  static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, ostride, w, s->bad);
 }
 
 template <typename T, int NIND, int O>
 static bsk_status launch_eval_fixed(bsk_spline s, const Plan &p, const Params<T> &prm, long long n, T *out,
                                     long long ostride, const Wrt &w, hipStream_t st)
 {
-    const Desc<T> &d = desc_of<T>(s);
-    const T *tab = static_cast<const T *>(s->tab);
-    const T *coef = static_cast<const T *>(s->coef);
-    if (p.lds_coefs) {
-        HIPCHK(allow_lds(eval_fixed<T, NIND, O, true>, p.lds_bytes));
-        s->last_kernel = "eval_fixed";
-        hipLaunchKernelGGL((eval_fixed<T, NIND, O, true>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, ostride, w, s->bad);
-    } else {
-        HIPCHK(allow_lds(eval_fixed<T, NIND, O, false>, p.lds_bytes));
-        s->last_kernel = "eval_fixed";
-        hipLaunchKernelGGL((eval_fixed<T, NIND, O, false>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, ostride, w, s->bad);
-    }
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    return with_bool(p.lds_coefs, [&](auto lc) {
+        return launch(s, "eval_fixed", eval_fixed<T, NIND, O, decltype(lc)::value>, dim3(p.grid), dim3(p.block), p.lds_bytes,
+                      st, desc_of<T>(s),
+                      static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, ostride, w, s->bad);
+    });
 }
-
-template <typename T>
-static bsk_status launch_eval_generic(bsk_spline s, const Params<T> &prm, long long n, T *out, long long ostride,
-                                      const Wrt &w, hipStream_t st);
 
 // Variables of different orders (or one order beyond the fixed-order kernels): eval_mixed at OMAX = the
 // largest order - surfaces up to order 8, volumes up to 6, curves 9..12.
@@ -381,69 +375,31 @@ template <typename T, int NIND, int OMAX>
 static bsk_status launch_eval_mixed(bsk_spline s, const Plan &p, const Params<T> &prm, long long n, T *out,
                                     long long ostride, const Wrt &w, hipStream_t st)
 {
-    const Desc<T> &d = desc_of<T>(s);
-    const T *tab = static_cast<const T *>(s->tab);
-    const T *coef = static_cast<const T *>(s->coef);
-    if (p.lds_coefs) {
-        HIPCHK(allow_lds(eval_mixed<T, NIND, OMAX, true>, p.lds_bytes));
-        s->last_kernel = "eval_mixed";
-        hipLaunchKernelGGL((eval_mixed<T, NIND, OMAX, true>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, ostride, w, s->bad);
-    } else if constexpr (NIND >= 4) {
-        // four and five variables: only the LDS-resident form is instantiated (build time); larger tables
-        // stay on the generic kernel
-        return launch_eval_generic<T>(s, prm, n, out, ostride, w, st);
-    } else {
-        HIPCHK(allow_lds(eval_mixed<T, NIND, OMAX, false>, p.lds_bytes));
-        s->last_kernel = "eval_mixed";
-        hipLaunchKernelGGL((eval_mixed<T, NIND, OMAX, false>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, ostride, w, s->bad);
-    }
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    auto go = [&](auto lc) {
+        return launch(s, "eval_mixed", eval_mixed<T, NIND, OMAX, decltype(lc)::value>, dim3(p.grid), dim3(p.block), p.lds_bytes,
+                      st, desc_of<T>(s),
+                      static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, ostride, w, s->bad);
+    };
+    // four and five variables: only the LDS-resident form is instantiated (build time); larger tables
+    // stay on the generic kernel
+    if constexpr (NIND >= 4) return p.lds_coefs ? go(std::true_type{}) : launch_eval_generic<T>(s, prm, n, out, ostride, w, st);
+    else return with_bool(p.lds_coefs, go);
 }
 
 template <typename T, int NIND, int O>
 static bsk_status launch_jac_fixed(bsk_spline s, const Plan &p, const Params<T> &prm, long long n, T *out,
                                    hipStream_t st)
 {
-    const Desc<T> &d = desc_of<T>(s);
-    const T *tab = static_cast<const T *>(s->tab);
-    const T *coef = static_cast<const T *>(s->coef);
-    if (p.lds_coefs) {
-        HIPCHK(allow_lds(jac_fixed<T, NIND, O, true>, p.lds_bytes));
-        s->last_kernel = "jac_fixed";
-        hipLaunchKernelGGL((jac_fixed<T, NIND, O, true>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, s->bad);
-    } else {
-        HIPCHK(allow_lds(jac_fixed<T, NIND, O, false>, p.lds_bytes));
-        s->last_kernel = "jac_fixed";
-        hipLaunchKernelGGL((jac_fixed<T, NIND, O, false>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef,
-                           prm, n, out, s->bad);
-    }
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
-}
-
-template <typename T>
-static bsk_status launch_eval_generic(bsk_spline s, const Params<T> &prm, long long n, T *out, long long ostride,
-                                      const Wrt &w, hipStream_t st)
-{
-    const Desc<T> &d = desc_of<T>(s);
-    const int block = 256;
-    const long long blocks = (n + block - 1) / block;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(blocks, (long long)s->num_cu * 8));
-    s->last_kernel = "eval_generic";
-    hipLaunchKernelGGL((eval_generic<T>), dim3(grid), dim3(block), 0, st, d, static_cast<const T *>(s->tab),
-                       static_cast<const T *>(s->coef), prm, n, out, ostride, w, s->bad);
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    return with_bool(p.lds_coefs, [&](auto lc) {
+        return launch(s, "jac_fixed", jac_fixed<T, NIND, O, decltype(lc)::value>, dim3(p.grid), dim3(p.block), p.lds_bytes, st,
+                      desc_of<T>(s), static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, s->bad);
+    });
 }
 
 // LDS-resident kernels: bytes of the table image (axis tables, bucket tables, coefficients),
 // or 0 when it does not fit in one CU's LDS.
 template <typename T>
-static size_t tile_lds_bytes(bsk_spline s, bool /*unused*/)
+static size_t tile_lds_bytes(bsk_spline s)
 {
     const TileDesc<T> &td = tile_of<T>(s);
     const size_t b = (size_t)td.tab_bytes + td.lut_bytes + td.coef_bytes;
@@ -452,7 +408,16 @@ static size_t tile_lds_bytes(bsk_spline s, bool /*unused*/)
     return b <= s->lds_max ? b : 0;
 }
 
-static bool has_fixed_path(bsk_spline s);
+static size_t tile_lds_bytes_any(bsk_spline s)
+{
+    return s->dtype == BSK_F32 ? tile_lds_bytes<float>(s) : tile_lds_bytes<double>(s);
+}
+
+// Fast-path coverage: nInd 1..3, one common order 1..6.
+static bool has_fixed_path(bsk_spline s)
+{
+    return s->same_order && s->nInd >= 1 && s->nInd <= 3 && s->order[0] >= 1 && s->order[0] <= 6;
+}
 
 // eval_rowrot / jac_rowrot / fused normal: surfaces of order 2 or 4 whose odd-stride image fits LDS
 // Points per launch of the rowrot kernels (32-bit indices).  BSK_RR_CHUNK lowers it so that the
@@ -465,6 +430,20 @@ static long long rr_chunk_points()
         return x > 0 && x < (long long)RR_MAX_CHUNK ? x : (long long)RR_MAX_CHUNK;
     }();
     return v;
+}
+
+// 32-bit point indices inside a launch of the rowrot family: fn(cp, m, n0) for chunks of at most
+// rr_chunk_points() points, cp = the parameter rows from point n0 on.
+template <typename T, typename F>
+static bsk_status for_rr_chunks(bsk_spline s, const Params<T> &prm, long long n, F &&fn)
+{
+    const long long cmax = rr_chunk_points();
+    for (long long n0 = 0; n0 < n; n0 += cmax) {
+        Params<T> cp = prm;
+        for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
+        if (const bsk_status r = fn(cp, std::min<long long>(n - n0, cmax), n0); r != BSK_OK) return r;
+    }
+    return BSK_OK;
 }
 
 template <typename T>
@@ -595,9 +574,6 @@ static void unclamp_axis(std::vector<long double> &w, size_t outer, int nc, size
 }
 
 template <typename T>
-static bool rowrot_applies(bsk_spline s);
-
-template <typename T>
 static bsk_status upload_uniform(bsk_spline s, const void *const *knots, const void *coefs)
 {
     s->uni = false;
@@ -674,7 +650,6 @@ static bsk_status upload_uniform(bsk_spline s, const void *const *knots, const v
 // Unclamping a variable multiplies the rounding errors of its boundary control points by the largest absolute row
 // sum of its matrix; the path is taken while the product over the variables stays below 5000 (three variables of
 // order 5 exceed it) and, as for surfaces, in fp64 only unless nothing has to be unclamped (order <= 2).
-static size_t tile_lds_bytes_any(bsk_spline s);
 template <typename T>
 static bsk_status upload_uniform_nd(bsk_spline s, const void *const *knots, const void *coefs)
 {
@@ -741,74 +716,44 @@ static bsk_status upload_uniform_nd(bsk_spline s, const void *const *knots, cons
     return BSK_OK;
 }
 
+// Grid of one launch of the rowrot family: a workgroup per tile of m points, as many per CU as LDS images fit.
+static dim3 rr_grid(bsk_spline s, long long m, size_t lds)
+{
+    return dim3(persistent_grid(s, (m + TILE - 1) / TILE, lds_per_cu(s, lds)));
+}
+
+// The number of dependent variables is a template constant up to 3 (0 = run-time loop) in jac_uni / jac_rowrot;
+// the fused normal (NORMAL) instantiates one class of each.
 template <typename T, bool NORMAL>
 static bsk_status launch_jac_rowrot(bsk_spline s, const Params<T> &prm, long long n, T *out, int normalize, int negate,
                                     hipStream_t st)
 {
-    const Desc<T> &d = desc_of<T>(s);
-    const TileDesc<T> &tdr = tile_of<T>(s);
-    const size_t lds_rr = rowrot_lds_bytes<T>(s);
-    const T *tab = static_cast<const T *>(s->tab);
-    const T *coef = static_cast<const T *>(s->coef);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_rr));
-    if (s->uni) {
-        // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
-        const UniDesc<T> &ud = uni_of<T>(s);
-        const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
-        const int per_cu_u = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_u));
-#define BSK_JUNI(O_, ND_)                                                                                               \
-    do {                                                                                                                 \
-        s->last_kernel = "jac_uni";                                        \
-        HIPCHK(allow_lds(jac_uni<T, O_, NORMAL, ND_>, lds_u));                                                          \
-        hipLaunchKernelGGL((jac_uni<T, O_, NORMAL, ND_>), dim3(g), dim3(TILE), lds_u, st, ud, s->uni_img.p, cp,         \
-                           (unsigned)m, n0, out + n0, n, s->bad, normalize, negate);                                    \
-    } while (0)
-        const int ndu = (NORMAL || s->nDep > 3) ? 0 : s->nDep;
-        const long long cmaxu = rr_chunk_points();
-        for (long long n0 = 0; n0 < n; n0 += cmaxu) {
-            const long long m = std::min<long long>(n - n0, cmaxu);
-            const int g = (int)std::max<long long>(1, std::min<long long>((m + TILE - 1) / TILE, (long long)s->num_cu * per_cu_u));
-            Params<T> cp = prm;
-            for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
-            if (s->order[0] == 4) {
-                if constexpr (NORMAL) BSK_JUNI(4, 3);
-                else switch (ndu) { case 1: BSK_JUNI(4, 1); break; case 2: BSK_JUNI(4, 2); break; case 3: BSK_JUNI(4, 3); break; default: BSK_JUNI(4, 0); }
-            } else {
-                if constexpr (NORMAL) BSK_JUNI(2, 3);
-                else switch (ndu) { case 1: BSK_JUNI(2, 1); break; case 2: BSK_JUNI(2, 2); break; case 3: BSK_JUNI(2, 3); break; default: BSK_JUNI(2, 0); }
-            }
-            HIPCHK(hipGetLastError());
+    return with_int<4, 2>(s->order[0], [&](auto o) {
+        constexpr int O = decltype(o)::value;
+        if (s->uni) {
+            // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
+            const UniDesc<T> &ud = uni_of<T>(s);
+            const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
+            auto go = [&](auto nd) {
+                return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
+                    return launch(s, "jac_uni", jac_uni<T, O, NORMAL, decltype(nd)::value>, rr_grid(s, m, lds_u), dim3(TILE),
+                                  lds_u, st, ud, s->uni_img.p, cp, (unsigned)m, n0, out + n0, n, s->bad, normalize, negate);
+                });
+            };
+            if constexpr (NORMAL) return go(std::integral_constant<int, 3>{});
+            else return with_int<1, 2, 3, 0>(s->nDep, go);
         }
-#undef BSK_JUNI
-        return BSK_OK;
-    }
-#define BSK_JROT(O_, ND_)                                                                                               \
-    do {                                                                                                                 \
-        s->last_kernel = "jac_rowrot";                                        \
-        HIPCHK(allow_lds(jac_rowrot<T, O_, NORMAL, ND_>, lds_rr));                                                      \
-        hipLaunchKernelGGL((jac_rowrot<T, O_, NORMAL, ND_>), dim3(g), dim3(TILE), lds_rr, st, d, tdr, tab, s->lut, coef, \
-                           cp, (unsigned)m, n0, out + n0, n, s->bad, normalize, negate);                                \
-    } while (0)
-    // the number of dependent variables is a template constant up to 3 (0 = run-time loop)
-    const int nd = (NORMAL || s->nDep > 3) ? 0 : s->nDep;
-    // 32-bit point indices inside a launch: chunks of at most RR_MAX_CHUNK points
-    const long long cmax = rr_chunk_points();
-    for (long long n0 = 0; n0 < n; n0 += cmax) {
-        const long long m = std::min<long long>(n - n0, cmax);
-        const int g = (int)std::max<long long>(1, std::min<long long>((m + TILE - 1) / TILE, (long long)s->num_cu * per_cu));
-        Params<T> cp = prm;
-        for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
-        if (s->order[0] == 4) {
-            if constexpr (NORMAL) BSK_JROT(4, 0);
-            else switch (nd) { case 1: BSK_JROT(4, 1); break; case 2: BSK_JROT(4, 2); break; case 3: BSK_JROT(4, 3); break; default: BSK_JROT(4, 0); }
-        } else {
-            if constexpr (NORMAL) BSK_JROT(2, 0);
-            else switch (nd) { case 1: BSK_JROT(2, 1); break; case 2: BSK_JROT(2, 2); break; case 3: BSK_JROT(2, 3); break; default: BSK_JROT(2, 0); }
-        }
-        HIPCHK(hipGetLastError());
-    }
-#undef BSK_JROT
-    return BSK_OK;
+        const size_t lds_rr = rowrot_lds_bytes<T>(s);
+        auto go = [&](auto nd) {
+            return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
+                return launch(s, "jac_rowrot", jac_rowrot<T, O, NORMAL, decltype(nd)::value>, rr_grid(s, m, lds_rr), dim3(TILE),
+                              lds_rr, st, desc_of<T>(s), tile_of<T>(s), static_cast<const T *>(s->tab), s->lut,
+                              static_cast<const T *>(s->coef), cp, (unsigned)m, n0, out + n0, n, s->bad, normalize, negate);
+            });
+        };
+        if constexpr (NORMAL) return go(std::integral_constant<int, 0>{});
+        else return with_int<1, 2, 3, 0>(s->nDep, go);
+    });
 }
 
 template <typename T, int NIND, int O>
@@ -822,153 +767,58 @@ static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm
     bool deriv = false;
     for (int iv = 0; iv < s->nInd; ++iv) deriv |= w.w[iv] != 0;
     const long long ntiles = (n + TILE - 1) / TILE;
-    if constexpr (NIND == 2 && (O == 2 || O == 4)) {
-        // surfaces of order 2 / 4: row rotation on an odd-stride LDS image
-        if (rowrot_applies<T>(s)) {
-            if (s->uni) {
+    return with_bool(deriv, [&](auto dv) {
+        constexpr bool DERIV = decltype(dv)::value;
+        if constexpr (NIND == 2 && (O == 2 || O == 4)) {
+            // surfaces of order 2 / 4: row rotation on an odd-stride LDS image
+            if (rowrot_applies<T>(s)) {
+                if (s->uni) {
+                    // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
+                    const UniDesc<T> &ud = uni_of<T>(s);
+                    const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
+                    return with_int<1, 2, 3, 0>(s->nDep, [&](auto nd) {     // 0 = run-time loop
+                        return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
+                            return launch(s, "eval_uni", eval_uni<T, O, DERIV, decltype(nd)::value>, rr_grid(s, m, lds_u),
+                                          dim3(TILE), lds_u, st, ud, s->uni_img.p, cp, (unsigned)m, n0, out + n0, ostride, w,
+                                          s->bad);
+                        });
+                    });
+                }
+                if constexpr (sizeof(T) == 4 && O == 4) {
+                    // fp32 bicubics: everything in 16-byte LDS reads (bsk_rec32.hpp); BSK_VARIANT=9 keeps eval_rowrot
+                    const size_t lds_r = r32_lds_bytes(s->ncoef[0] - 3, s->ncoef[1] - 3, td.lut_len, s->ncoef[0], s->ncoef[1]);
+                    if (s->variant == 0 && s->nDep >= 1 && s->nDep <= 4 && lds_r + 256 <= s->lds_max)
+                        return with_int<1, 2, 3, 4>(s->nDep, [&](auto nd) {
+                            return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
+                                return launch(s, "eval_rec32", eval_rec32<DERIV, decltype(nd)::value>, rr_grid(s, m, lds_r),
+                                              dim3(TILE), lds_r, st, d, td, tab, s->lut, coef, cp, (unsigned)m, n0, out + n0,
+                                              ostride, w, s->bad);
+                            });
+                        });
+                }
+                const size_t lds_rr = rowrot_lds_bytes<T>(s);
+                return with_int<1, 2, 3, 0>(s->nDep, [&](auto nd) {         // 0 = run-time loop
+                    return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
+                        return launch(s, "eval_rowrot", eval_rowrot<T, O, DERIV, decltype(nd)::value>, rr_grid(s, m, lds_rr),
+                                      dim3(TILE), lds_rr, st, d, td, tab, s->lut, coef, cp, (unsigned)m, n0, out + n0, ostride,
+                                      w, s->bad);
+                    });
+                });
+            }
+        }
+        if constexpr (O <= 5) {
+            if (s->uniN) {
                 // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
-                const UniDesc<T> &ud = uni_of<T>(s);
-                const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
-                const int per_cu_u = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_u));
-#define BSK_UNI(DERIV_, ND_)                                                                                             \
-    do {                                                                                                                 \
-        s->last_kernel = "eval_uni";                                        \
-        HIPCHK(allow_lds(eval_uni<T, O, DERIV_, ND_>, lds_u));                                                          \
-        hipLaunchKernelGGL((eval_uni<T, O, DERIV_, ND_>), dim3(g), dim3(TILE), lds_u, st, ud, s->uni_img.p, cp,         \
-                           (unsigned)m, n0, out + n0, ostride, w, s->bad);                                              \
-    } while (0)
-#define BSK_UNI_ND(DERIV_)                                                                                               \
-    switch (s->nDep) {                                                                                                   \
-    case 1: BSK_UNI(DERIV_, 1); break;                                                                                   \
-    case 2: BSK_UNI(DERIV_, 2); break;                                                                                   \
-    case 3: BSK_UNI(DERIV_, 3); break;                                                                                   \
-    default: BSK_UNI(DERIV_, 0); break;                                                                                  \
-    }
-                const long long cmaxu = rr_chunk_points();
-                for (long long n0 = 0; n0 < n; n0 += cmaxu) {
-                    const long long m = std::min<long long>(n - n0, cmaxu);
-                    const int g = (int)std::max<long long>(1, std::min<long long>((m + TILE - 1) / TILE, (long long)s->num_cu * per_cu_u));
-                    Params<T> cp = prm;
-                    for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
-                    if (deriv) { BSK_UNI_ND(true); } else { BSK_UNI_ND(false); }
-                    HIPCHK(hipGetLastError());
-                }
-#undef BSK_UNI_ND
-#undef BSK_UNI
-                return BSK_OK;
+                const UniDescN<T> &un = uniN_of<T>(s);
+                const size_t lds_u = un.img_bytes;
+                return launch(s, "eval_stream_uni", eval_stream_uni<T, NIND, O, DERIV>,
+                              dim3(persistent_grid(s, ntiles, lds_per_cu(s, lds_u))), dim3(STREAM_BLOCK), lds_u, st, d, un,
+                              s->uni_img.p, prm, n, out, ostride, w, s->bad);
             }
-            if constexpr (sizeof(T) == 4 && O == 4) {
-                // fp32 bicubics: everything in 16-byte LDS reads (bsk_rec32.hpp); BSK_VARIANT=9 keeps eval_rowrot
-                const size_t lds_r = r32_lds_bytes(s->ncoef[0] - 3, s->ncoef[1] - 3, td.lut_len, s->ncoef[0], s->ncoef[1]);
-                if (s->variant == 0 && s->nDep >= 1 && s->nDep <= 4 && lds_r + 256 <= s->lds_max) {
-                    const int per_cu_r = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_r));
-#define BSK_R32(DERIV_, ND_)                                                                                             \
-    do {                                                                                                                 \
-        HIPCHK(allow_lds(eval_rec32<DERIV_, ND_>, lds_r));                                                              \
-        hipLaunchKernelGGL((eval_rec32<DERIV_, ND_>), dim3(g), dim3(TILE), lds_r, st, d, td, tab, s->lut, coef, cp,     \
-                           (unsigned)m, n0, out + n0, ostride, w, s->bad);                                              \
-    } while (0)
-#define BSK_R32_ND(DERIV_)                                                                                               \
-    switch (s->nDep) {                                                                                                   \
-    case 1: BSK_R32(DERIV_, 1); break;                                                                                   \
-    case 2: BSK_R32(DERIV_, 2); break;                                                                                   \
-    case 3: BSK_R32(DERIV_, 3); break;                                                                                   \
-    default: BSK_R32(DERIV_, 4); break;                                                                                  \
-    }
-                    s->last_kernel = "eval_rec32";
-                    const long long cmaxr = rr_chunk_points();
-                    for (long long n0 = 0; n0 < n; n0 += cmaxr) {
-                        const long long m = std::min<long long>(n - n0, cmaxr);
-                        const int g = (int)std::max<long long>(1, std::min<long long>((m + TILE - 1) / TILE, (long long)s->num_cu * per_cu_r));
-                        Params<T> cp = prm;
-                        for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
-                        if (deriv) { BSK_R32_ND(true); } else { BSK_R32_ND(false); }
-                        HIPCHK(hipGetLastError());
-                    }
-#undef BSK_R32_ND
-#undef BSK_R32
-                    return BSK_OK;
-                }
-            }
-            const size_t lds_rr = rowrot_lds_bytes<T>(s);
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_rr));
-            // the number of dependent variables is a template constant up to 3 (0 = run-time loop)
-#define BSK_ROWROT(DERIV_, ND_)                                                                                          \
-    do {                                                                                                                 \
-        s->last_kernel = "eval_rowrot";                                        \
-        HIPCHK(allow_lds(eval_rowrot<T, O, DERIV_, ND_>, lds_rr));                                                      \
-        hipLaunchKernelGGL((eval_rowrot<T, O, DERIV_, ND_>), dim3(g), dim3(TILE), lds_rr, st, d, td, tab, s->lut, coef, \
-                           cp, (unsigned)m, n0, out + n0, ostride, w, s->bad);                                          \
-    } while (0)
-#define BSK_ROWROT_ND(DERIV_)                                                                                            \
-    switch (s->nDep) {                                                                                                   \
-    case 1: BSK_ROWROT(DERIV_, 1); break;                                                                                \
-    case 2: BSK_ROWROT(DERIV_, 2); break;                                                                                \
-    case 3: BSK_ROWROT(DERIV_, 3); break;                                                                                \
-    default: BSK_ROWROT(DERIV_, 0); break;                                                                               \
-    }
-            // 32-bit point indices inside a launch: chunks of at most RR_MAX_CHUNK points
-            const long long cmax = rr_chunk_points();
-            for (long long n0 = 0; n0 < n; n0 += cmax) {
-                const long long m = std::min<long long>(n - n0, cmax);
-                const int g = (int)std::max<long long>(1, std::min<long long>((m + TILE - 1) / TILE, (long long)s->num_cu * per_cu));
-                Params<T> cp = prm;
-                for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + n0;
-                if (deriv) { BSK_ROWROT_ND(true); } else { BSK_ROWROT_ND(false); }
-                HIPCHK(hipGetLastError());
-            }
-#undef BSK_ROWROT_ND
-#undef BSK_ROWROT
-            return BSK_OK;
         }
-    }
-    if constexpr (O <= 5) {
-        if (s->uniN) {
-            // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
-            const UniDescN<T> &un = uniN_of<T>(s);
-            const size_t lds_u = un.img_bytes;
-            const int per_cu_u = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_u));
-            const int grid_u = (int)std::max<long long>(1, std::min<long long>(ntiles, (long long)s->num_cu * per_cu_u));
-            s->last_kernel = "eval_stream_uni";
-            if (deriv) {
-                HIPCHK(allow_lds(eval_stream_uni<T, NIND, O, true>, lds_u));
-                hipLaunchKernelGGL((eval_stream_uni<T, NIND, O, true>), dim3(grid_u), dim3(STREAM_BLOCK), lds_u, st, d, un, s->uni_img.p,
-                                   prm, n, out, ostride, w, s->bad);
-            } else {
-                HIPCHK(allow_lds(eval_stream_uni<T, NIND, O, false>, lds_u));
-                hipLaunchKernelGGL((eval_stream_uni<T, NIND, O, false>), dim3(grid_u), dim3(STREAM_BLOCK), lds_u, st, d, un, s->uni_img.p,
-                                   prm, n, out, ostride, w, s->bad);
-            }
-            HIPCHK(hipGetLastError());
-            return BSK_OK;
-        }
-    }
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds));
-    const int grid = (int)std::max<long long>(1, std::min<long long>(ntiles, (long long)s->num_cu * per_cu));
-    if (deriv) {
-        HIPCHK(allow_lds(eval_stream<T, NIND, O, true>, lds));
-        s->last_kernel = "eval_stream";
-        hipLaunchKernelGGL((eval_stream<T, NIND, O, true>), dim3(grid), dim3(STREAM_BLOCK), lds, st, d, td, tab, s->lut, coef, prm,
-                           n, out, ostride, w, s->bad);
-    } else {
-        HIPCHK(allow_lds(eval_stream<T, NIND, O, false>, lds));
-        s->last_kernel = "eval_stream";
-        hipLaunchKernelGGL((eval_stream<T, NIND, O, false>), dim3(grid), dim3(STREAM_BLOCK), lds, st, d, td, tab, s->lut, coef, prm,
-                           n, out, ostride, w, s->bad);
-    }
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
-}
-
-// Fast-path coverage: nInd 1..3, one common order 1..6.
-static bool has_fixed_path(bsk_spline s)
-{
-    return s->same_order && s->nInd >= 1 && s->nInd <= 3 && s->order[0] >= 1 && s->order[0] <= 6;
-}
-
-static size_t tile_lds_bytes_any(bsk_spline s)
-{
-    return s->dtype == BSK_F32 ? tile_lds_bytes<float>(s, false) : tile_lds_bytes<double>(s, false);
+        return launch(s, "eval_stream", eval_stream<T, NIND, O, DERIV>, dim3(persistent_grid(s, ntiles, lds_per_cu(s, lds))),
+                      dim3(STREAM_BLOCK), lds, st, d, td, tab, s->lut, coef, prm, n, out, ostride, w, s->bad);
+    });
 }
 
 // The LDS-staging kernels (eval_fixed / jac_fixed / eval_mixed) keep at least the axis tables in LDS.
@@ -992,31 +842,19 @@ static bool axis_tables_fit_lds(bsk_spline s)
 template <typename T, int NIND, int O>
 static bsk_status launch_jac_stream(bsk_spline s, size_t lds, const Params<T> &prm, long long n, T *out, hipStream_t st)
 {
-    const Desc<T> &d = desc_of<T>(s);
-    const TileDesc<T> &td = tile_of<T>(s);
     const long long ntiles = (n + STREAM_BLOCK - 1) / STREAM_BLOCK;
     if constexpr (O <= 5) {
         if (s->uniN) {
             const UniDescN<T> &un = uniN_of<T>(s);
             const size_t lds_u = un.img_bytes;
-            const int per_cu_u = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_u));
-            const int grid_u = (int)std::max<long long>(1, std::min<long long>(ntiles, (long long)s->num_cu * per_cu_u));
-            HIPCHK(allow_lds(jac_stream_uni<T, NIND, O>, lds_u));
-            s->last_kernel = "jac_stream_uni";
-            hipLaunchKernelGGL((jac_stream_uni<T, NIND, O>), dim3(grid_u), dim3(STREAM_BLOCK), lds_u, st, d, un, s->uni_img.p, prm, n,
-                               out, s->bad);
-            HIPCHK(hipGetLastError());
-            return BSK_OK;
+            return launch(s, "jac_stream_uni", jac_stream_uni<T, NIND, O>,
+                          dim3(persistent_grid(s, ntiles, lds_per_cu(s, lds_u))), dim3(STREAM_BLOCK), lds_u, st, desc_of<T>(s),
+                          un, s->uni_img.p, prm, n, out, s->bad);
         }
     }
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds));
-    const int grid = (int)std::max<long long>(1, std::min<long long>(ntiles, (long long)s->num_cu * per_cu));
-    HIPCHK(allow_lds(jac_stream<T, NIND, O>, lds));
-    s->last_kernel = "jac_stream";
-    hipLaunchKernelGGL((jac_stream<T, NIND, O>), dim3(grid), dim3(STREAM_BLOCK), lds, st, d, td, static_cast<const T *>(s->tab),
-                       s->lut, static_cast<const T *>(s->coef), prm, n, out, s->bad);
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    return launch(s, "jac_stream", jac_stream<T, NIND, O>, dim3(persistent_grid(s, ntiles, lds_per_cu(s, lds))),
+                  dim3(STREAM_BLOCK), lds, st, desc_of<T>(s), tile_of<T>(s), static_cast<const T *>(s->tab), s->lut,
+                  static_cast<const T *>(s->coef), prm, n, out, s->bad);
 }
 
 // The asm-LDS kernels (tile / stream) cover orders 1..5: at order 6 their register windows
@@ -1040,7 +878,7 @@ static bsk_status dispatch_eval(bsk_spline s, const Params<T> &prm, long long n,
     if (n <= 0) return BSK_OK;
     if (s->nInd == 1 && s->order[0] >= 6 && s->order[0] <= 8 && s->variant != 1) {
         // curves of order 6..8: one window row per dependent variable still fits the registers
-        const size_t lds = tile_lds_bytes<T>(s, false);
+        const size_t lds = tile_lds_bytes<T>(s);
         if (lds != 0) switch (s->order[0]) {
             case 6: return launch_eval_lds<T, 1, 6>(s, lds, prm, n, out, ostride, w, st);
             case 7: return launch_eval_lds<T, 1, 7>(s, lds, prm, n, out, ostride, w, st);
@@ -1049,7 +887,7 @@ static bsk_status dispatch_eval(bsk_spline s, const Params<T> &prm, long long n,
     }
     if (has_fixed_path(s) && s->variant != 1 && s->order[0] <= 5) {
         // table image fits in LDS: eval_rowrot (surfaces of order 2 / 4) or eval_stream
-        const size_t lds = tile_lds_bytes<T>(s, false);
+        const size_t lds = tile_lds_bytes<T>(s);
         if (lds != 0) {
 #define CALL_LDS(NIND, O) launch_eval_lds<T, NIND, O>(s, lds, prm, n, out, ostride, w, st)
             if (s->nInd == 1) { BSK_ORDER_SWITCH5(1, CALL_LDS) }
@@ -1107,7 +945,7 @@ static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, 
     if (n <= 0) return BSK_OK;
     if (rowrot_applies<T>(s)) return launch_jac_rowrot<T, false>(s, prm, n, out, 0, 0, st);
     if (s->nInd == 1 && s->order[0] >= 6 && s->order[0] <= 8 && s->variant != 1) {
-        const size_t lds = tile_lds_bytes<T>(s, false);
+        const size_t lds = tile_lds_bytes<T>(s);
         if (lds != 0) switch (s->order[0]) {
             case 6: return launch_jac_stream<T, 1, 6>(s, lds, prm, n, out, st);
             case 7: return launch_jac_stream<T, 1, 7>(s, lds, prm, n, out, st);
@@ -1115,7 +953,7 @@ static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, 
         }
     }
     if (has_fixed_path(s) && s->variant != 1 && s->order[0] <= 5) {
-        const size_t lds = tile_lds_bytes<T>(s, false);
+        const size_t lds = tile_lds_bytes<T>(s);
         if (lds != 0) {
 #define CALL_JACS(NIND, O) launch_jac_stream<T, NIND, O>(s, lds, prm, n, out, st)
             if (s->nInd == 1) { BSK_ORDER_SWITCH5(1, CALL_JACS) }
@@ -1151,20 +989,15 @@ static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, 
         for (int iv = 0; iv < s->nInd; ++iv) omax = std::max(omax, s->order[iv]);
         const Plan p = make_plan<T>(s, n);
         if (p.lds_coefs && omax >= 2 && omax <= (s->nInd == 2 ? 8 : 6)) {
-            const Desc<T> &d = desc_of<T>(s);
-            const T *tab = static_cast<const T *>(s->tab);
-            const T *coef = static_cast<const T *>(s->coef);
-#define JMIX(NIND, OM)                                                                                              \
-    case OM:                                                                                                        \
-        s->last_kernel = "jac_mixed";                                        \
-        HIPCHK(allow_lds(jac_mixed<T, NIND, OM>, p.lds_bytes));                                                     \
-        hipLaunchKernelGGL((jac_mixed<T, NIND, OM>), dim3(p.grid), dim3(p.block), p.lds_bytes, st, d, tab, coef, prm, n, \
-                           out, s->bad);                                                                            \
-        HIPCHK(hipGetLastError());                                                                                  \
-        return BSK_OK;
-            if (s->nInd == 2) switch (omax) { JMIX(2, 2) JMIX(2, 3) JMIX(2, 4) JMIX(2, 5) JMIX(2, 6) JMIX(2, 7) JMIX(2, 8) default: break; }
-            else switch (omax) { JMIX(3, 2) JMIX(3, 3) JMIX(3, 4) JMIX(3, 5) JMIX(3, 6) default: break; }
-#undef JMIX
+            auto go = [&](auto ni, auto om) {
+                return launch(s, "jac_mixed", jac_mixed<T, decltype(ni)::value, decltype(om)::value>, dim3(p.grid),
+                              dim3(p.block), p.lds_bytes, st, desc_of<T>(s),
+                              static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, s->bad);
+            };
+            const std::integral_constant<int, 2> two;
+            const std::integral_constant<int, 3> three;
+            if (s->nInd == 2) return with_int<2, 3, 4, 5, 6, 7, 8>(omax, [&](auto om) { return go(two, om); });
+            return with_int<2, 3, 4, 5, 6>(omax, [&](auto om) { return go(three, om); });
         }
     }
     // large batches on L2-resident tables of three variables: the fused jacobian of the cell-order pipeline
@@ -1188,7 +1021,16 @@ static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, 
 // ------------------------------------------------------------------------------------
 // out-of-domain record
 // ------------------------------------------------------------------------------------
-static bsk_status read_bad(bsk_spline s, hipStream_t st, int64_t *first_bad)
+// The record `v` of a batch that began at point `start` of the call: NO_BAD, or the batch's first offender.
+static bsk_status domain_status(unsigned long long v, long long start, int64_t *first_bad)
+{
+    if (first_bad) *first_bad = v == NO_BAD ? -1 : start + (int64_t)v;
+    if (v == NO_BAD) return BSK_OK;
+    return fail(BSK_ERR_DOMAIN, "parameter outside the spline's domain at flat index " + std::to_string(start + (long long)v));
+}
+
+// Fetches and clears the record; synchronises `st`.
+static bsk_status read_bad(bsk_spline s, hipStream_t st, int64_t *first_bad, long long start = 0)
 {
     unsigned long long v = NO_BAD;
     HIPCHK(hipMemcpyAsync(&v, s->bad, sizeof(v), hipMemcpyDeviceToHost, st));
@@ -1196,11 +1038,8 @@ static bsk_status read_bad(bsk_spline s, hipStream_t st, int64_t *first_bad)
     if (v != NO_BAD) {
         HIPCHK(hipMemsetAsync(s->bad, 0xff, sizeof(v), st));
         HIPCHK(hipStreamSynchronize(st));
-        if (first_bad) *first_bad = (int64_t)v;
-        return fail(BSK_ERR_DOMAIN, "parameter outside the spline's domain at flat index " + std::to_string(v));
     }
-    if (first_bad) *first_bad = -1;
-    return BSK_OK;
+    return domain_status(v, start, first_bad);
 }
 
 // Grow a per-handle device workspace.  Growth frees and allocates (a device-wide synchronisation) and cannot be
@@ -1259,10 +1098,12 @@ static bsk_status reserve_pin(bsk_spline s, size_t bytes)
     return BSK_OK;
 }
 
+// The three BSK_HOST paths below share one callback: chunk(prm, m, dout, stream) enqueues the kernels for m points
+// whose parameter rows are prm, writing rows_out rows of stride m at dout.
 // layout of the pinned buffer: [first_bad u64][pad to 64][inputs: rows_in x n][outputs: rows_out x n]
-template <typename T, typename Launch>
+template <typename T, typename Chunk>
 static bsk_status run_small(bsk_spline s, const void *const *uvw, long long n, int rows_out, void *out, hipStream_t st,
-                            int64_t *first_bad, Launch launch)
+                            int64_t *first_bad, Chunk chunk)
 {
     const size_t in_b = sizeof(T) * (size_t)n * s->nInd, out_b = sizeof(T) * (size_t)n * rows_out;
     bsk_status r = reserve_pin(s, 64 + ((in_b + 63) & ~(size_t)63) + out_b + 64);
@@ -1281,19 +1122,14 @@ static bsk_status run_small(bsk_spline s, const void *const *uvw, long long n, i
         memcpy(hin + (size_t)iv * n, uvw[iv], sizeof(T) * (size_t)n);
         prm.p[iv] = din + (size_t)iv * n;
     }
-    r = launch(prm, dout);
+    r = chunk(prm, n, dout, st);
     if (r != BSK_OK) return r;
-    hipLaunchKernelGGL(publish_bad, dim3(1), dim3(1), 0, st, s->bad, reinterpret_cast<unsigned long long *>(dbase));
-    HIPCHK(hipGetLastError());
+    r = launch(s, nullptr, publish_bad, dim3(1), dim3(1), 0, st, s->bad, reinterpret_cast<unsigned long long *>(dbase));
+    if (r != BSK_OK) return r;
     HIPCHK(hipStreamSynchronize(st));
-    const unsigned long long v = *hslot;
-    if (v != NO_BAD) {
-        if (first_bad) *first_bad = (int64_t)v;
-        return fail(BSK_ERR_DOMAIN, "parameter outside the spline's domain at flat index " + std::to_string(v));
-    }
-    memcpy(out, hout, out_b);
-    if (first_bad) *first_bad = -1;
-    return BSK_OK;
+    r = domain_status(*hslot, 0, first_bad);
+    if (r == BSK_OK) memcpy(out, hout, out_b);
+    return r;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1448,11 +1284,10 @@ static bsk_status pipe_prepare(bsk_spline s, size_t in_b, size_t out_b)
     return BSK_OK;
 }
 
-// rows_out result rows of n values each at out (row stride n); launch(prm, m, dout, stream) enqueues the
-// kernels of one chunk of m points writing rows of stride m
-template <typename T, typename Launch>
+// rows_out result rows of n values each at out (row stride n), in chunks of PIPE_CHUNK points
+template <typename T, typename Chunk>
 static bsk_status run_piped(bsk_spline s, CopyPool *pool, const void *const *uvw, long long n, int rows_out, void *out,
-                            int64_t *first_bad, Launch launch)
+                            int64_t *first_bad, Chunk chunk)
 {
     const long long C = PIPE_CHUNK;
     const long long K = (n + C - 1) / C;
@@ -1467,11 +1302,7 @@ static bsk_status run_piped(bsk_spline s, CopyPool *pool, const void *const *uvw
         const int slot = (int)(k % HostPipe::SLOTS);
         const long long start = k * C, m = std::min(C, n - start);
         HIPCHK(hipEventSynchronize(p.e_out[slot]));
-        const unsigned long long v = p.pin_bad[slot];
-        if (v != NO_BAD) {
-            if (first_bad) *first_bad = start + (int64_t)v;
-            return fail(BSK_ERR_DOMAIN, "parameter outside the spline's domain at flat index " + std::to_string(start + (long long)v));
-        }
+        if (const bsk_status bad = domain_status(p.pin_bad[slot], start, first_bad); bad != BSK_OK) return bad;
         const T *src = static_cast<const T *>(p.pin_out[slot]);
         for (int row = 0; row < rows_out; ++row)
             pool->copy(static_cast<T *>(out) + (size_t)row * n + start, src + (size_t)row * m, sizeof(T) * (size_t)m);
@@ -1495,9 +1326,9 @@ static bsk_status run_piped(bsk_spline s, CopyPool *pool, const void *const *uvw
         HIPCHK(hipMemcpyAsync(din, hin, sizeof(T) * (size_t)m * s->nInd, hipMemcpyHostToDevice, p.s_in));
         HIPCHK(hipEventRecord(p.e_in[slot], p.s_in));
         HIPCHK(hipStreamWaitEvent(p.s_k, p.e_in[slot], 0));
-        r = launch(prm, m, dout, p.s_k);
+        r = chunk(prm, m, dout, p.s_k);
+        if (r == BSK_OK) r = launch(s, nullptr, publish_bad, dim3(1), dim3(1), 0, p.s_k, s->bad, dbad + slot);
         if (r != BSK_OK) { result = r; break; }
-        hipLaunchKernelGGL(publish_bad, dim3(1), dim3(1), 0, p.s_k, s->bad, dbad + slot);
         HIPCHK(hipEventRecord(p.e_k[slot], p.s_k));
         HIPCHK(hipStreamWaitEvent(p.s_out, p.e_k[slot], 0));
         HIPCHK(hipMemcpyAsync(p.pin_out[slot], dout, sizeof(T) * (size_t)m * rows_out, hipMemcpyDeviceToHost, p.s_out));
@@ -1511,10 +1342,8 @@ static bsk_status run_piped(bsk_spline s, CopyPool *pool, const void *const *uvw
         (void)hipStreamSynchronize(p.s_out);
         (void)hipMemsetAsync(s->bad, 0xff, sizeof(unsigned long long), p.s_k);
         (void)hipStreamSynchronize(p.s_k);
-        return result;
     }
-    if (first_bad) *first_bad = -1;
-    return BSK_OK;
+    return result;
 }
 
 // BSK_HOST batches are processed in chunks so the staging buffers stay bounded.
@@ -1529,43 +1358,13 @@ static long long host_chunk_points()
     return v;
 }
 
-template <typename T>
-static bsk_status run_points(bsk_spline s, bool jac, const int *wrt, const void *const *uvw, long long n, bsk_mem mem,
-                             void *out, hipStream_t st, int64_t *first_bad)
+// Staged path: chunks of `chunk` points through in_ws / out_ws on the caller's stream, one synchronisation per chunk.
+template <typename T, typename Chunk>
+static bsk_status run_staged(bsk_spline s, const void *const *uvw, long long n, long long chunk, int rows_out, void *out,
+                             hipStream_t st, int64_t *first_bad, Chunk chunk_fn)
 {
-    Wrt w;
-    for (int iv = 0; iv < MAXI; ++iv) w.w[iv] = (wrt && iv < s->nInd) ? wrt[iv] : 0;
-    for (int iv = 0; iv < s->nInd; ++iv)
-        if (w.w[iv] < 0) return fail(BSK_ERR_INVALID, "negative derivative order");
-    const int outs = jac ? s->nDep * s->nInd : s->nDep;   // output rows per point
-    if (first_bad) *first_bad = -1;
-    if (n == 0) return BSK_OK;
-
-    if (mem == BSK_DEVICE) {
-        Params<T> prm;
-        for (int iv = 0; iv < MAXI; ++iv) prm.p[iv] = iv < s->nInd ? static_cast<const T *>(uvw[iv]) : nullptr;
-        return jac ? dispatch_jac<T>(s, prm, n, static_cast<T *>(out), st)
-                   : dispatch_eval<T>(s, prm, n, static_cast<T *>(out), n, w, st);
-    }
-
-    if (n <= small_call_points())
-        return run_small<T>(s, uvw, n, outs, out, st, first_bad, [&](const Params<T> &prm, T *dout) {
-            return jac ? dispatch_jac<T>(s, prm, n, dout, st) : dispatch_eval<T>(s, prm, n, dout, n, w, st);
-        });
-
-    if (n >= PIPE_MIN_POINTS) {
-        if (CopyPool *pool = copy_pool()) {
-            HIPCHK(hipStreamSynchronize(st));                 // the call is blocking: order it after the caller's stream
-            return run_piped<T>(s, pool, uvw, n, outs, out, first_bad, [&](const Params<T> &prm, long long m, T *dout, hipStream_t ks) {
-                return jac ? dispatch_jac<T>(s, prm, m, dout, ks) : dispatch_eval<T>(s, prm, m, dout, m, w, ks);
-            });
-        }
-    }
-
-    // host buffers: stage chunk by chunk
-    const long long chunk = std::min(n, host_chunk_points());
     HIPCHK(s->in_ws.reserve(sizeof(T) * (size_t)chunk * s->nInd));
-    HIPCHK(s->out_ws.reserve(sizeof(T) * (size_t)chunk * outs));
+    HIPCHK(s->out_ws.reserve(sizeof(T) * (size_t)chunk * rows_out));
     T *din = static_cast<T *>(s->in_ws.p);
     T *dout = static_cast<T *>(s->out_ws.p);
     for (long long start = 0; start < n; start += chunk) {
@@ -1577,20 +1376,65 @@ static bsk_status run_points(bsk_spline s, bool jac, const int *wrt, const void 
                                   hipMemcpyHostToDevice, st));
             prm.p[iv] = din + (size_t)iv * m;
         }
-        bsk_status r = jac ? dispatch_jac<T>(s, prm, m, dout, st) : dispatch_eval<T>(s, prm, m, dout, m, w, st);
+        bsk_status r = chunk_fn(prm, m, dout, st);
         if (r != BSK_OK) return r;
-        for (int row = 0; row < outs; ++row)
+        for (int row = 0; row < rows_out; ++row)
             HIPCHK(hipMemcpyAsync(static_cast<T *>(out) + (size_t)row * n + start, dout + (size_t)row * m,
                                   sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, st));
-        int64_t bad = -1;
-        r = read_bad(s, st, &bad);     // also synchronises the chunk
-        if (r == BSK_ERR_DOMAIN) {
-            if (first_bad) *first_bad = start + bad;
-            return r;
-        }
+        r = read_bad(s, st, first_bad, start);     // also synchronises the chunk
         if (r != BSK_OK) return r;
     }
     return BSK_OK;
+}
+
+// A BSK_HOST batch on the path for its size: small (one pinned buffer), pipelined, or staged.  aux_per_point: bytes of
+// aux_ws the callback needs per point of the largest chunk the chosen path hands it (reserved before the first launch).
+template <typename T, typename Chunk>
+static bsk_status run_host(bsk_spline s, const void *const *uvw, long long n, int rows_out, void *out, hipStream_t st,
+                           int64_t *first_bad, size_t aux_per_point, Chunk chunk_fn)
+{
+    bsk_status r;
+    if (n <= small_call_points()) {
+        if ((r = ws_reserve(s->aux_ws, aux_per_point * (size_t)n, st)) != BSK_OK) return r;
+        return run_small<T>(s, uvw, n, rows_out, out, st, first_bad, chunk_fn);
+    }
+    if (n >= PIPE_MIN_POINTS) {
+        if (CopyPool *pool = copy_pool()) {
+            if ((r = ws_reserve(s->aux_ws, aux_per_point * (size_t)PIPE_CHUNK, st)) != BSK_OK) return r;
+            HIPCHK(hipStreamSynchronize(st));                 // the call is blocking: order it after the caller's stream
+            return run_piped<T>(s, pool, uvw, n, rows_out, out, first_bad, chunk_fn);
+        }
+    }
+    const long long chunk = std::min(n, host_chunk_points());
+    if ((r = ws_reserve(s->aux_ws, aux_per_point * (size_t)chunk, st)) != BSK_OK) return r;
+    return run_staged<T>(s, uvw, n, chunk, rows_out, out, st, first_bad, chunk_fn);
+}
+
+// Parameter rows that already are in device memory
+template <typename T>
+static Params<T> device_params(bsk_spline s, const void *const *uvw, long long start = 0)
+{
+    Params<T> prm;
+    for (int iv = 0; iv < MAXI; ++iv) prm.p[iv] = iv < s->nInd ? static_cast<const T *>(uvw[iv]) + start : nullptr;
+    return prm;
+}
+
+template <typename T>
+static bsk_status run_points(bsk_spline s, bool jac, const int *wrt, const void *const *uvw, long long n, bsk_mem mem,
+                             void *out, hipStream_t st, int64_t *first_bad)
+{
+    Wrt w;
+    for (int iv = 0; iv < MAXI; ++iv) w.w[iv] = (wrt && iv < s->nInd) ? wrt[iv] : 0;
+    for (int iv = 0; iv < s->nInd; ++iv)
+        if (w.w[iv] < 0) return fail(BSK_ERR_INVALID, "negative derivative order");
+    const int outs = jac ? s->nDep * s->nInd : s->nDep;   // output rows per point
+    if (first_bad) *first_bad = -1;
+    if (n == 0) return BSK_OK;
+    auto points_chunk = [&](const Params<T> &prm, long long m, T *dout, hipStream_t ks) {
+        return jac ? dispatch_jac<T>(s, prm, m, dout, ks) : dispatch_eval<T>(s, prm, m, dout, m, w, ks);
+    };
+    if (mem == BSK_DEVICE) return points_chunk(device_params<T>(s, uvw), n, static_cast<T *>(out), st);
+    return run_host<T>(s, uvw, n, outs, out, st, first_bad, 0, points_chunk);
 }
 
 static bsk_status check_call(bsk_spline s, const void *const *uvw, int64_t n, void *out)
@@ -1637,82 +1481,21 @@ static bsk_status run_normal(bsk_spline s, const void *const *uvw, long long n, 
     const int big = std::max(s->nInd, s->nDep);
     if (first_bad) *first_bad = -1;
     if (n == 0) return BSK_OK;
-    const long long chunk = mem == BSK_HOST ? std::min(n, host_chunk_points()) : n;
-    // jacobian workspace (device) for one chunk, unless the normal is fused into the jacobian kernel
+    // surface in 3-D on the LDS image: the normal is fused into the jacobian kernel, tangents never leave the registers
     const bool fused = s->nDep == 3 && rowrot_applies<T>(s);
-    // one chunk of m points on stream ks (jacobian workspace in aux_ws when the normal is not fused)
+    const size_t jac_b = fused ? 0 : sizeof(T) * (size_t)s->nDep * s->nInd;     // jacobian workspace (aux_ws) per point
+    // one chunk of m points on stream ks
     auto normal_chunk = [&](const Params<T> &prm, long long m, T *dout, hipStream_t ks) -> bsk_status {
         if (fused) return launch_jac_rowrot<T, true>(s, prm, m, dout, normalize, negate, ks);
         T *dj = static_cast<T *>(s->aux_ws.p);
         const bsk_status r = dispatch_jac<T>(s, prm, m, dj, ks);
         if (r != BSK_OK) return r;
-        const int grid = (int)std::max<long long>(1, std::min<long long>((m + 255) / 256, (long long)s->num_cu * 8));
-        hipLaunchKernelGGL((normal_epilogue<T>), dim3(grid), dim3(256), 0, ks, dj, s->nInd, s->nDep, m, normalize, negate, dout);
-        HIPCHK(hipGetLastError());
-        return BSK_OK;
+        return launch(s, nullptr, normal_epilogue<T>, dim3(persistent_grid(s, (m + 255) / 256, 8)), dim3(256), 0, ks, dj,
+                      s->nInd, s->nDep, m, normalize, negate, dout);
     };
-    if (mem == BSK_HOST && n <= small_call_points()) {
-        if (!fused) if (bsk_status r_ = ws_reserve(s->aux_ws, sizeof(T) * (size_t)n * s->nDep * s->nInd, st); r_ != BSK_OK) return r_;
-        return run_small<T>(s, uvw, n, big, out, st, first_bad,
-                            [&](const Params<T> &prm, T *dout) { return normal_chunk(prm, n, dout, st); });
-    }
-    if (mem == BSK_HOST && n >= PIPE_MIN_POINTS) {
-        if (CopyPool *pool = copy_pool()) {
-            if (!fused) if (bsk_status r_ = ws_reserve(s->aux_ws, sizeof(T) * (size_t)PIPE_CHUNK * s->nDep * s->nInd, st); r_ != BSK_OK) return r_;
-            HIPCHK(hipStreamSynchronize(st));
-            return run_piped<T>(s, pool, uvw, n, big, out, first_bad, normal_chunk);
-        }
-    }
-    if (!fused) if (bsk_status r_ = ws_reserve(s->aux_ws, sizeof(T) * (size_t)chunk * s->nDep * s->nInd, st); r_ != BSK_OK) return r_;
-    T *djac = static_cast<T *>(s->aux_ws.p);
-    T *din = nullptr, *dout = static_cast<T *>(out);
-    if (mem == BSK_HOST) {
-        HIPCHK(s->in_ws.reserve(sizeof(T) * (size_t)chunk * s->nInd));
-        HIPCHK(s->out_ws.reserve(sizeof(T) * (size_t)chunk * big));
-        din = static_cast<T *>(s->in_ws.p);
-        dout = static_cast<T *>(s->out_ws.p);
-    }
-    for (long long start = 0; start < n; start += chunk) {
-        const long long m = std::min(chunk, n - start);
-        Params<T> prm;
-        for (int iv = 0; iv < MAXI; ++iv) prm.p[iv] = nullptr;
-        for (int iv = 0; iv < s->nInd; ++iv) {
-            if (mem == BSK_HOST) {
-                HIPCHK(hipMemcpyAsync(din + (size_t)iv * m, static_cast<const T *>(uvw[iv]) + start, sizeof(T) * (size_t)m,
-                                      hipMemcpyHostToDevice, st));
-                prm.p[iv] = din + (size_t)iv * m;
-            } else {
-                prm.p[iv] = static_cast<const T *>(uvw[iv]);
-            }
-        }
-        bsk_status r;
-        if (fused) {
-            // surface in 3-D on the LDS image: tangents never leave the registers
-            r = launch_jac_rowrot<T, true>(s, prm, m, dout, normalize, negate, st);
-            if (r != BSK_OK) return r;
-        } else {
-            r = dispatch_jac<T>(s, prm, m, djac, st);
-            if (r != BSK_OK) return r;
-            const int block = 256;
-            const int grid = (int)std::max<long long>(1, std::min<long long>((m + block - 1) / block, (long long)s->num_cu * 8));
-            hipLaunchKernelGGL((normal_epilogue<T>), dim3(grid), dim3(block), 0, st, djac, s->nInd, s->nDep, m, normalize,
-                               negate, dout);
-            HIPCHK(hipGetLastError());
-        }
-        if (mem == BSK_HOST) {
-            for (int row = 0; row < big; ++row)
-                HIPCHK(hipMemcpyAsync(static_cast<T *>(out) + (size_t)row * n + start, dout + (size_t)row * m,
-                                      sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, st));
-            int64_t bad = -1;
-            r = read_bad(s, st, &bad);
-            if (r == BSK_ERR_DOMAIN) {
-                if (first_bad) *first_bad = start + bad;
-                return r;
-            }
-            if (r != BSK_OK) return r;
-        }
-    }
-    return BSK_OK;
+    if (mem == BSK_HOST) return run_host<T>(s, uvw, n, big, out, st, first_bad, jac_b, normal_chunk);
+    if (bsk_status r = ws_reserve(s->aux_ws, jac_b * (size_t)n, st); r != BSK_OK) return r;
+    return normal_chunk(device_params<T>(s, uvw), n, static_cast<T *>(out), st);
 }
 
 extern "C" bsk_status bsk_normal(bsk_spline s, const void *const *uvw, int64_t n, bsk_mem mem, int normalize, int negate,
@@ -1745,93 +1528,57 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
     // derivative workspace: persistent on the handle (no allocation, free or synchronisation per call)
     if (bsk_status r_ = ws_reserve(s->curv_ws, std::max<size_t>(16, sizeof(T) * (size_t)chunk * s->nDep * nbuf), st); r_ != BSK_OK) return r_;
     T *w = static_cast<T *>(s->curv_ws.p);
-    T *din = nullptr, *dout = static_cast<T *>(out);
-    if (mem == BSK_HOST) {
-        HIPCHK(s->in_ws.reserve(sizeof(T) * (size_t)chunk * s->nInd));
-        HIPCHK(s->out_ws.reserve(sizeof(T) * (size_t)chunk));
-        din = static_cast<T *>(s->in_ws.p);
-    }
     const size_t one = (size_t)chunk * s->nDep;
-    for (long long start = 0; start < n; start += chunk) {
-        const long long m = std::min(chunk, n - start);
-        Params<T> prm;
-        for (int iv = 0; iv < MAXI; ++iv) prm.p[iv] = nullptr;
-        for (int iv = 0; iv < s->nInd; ++iv) {
-            if (mem == BSK_HOST) {
-                HIPCHK(hipMemcpyAsync(din + (size_t)iv * m, static_cast<const T *>(uvw[iv]) + start, sizeof(T) * (size_t)m,
-                                      hipMemcpyHostToDevice, st));
-                prm.p[iv] = din + (size_t)iv * m;
-            } else {
-                prm.p[iv] = static_cast<const T *>(uvw[iv]) + start;
-            }
-        }
-        T *o = mem == BSK_HOST ? static_cast<T *>(s->out_ws.p) : dout + start;
+    // one chunk of m points on stream ks: curvatures at o
+    auto curv_chunk = [&](const Params<T> &prm, long long m, T *o, hipStream_t ks) -> bsk_status {
         auto deriv = [&](int w0, int w1, T *dst) -> bsk_status {
             Wrt wr;
             for (int iv = 0; iv < MAXI; ++iv) wr.w[iv] = 0;
             wr.w[0] = w0;
             wr.w[1] = w1;
-            return dispatch_eval<T>(s, prm, m, dst, m, wr, st);
+            return dispatch_eval<T>(s, prm, m, dst, m, wr, ks);
         };
-        const int block = 256;
-        const int grid = (int)std::max<long long>(1, std::min<long long>((m + block - 1) / block, (long long)s->num_cu * 8));
+        const dim3 block(256), grid(persistent_grid(s, (m + 255) / 256, 8));
         bsk_status r;
         if (!surface) {
             if ((r = deriv(1, 0, w)) != BSK_OK) return r;
             if ((r = deriv(2, 0, w + one)) != BSK_OK) return r;
-            hipLaunchKernelGGL((curvature_curve<T>), dim3(grid), dim3(block), 0, st, w, w + one, s->nDep, m, o);
-        } else if (fused) {
-            const Desc<T> &d = desc_of<T>(s);
-            const TileDesc<T> &tdr = tile_of<T>(s);
+            return launch(s, nullptr, curvature_curve<T>, grid, block, 0, ks, w, w + one, s->nDep, m, o);
+        }
+        if (fused) {
             const size_t lds_rr = rowrot_lds_bytes<T>(s);
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_rr));
-            const long long cmax = rr_chunk_points();
-            for (long long c0 = 0; c0 < m; c0 += cmax) {
-                const long long mm = std::min<long long>(m - c0, cmax);
-                const int g = (int)std::max<long long>(1, std::min<long long>((mm + TILE - 1) / TILE, (long long)s->num_cu * per_cu));
-                Params<T> cp = prm;
-                for (int iv = 0; iv < s->nInd; ++iv) cp.p[iv] = prm.p[iv] + c0;
-                if (s->order[0] == 4) {
-                    HIPCHK(allow_lds(curv_rowrot<T, 4>, lds_rr));
-                    s->last_kernel = "curv_rowrot";
-                    hipLaunchKernelGGL((curv_rowrot<T, 4>), dim3(g), dim3(TILE), lds_rr, st, d, tdr, static_cast<const T *>(s->tab),
-                                       s->lut, static_cast<const T *>(s->coef), cp, (unsigned)mm, c0, o + c0, s->bad);
-                } else {
-                    HIPCHK(allow_lds(curv_rowrot<T, 2>, lds_rr));
-                    s->last_kernel = "curv_rowrot";
-                    hipLaunchKernelGGL((curv_rowrot<T, 2>), dim3(g), dim3(TILE), lds_rr, st, d, tdr, static_cast<const T *>(s->tab),
-                                       s->lut, static_cast<const T *>(s->coef), cp, (unsigned)mm, c0, o + c0, s->bad);
-                }
-            }
+            return with_int<4, 2>(s->order[0], [&](auto ord) {
+                return for_rr_chunks<T>(s, prm, m, [&](const Params<T> &cp, long long mm, long long c0) {
+                    return launch(s, "curv_rowrot", curv_rowrot<T, decltype(ord)::value>, rr_grid(s, mm, lds_rr), dim3(TILE),
+                                  lds_rr, ks, desc_of<T>(s), tile_of<T>(s), static_cast<const T *>(s->tab), s->lut,
+                                  static_cast<const T *>(s->coef), cp, (unsigned)mm, c0, o + c0, s->bad);
+                });
+            });
+        }
+        if ((r = deriv(1, 0, w)) != BSK_OK) return r;
+        if ((r = deriv(0, 1, w + one)) != BSK_OK) return r;
+        if ((r = deriv(2, 0, w + 2 * one)) != BSK_OK) return r;
+        if ((r = deriv(1, 1, w + 3 * one)) != BSK_OK) return r;
+        if ((r = deriv(0, 2, w + 4 * one)) != BSK_OK) return r;
+        // unit normal (fused into the jacobian kernel when the image fits LDS)
+        if (rowrot_applies<T>(s)) {
+            if ((r = launch_jac_rowrot<T, true>(s, prm, m, w + 5 * one, 1, 0, ks)) != BSK_OK) return r;
         } else {
-            if ((r = deriv(1, 0, w)) != BSK_OK) return r;
-            if ((r = deriv(0, 1, w + one)) != BSK_OK) return r;
-            if ((r = deriv(2, 0, w + 2 * one)) != BSK_OK) return r;
-            if ((r = deriv(1, 1, w + 3 * one)) != BSK_OK) return r;
-            if ((r = deriv(0, 2, w + 4 * one)) != BSK_OK) return r;
-            // unit normal (fused into the jacobian kernel when the image fits LDS)
-            if (rowrot_applies<T>(s)) {
-                if ((r = launch_jac_rowrot<T, true>(s, prm, m, w + 5 * one, 1, 0, st)) != BSK_OK) return r;
-            } else {
-                if (bsk_status r_ = ws_reserve(s->aux_ws, sizeof(T) * (size_t)m * s->nDep * s->nInd, st); r_ != BSK_OK) return r_;
-                T *djac = static_cast<T *>(s->aux_ws.p);
-                if ((r = dispatch_jac<T>(s, prm, m, djac, st)) != BSK_OK) return r;
-                hipLaunchKernelGGL((normal_epilogue<T>), dim3(grid), dim3(block), 0, st, djac, 2, 3, m, 1, 0, w + 5 * one);
-            }
-            hipLaunchKernelGGL((curvature_surface<T>), dim3(grid), dim3(block), 0, st, w, w + one, w + 2 * one, w + 3 * one,
-                               w + 4 * one, w + 5 * one, m, o);
+            if ((r = ws_reserve(s->aux_ws, sizeof(T) * (size_t)m * s->nDep * s->nInd, ks)) != BSK_OK) return r;
+            T *djac = static_cast<T *>(s->aux_ws.p);
+            if ((r = dispatch_jac<T>(s, prm, m, djac, ks)) != BSK_OK) return r;
+            if ((r = launch(s, nullptr, normal_epilogue<T>, grid, block, 0, ks, djac, 2, 3, m, 1, 0,
+                            w + 5 * one)) != BSK_OK) return r;
         }
-        HIPCHK(hipGetLastError());
-        if (mem == BSK_HOST) {
-            HIPCHK(hipMemcpyAsync(static_cast<T *>(out) + start, o, sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, st));
-            int64_t bad = -1;
-            r = read_bad(s, st, &bad);
-            if (r == BSK_ERR_DOMAIN) {
-                if (first_bad) *first_bad = start + bad;
-                return r;
-            }
-            if (r != BSK_OK) return r;
-        }
+        return launch(s, nullptr, curvature_surface<T>, grid, block, 0, ks, w, w + one, w + 2 * one, w + 3 * one, w + 4 * one,
+                      w + 5 * one, m, o);
+    };
+    // BSK_HOST: the staged path at every size (the small-call and the pipelined path have not been measured for curvature)
+    if (mem == BSK_HOST) return run_staged<T>(s, uvw, n, chunk, 1, out, st, first_bad, curv_chunk);
+    for (long long start = 0; start < n; start += chunk) {
+        const long long m = std::min(chunk, n - start);
+        const bsk_status r = curv_chunk(device_params<T>(s, uvw, start), m, static_cast<T *>(out) + start, st);
+        if (r != BSK_OK) return r;
     }
     return BSK_OK;
 }
@@ -1852,14 +1599,24 @@ extern "C" bsk_status bsk_curvature(bsk_spline s, const void *const *uvw, int64_
 // ------------------------------------------------------------------------------------
 // tensor-product grid
 // ------------------------------------------------------------------------------------
+// Per-axis tables of a tensor-product grid in aux_ws: basis rows, span indices and outside flags of every grid
+// parameter, in one set (wrt) or two (the second: first derivatives of every variable, launched when `second`).
 template <typename T>
-static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid, const int64_t *ngrid, bsk_mem mem,
-                           void *out, hipStream_t st, int64_t *first_bad)
-{
-    const Desc<T> &d = desc_of<T>(s);
-    if (first_bad) *first_bad = -1;
+struct GridTables {
     GridDims g;
-    long long total = 1, npar = 0, nrow = 0;
+    long long total = 0;          // grid points; 0: nothing to do
+    T *rows[2];
+    int *ixs[2];
+    unsigned char *outside[2];
+};
+
+// aux_ws: [params T x npar (host mode only)] [rows T x nrow] x sets [ix int x npar] x sets [outside u8 x npar, padded] x sets
+template <typename T>
+static bsk_status grid_tables(bsk_spline s, const int *wrt, const void *const *grid, const int64_t *ngrid, bsk_mem mem,
+                              int sets, bool second, hipStream_t st, GridTables<T> &t)
+{
+    GridDims &g = t.g;
+    long long total = 1, npar = 0, nrow = 0, nmax = 1;
     for (int iv = 0; iv < MAXI; ++iv) { g.n[iv] = 1; g.goff[iv] = 0; g.roff[iv] = 0; }
     for (int iv = 0; iv < s->nInd; ++iv) {
         if (ngrid[iv] < 0) return fail(BSK_ERR_INVALID, "negative grid size");
@@ -1870,22 +1627,22 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
         npar += ngrid[iv];
         nrow += ngrid[iv] * s->order[iv];
         total *= ngrid[iv];
+        nmax = std::max<long long>(nmax, ngrid[iv]);
     }
     if (total == 0) return BSK_OK;
 
-    // aux workspace: [params T x npar (host mode only)] [rows T x nrow] [ix int x npar] [outside u8 x npar]
     const size_t par_b = mem == BSK_HOST ? ((sizeof(T) * (size_t)npar + 15) & ~(size_t)15) : 0;
     const size_t row_b = (sizeof(T) * (size_t)nrow + 15) & ~(size_t)15;
     const size_t ix_b = (sizeof(int) * (size_t)npar + 15) & ~(size_t)15;
-    if (bsk_status r_ = ws_reserve(s->aux_ws, par_b + row_b + ix_b + (size_t)npar + 16, st); r_ != BSK_OK) return r_;
+    if (bsk_status r = ws_reserve(s->aux_ws, par_b + sets * (row_b + ix_b + (size_t)npar + 16), st); r != BSK_OK) return r;
     char *base = static_cast<char *>(s->aux_ws.p);
     T *dpar = reinterpret_cast<T *>(base);
-    T *rows = reinterpret_cast<T *>(base + par_b);
-    int *ixs = reinterpret_cast<int *>(base + par_b + row_b);
-    unsigned char *outside = reinterpret_cast<unsigned char *>(base + par_b + row_b + ix_b);
-
+    for (int k = 0; k < sets; ++k) {
+        t.rows[k] = reinterpret_cast<T *>(base + par_b + k * row_b);
+        t.ixs[k] = reinterpret_cast<int *>(base + par_b + sets * row_b + k * ix_b);
+        t.outside[k] = reinterpret_cast<unsigned char *>(base + par_b + sets * (row_b + ix_b)) + k * ((npar + 15) & ~15ll);
+    }
     GridAxes<T> ax;
-    long long nmax = 1;
     for (int iv = 0; iv < MAXI; ++iv) { ax.u[iv] = nullptr; ax.wrt[iv] = 0; }
     for (int iv = 0; iv < s->nInd; ++iv) {
         const T *u = static_cast<const T *>(grid[iv]);
@@ -1895,11 +1652,32 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
         }
         ax.u[iv] = u;
         ax.wrt[iv] = wrt ? wrt[iv] : 0;
-        nmax = std::max<long long>(nmax, ngrid[iv]);
     }
-    hipLaunchKernelGGL((basis_rows_grid<T>), dim3((unsigned)((nmax + 255) / 256), (unsigned)s->nInd), dim3(256), 0, st, d,
-                       static_cast<const T *>(s->tab), ax, g, ixs, rows, outside);
-    HIPCHK(hipGetLastError());
+    const dim3 grid2((unsigned)((nmax + 255) / 256), (unsigned)s->nInd);
+    for (int k = 0; k < (second ? 2 : 1); ++k) {
+        if (k == 1) for (int iv = 0; iv < s->nInd; ++iv) ax.wrt[iv] = 1;
+        const bsk_status r = launch(s, nullptr, basis_rows_grid<T>, grid2, dim3(256), 0, st, desc_of<T>(s),
+                                    static_cast<const T *>(s->tab), ax, g, t.ixs[k], t.rows[k], t.outside[k]);
+        if (r != BSK_OK) return r;
+    }
+    t.total = total;
+    return BSK_OK;
+}
+
+template <typename T>
+static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid, const int64_t *ngrid, bsk_mem mem,
+                           void *out, hipStream_t st, int64_t *first_bad)
+{
+    const Desc<T> &d = desc_of<T>(s);
+    if (first_bad) *first_bad = -1;
+    GridTables<T> t;
+    const bsk_status rt = grid_tables<T>(s, wrt, grid, ngrid, mem, 1, false, st, t);
+    if (rt != BSK_OK || t.total == 0) return rt;
+    const GridDims &g = t.g;
+    const long long total = t.total;
+    T *rows = t.rows[0];
+    int *ixs = t.ixs[0];
+    unsigned char *outside = t.outside[0];
 
     T *dout = static_cast<T *>(out);
     if (mem == BSK_HOST) {
@@ -1907,56 +1685,33 @@ static bsk_status run_grid(bsk_spline s, const int *wrt, const void *const *grid
         dout = static_cast<T *>(s->out_ws.p);
     }
     const T *coef = static_cast<const T *>(s->coef);
-    bool launched = false;
     const size_t rowc_bytes = sizeof(T) * (size_t)s->nDep * (size_t)(s->nInd == 2 ? s->ncoef[1] : 0);
     const int omax2 = s->nInd == 2 ? std::max(s->order[0], s->order[1]) : 0;
+    bsk_status r;
     if (s->nInd == 2 && omax2 <= 6 && rowc_bytes <= 48 * 1024 && g.n[1] >= 64 && s->variant != 1) {
         // row-factored surface grid
         constexpr long long VEC = 16 / (long long)sizeof(T);
         const int vec_ok = (g.n[1] % VEC == 0) && ((reinterpret_cast<uintptr_t>(dout) & 15) == 0) ? 1 : 0;
-        const int gridx = (int)std::max<long long>(1, std::min<long long>(g.n[0], (long long)s->num_cu * 8));
-#define GRID_ROWS(O)                                                                                           \
-    case O:                                                                                                    \
-        if (s->same_order)                                                                                     \
-            hipLaunchKernelGGL((grid_rows<T, O, false>), dim3(gridx), dim3(256), rowc_bytes, st, d, coef, g, ixs, rows, \
-                               outside, dout, s->bad, vec_ok);                                                 \
-        else                                                                                                   \
-            hipLaunchKernelGGL((grid_rows<T, O, true>), dim3(gridx), dim3(256), rowc_bytes, st, d, coef, g, ixs, rows,  \
-                               outside, dout, s->bad, vec_ok);                                                 \
-        launched = true;                                                                                       \
-        s->last_kernel = "grid_rows";                                                                          \
-        break;
-        switch (omax2) {
-            GRID_ROWS(1) GRID_ROWS(2) GRID_ROWS(3) GRID_ROWS(4) GRID_ROWS(5) GRID_ROWS(6)
-            default: break;
-        }
-#undef GRID_ROWS
-    }
-    if (!launched && s->nInd == 2 && s->same_order && g.n[0] <= 65535) {
+        r = with_int<1, 2, 3, 4, 5, 6>(omax2, [&](auto o) {
+            return with_bool(!s->same_order, [&](auto mix) {
+                return launch(s, "grid_rows", grid_rows<T, decltype(o)::value, decltype(mix)::value>,
+                              dim3(persistent_grid(s, g.n[0], 8)), dim3(256), rowc_bytes, st, d, coef, g, ixs, rows, outside,
+                              dout, s->bad, vec_ok);
+            });
+        });
+    } else if (s->nInd == 2 && s->same_order && s->order[0] <= 6 && g.n[0] <= 65535) {
         const int block = 256;
         const int gx = (int)std::max<long long>(1, std::min<long long>((g.n[1] + block - 1) / block, 64));
-#define GRID_SURF(O)                                                                                           \
-    case O:                                                                                                    \
-        hipLaunchKernelGGL((grid_surface<T, O>), dim3(gx, (unsigned)g.n[0]), dim3(block), 0, st, d, coef, g,   \
-                           ixs, rows, outside, dout, s->bad);                                                  \
-        launched = true;                                                                                       \
-        s->last_kernel = "grid_surface";                                                                       \
-        break;
-        switch (s->order[0]) {
-            GRID_SURF(1) GRID_SURF(2) GRID_SURF(3) GRID_SURF(4) GRID_SURF(5) GRID_SURF(6)
-            default: break;
-        }
-#undef GRID_SURF
-    }
-    if (!launched) {
+        r = with_int<1, 2, 3, 4, 5, 6>(s->order[0], [&](auto o) {
+            return launch(s, "grid_surface", grid_surface<T, decltype(o)::value>, dim3(gx, (unsigned)g.n[0]), dim3(block), 0,
+                          st, d, coef, g, ixs, rows, outside, dout, s->bad);
+        });
+    } else {
         const int block = 256;
-        const long long blocks = (total + block - 1) / block;
-        const int gridx = (int)std::max<long long>(1, std::min<long long>(blocks, (long long)s->num_cu * 8));
-        hipLaunchKernelGGL((grid_generic<T>), dim3(gridx), dim3(block), 0, st, d, coef, g, ixs, rows, outside, total,
-                           dout, s->bad);
-        s->last_kernel = "grid_generic";
+        r = launch(s, "grid_generic", grid_generic<T>, dim3(persistent_grid(s, (total + block - 1) / block, 8)), dim3(block), 0,
+                   st, d, coef, g, ixs, rows, outside, total, dout, s->bad);
     }
-    HIPCHK(hipGetLastError());
+    if (r != BSK_OK) return r;
     if (mem == BSK_HOST) {
         HIPCHK(hipMemcpyAsync(out, dout, sizeof(T) * (size_t)total * s->nDep, hipMemcpyDeviceToHost, st));
         return read_bad(s, st, first_bad);
@@ -1987,55 +1742,15 @@ static bsk_status run_tessellate(const bsk_spline *sp, int count, const void *co
     bsk_spline s = sp[0];
     const Desc<T> &d = desc_of<T>(s);
     if (first_bad) *first_bad = -1;
-    GridDims g;
-    long long npar = 0, nrow = 0;
-    for (int iv = 0; iv < MAXI; ++iv) { g.n[iv] = 1; g.goff[iv] = 0; g.roff[iv] = 0; }
-    for (int iv = 0; iv < 2; ++iv) {
-        if (ngrid[iv] < 0) return fail(BSK_ERR_INVALID, "negative grid size");
-        g.n[iv] = ngrid[iv];
-        g.goff[iv] = npar;
-        g.roff[iv] = nrow;
-        npar += ngrid[iv];
-        nrow += ngrid[iv] * s->order[iv];
-    }
-    const long long total = g.n[0] * g.n[1];
-    if (total == 0 || count == 0) return BSK_OK;
-
-    // aux workspace of the first patch: [params (host mode)] [value rows] [derivative rows] [ix] [outside]
-    const size_t par_b = mem == BSK_HOST ? ((sizeof(T) * (size_t)npar + 15) & ~(size_t)15) : 0;
-    const size_t row_b = (sizeof(T) * (size_t)nrow + 15) & ~(size_t)15;
-    const size_t ix_b = (sizeof(int) * (size_t)npar + 15) & ~(size_t)15;
-    if (bsk_status r_ = ws_reserve(s->aux_ws, par_b + 2 * row_b + 2 * ix_b + 2 * (size_t)npar + 32, st); r_ != BSK_OK) return r_;
-    char *base = static_cast<char *>(s->aux_ws.p);
-    T *dpar = reinterpret_cast<T *>(base);
-    T *rows = reinterpret_cast<T *>(base + par_b);
-    T *drows = reinterpret_cast<T *>(base + par_b + row_b);
-    int *ixs = reinterpret_cast<int *>(base + par_b + 2 * row_b);
-    int *ixs2 = reinterpret_cast<int *>(base + par_b + 2 * row_b + ix_b);
-    unsigned char *outside = reinterpret_cast<unsigned char *>(base + par_b + 2 * row_b + 2 * ix_b);
-    unsigned char *outside2 = outside + ((npar + 15) & ~15ll);
-
-    GridAxes<T> ax;
-    long long nmax = 1;
-    for (int iv = 0; iv < MAXI; ++iv) { ax.u[iv] = nullptr; ax.wrt[iv] = 0; }
-    for (int iv = 0; iv < 2; ++iv) {
-        const T *u = static_cast<const T *>(grid[iv]);
-        if (mem == BSK_HOST) {
-            HIPCHK(hipMemcpyAsync(dpar + g.goff[iv], u, sizeof(T) * (size_t)ngrid[iv], hipMemcpyHostToDevice, st));
-            u = dpar + g.goff[iv];
-        }
-        ax.u[iv] = u;
-        nmax = std::max<long long>(nmax, ngrid[iv]);
-    }
-    const T *tab = static_cast<const T *>(s->tab);
-    hipLaunchKernelGGL((basis_rows_grid<T>), dim3((unsigned)((nmax + 255) / 256), 2u), dim3(256), 0, st, d, tab, ax, g, ixs,
-                       rows, outside);
-    if (normals) {
-        ax.wrt[0] = ax.wrt[1] = 1;                            // first-derivative rows of both variables
-        hipLaunchKernelGGL((basis_rows_grid<T>), dim3((unsigned)((nmax + 255) / 256), 2u), dim3(256), 0, st, d, tab, ax, g,
-                           ixs2, drows, outside2);
-    }
-    HIPCHK(hipGetLastError());
+    // tables of the first patch: value rows, and first-derivative rows for the normals
+    GridTables<T> t;
+    const bsk_status rt = grid_tables<T>(s, nullptr, grid, ngrid, mem, 2, normals != nullptr, st, t);
+    if (rt != BSK_OK || t.total == 0) return rt;
+    const GridDims &g = t.g;
+    const long long total = t.total;
+    T *rows = t.rows[0], *drows = t.rows[1];
+    int *ixs = t.ixs[0];
+    unsigned char *outside = t.outside[0];
 
     T *dpos = static_cast<T *>(positions), *dnrm = static_cast<T *>(normals);
     const size_t plane = sizeof(T) * (size_t)total * 3 * (size_t)count;
@@ -2062,29 +1777,25 @@ static bsk_status run_tessellate(const bsk_spline *sp, int count, const void *co
         const int gx = (int)std::max<long long>(1, std::min<long long>(row_units, std::max<long long>(1, (long long)s->num_cu * (tess_w ? tess_w : wide ? 2 : 8) / (wide ? 2 : 1) / np)));
         T *pp = dpos + (size_t)p0 * 3 * (size_t)total;
         T *pn = dnrm ? dnrm + (size_t)p0 * 3 * (size_t)total : nullptr;
-#define TESS_LAUNCH(O, NRM, MIX)                                                                                       \
-    hipLaunchKernelGGL((tess_rows<T, O, NRM, MIX>), dim3(gx, np), dim3(256), lds, st, d, pc, g, ixs, rows,             \
-                       NRM ? drows : rows, outside, pp, pn, s->bad, vec_ok, normalize, negate, tess_r)
-#define TESS_LAUNCH_WIDE(O)                                                                                            \
-    hipLaunchKernelGGL((tess_rows<T, O, false, false, 1>), dim3(gx, np), dim3(512), lds, st, d, pc, g, ixs, rows,      \
-                       rows, outside, pp, pn, s->bad, vec_ok, normalize, negate, tess_r)
-#define TESS(O)                                                                                                        \
-    case O:                                                                                                            \
-        if (s->same_order) { if (normals) TESS_LAUNCH(O, true, false); else if (wide) TESS_LAUNCH_WIDE(O); else TESS_LAUNCH(O, false, false); } \
-        else { if (normals) TESS_LAUNCH(O, true, true); else TESS_LAUNCH(O, false, true); }                            \
-        break;
-        switch (std::max(s->order[0], s->order[1])) {
-            TESS(1) TESS(2) TESS(3) TESS(4) TESS(5) TESS(6)
-            default: return fail(BSK_ERR_UNSUPPORTED, "bsk_tessellate: orders 1..6");
-        }
+        const bsk_status r = with_int<1, 2, 3, 4, 5, 6>(std::max(s->order[0], s->order[1]), [&](auto o) {
+            return with_bool(normals != nullptr, [&](auto nrm) {
+                return with_bool(!s->same_order, [&](auto mix) {
+                    constexpr int O = decltype(o)::value;
+                    constexpr bool NRM = decltype(nrm)::value, MIX = decltype(mix)::value;
+                    if constexpr (!NRM && !MIX)
+                        if (wide)
+                            return launch(s, nullptr, tess_rows<T, O, false, false, 1>, dim3(gx, np), dim3(512), lds, st, d, pc,
+                                          g, ixs, rows, rows, outside, pp, pn, s->bad, vec_ok, normalize, negate, tess_r);
+                    return launch(s, nullptr, tess_rows<T, O, NRM, MIX>, dim3(gx, np), dim3(256), lds, st, d, pc, g, ixs, rows,
+                                  NRM ? drows : rows, outside, pp, pn, s->bad, vec_ok, normalize, negate, tess_r);
+                });
+            });
+        });
+        if (r != BSK_OK) return r;
         // the form launched, on the first patch's handle
         s->last_kernel = !s->same_order ? "tess_rows mixed" : normals ? "tess_rows normals" : wide ? "tess_rows hoisted 512"
                        : hoist ? "tess_rows hoisted 256" : "tess_rows columns";
-#undef TESS
-#undef TESS_LAUNCH
-#undef TESS_LAUNCH_WIDE
     }
-    HIPCHK(hipGetLastError());
     if (mem == BSK_HOST) {
         HIPCHK(hipMemcpyAsync(positions, dpos, plane, hipMemcpyDeviceToHost, st));
         if (normals) HIPCHK(hipMemcpyAsync(normals, dnrm, plane, hipMemcpyDeviceToHost, st));
@@ -2279,17 +1990,11 @@ extern "C" bsk_status bsk_debug_probe(bsk_spline s, int mode, int blocks_per_cu,
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = s->num_cu * std::max(1, blocks_per_cu);
-    if (mode == 0) {
-        HIPCHK(allow_lds(probe_stream<0>, (size_t)lds_bytes));
-        hipLaunchKernelGGL((probe_stream<0>), dim3(grid), dim3(threads), (size_t)lds_bytes, st, static_cast<const double *>(u),
-                           static_cast<const double *>(v), (long long)n, static_cast<double *>(out), (long long)n);
-    } else {
-        HIPCHK(allow_lds(probe_stream<1>, (size_t)lds_bytes));
-        hipLaunchKernelGGL((probe_stream<1>), dim3(grid), dim3(threads), (size_t)lds_bytes, st, static_cast<const double *>(u),
-                           static_cast<const double *>(v), (long long)n, static_cast<double *>(out), (long long)n);
-    }
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    return with_bool(mode != 0, [&](auto wide) {
+        return launch(s, nullptr, probe_stream<decltype(wide)::value ? 1 : 0>, dim3(grid), dim3(threads), (size_t)lds_bytes, st,
+                      static_cast<const double *>(u), static_cast<const double *>(v), (long long)n, static_cast<double *>(out),
+                      (long long)n);
+    });
 }
 
 // Writes (mode 0) or checks (mode 1) `pattern` over the whole LDS of every CU: 8 * num_cu workgroups of 1024 lanes with

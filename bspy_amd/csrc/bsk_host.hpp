@@ -10,6 +10,7 @@
 #include <limits>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "bsk_common.hpp"
@@ -159,6 +160,45 @@ inline hipError_t allow_lds(K kernel, size_t bytes)
     hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (err == hipSuccess) done.emplace_back(fn, dev, bytes);
     return err;
+}
+
+// Workgroups of a persistent launch: one per unit of work, at most per_cu on every CU.
+inline int persistent_grid(bsk_spline s, long long units, long long per_cu)
+{
+    return (int)std::max<long long>(1, std::min<long long>(units, (long long)s->num_cu * per_cu));
+}
+
+// Workgroups per CU of the kernels that hold a table image in LDS: two when two images fit.
+inline int lds_per_cu(bsk_spline s, size_t lds_bytes)
+{
+    return (int)std::max<size_t>(1, std::min<size_t>(2, s->lds_max / lds_bytes));
+}
+
+// Every kernel launch of the point and grid paths: raises the dynamic-LDS limit where the launch needs it, records
+// the kernel family for bsk_last_kernel (`name` may be null: epilogues and helpers are not a family) and checks the launch.
+template <typename K, typename... Args>
+inline bsk_status launch(bsk_spline s, const char *name, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                         const Args &...args)
+{
+    HIPCHK(allow_lds(kernel, lds));
+    if (name) s->last_kernel = name;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    HIPCHK(hipGetLastError());
+    return BSK_OK;
+}
+
+// Run-time value -> template constant: f receives a std::integral_constant.  with_int<A, B, ..., Z>(v, f) hands over
+// v's own class, and Z for every value that is not listed (callers check the range, or Z is the "any" class).
+template <typename F>
+inline bsk_status with_bool(bool b, F &&f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int N0, int... Ns, typename F>
+inline bsk_status with_int(int v, F &&f)
+{
+    if constexpr (sizeof...(Ns) == 0) return f(std::integral_constant<int, N0>{});
+    else return v == N0 ? f(std::integral_constant<int, N0>{}) : with_int<Ns...>(v, f);
 }
 
 
