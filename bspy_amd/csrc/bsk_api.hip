@@ -551,6 +551,16 @@ static bool unclamp_matrix(int O, std::vector<long double> &M)
             for (int i = 0; i < O; ++i) { U[(size_t)r * O + i] -= f * U[(size_t)c * O + i]; C[(size_t)r * O + i] -= f * C[(size_t)c * O + i]; }
         }
     }
+    // M is upper triangular with the identity in its last row: the clamped form arises from the uniform one by inserting
+    // knots at the domain end, so uniform control point i is a combination of the clamped control points i .. O - 2 alone.
+    // The elimination leaves ~1e-18 below the diagonal, and such an entry carries a boundary control point into control
+    // points whose cells do not contain it: 2^20 times larger than its neighbours, it moved them by 1e-12 of their own
+    // scale (tests/test_gpu_scale.py, part C).  The structural zeros are therefore stored as zeros.
+    for (int i = 0; i < O; ++i)
+        for (int j = 0; j < i; ++j) {
+            if (std::fabs(C[(size_t)i * O + j]) > 1e-15L) return false;
+            C[(size_t)i * O + j] = 0;
+        }
     M = C;
     return true;
 }

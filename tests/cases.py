@@ -259,3 +259,157 @@ def bench_spline(cfg, seed=0):
     knots = [clamped_uniform_knots(o, c, dt) for o, c in zip(order, ncoef)]
     coefs = rng.standard_normal((ndep, *ncoef)).astype(dt)
     return nind, ndep, order, ncoef, knots, coefs, dt
+
+
+# ---------------------------------------------------------------------------------------------
+# Scale tests (tests/test_scale_host.py, tests/test_gpu_scale.py): identical inputs for the CPU preconditions and the
+# GPU checks.  Points are drawn by scale_ref.sample_points(order, nCoef, knots, n, dtype, default_rng(seed)).
+# ---------------------------------------------------------------------------------------------
+class ScaleFamily:
+    """One kernel family of the exact-scaling-law sweep: a spline, a batch size, the BSK_VARIANT that forces the family
+    and its calls (kind, wrt, kernel): kind in eval / jac / normal / curv / grid / tess / tessn / integral; `kernel` is
+    what last_kernel() must name (a trailing * matches a part of it)."""
+
+    def __init__(self, name, order, ncoef, knots, coefs, dt, n, calls, variant=None, seed=1, env=None, grid=None):
+        self.name, self.order, self.nCoef, self.knots, self.coefs, self.dt = name, tuple(order), tuple(ncoef), knots, coefs, dt
+        self.n, self.calls, self.variant, self.seed, self.env, self.grid = n, calls, variant, seed, env or {}, grid
+        self.nInd, self.nDep = len(order), coefs.shape[0]
+
+    @property
+    def kind(self):
+        return "fp32" if self.dt == np.float32 else "fp64"
+
+
+def _scale_spec(order, ncoef, ndep, dt, seed, lo=-1.0, hi=1.0, uniform=False):
+    rng = np.random.default_rng(seed)
+    if uniform:
+        knots = [clamped_uniform_knots(o, c, dt, lo, hi) for o, c in zip(order, ncoef)]
+    else:
+        knots = [nonuniform_knots(rng, o, c, dt, lo, hi) for o, c in zip(order, ncoef)]
+    return tuple(order), tuple(ncoef), knots, rng.standard_normal((ndep, *ncoef)).astype(dt)
+
+
+def _point_calls(order, ev, jac=None, extra=()):
+    """value, a first derivative (variable 0) and the highest non-zero derivative (last variable), then the jacobian."""
+    nind = len(order)
+    first = (1,) + (0,) * (nind - 1)
+    top = (0,) * (nind - 1) + (order[-1] - 1,)
+    calls = [("eval", (0,) * nind, ev), ("eval", first, ev)]
+    if top not in (first, (0,) * nind):
+        calls.append(("eval", top, ev))
+    if jac:
+        calls.append(("jac", None, jac))
+    return calls + list(extra)
+
+
+def scale_families():
+    """The enumeration of tests/test_gpu_stale_lds.py (same shapes, sizes and forcing variants), one entry per family."""
+    f32, f64 = np.float32, np.float64
+    P = {c.name: c for c in parity_cases()}
+    fams = []
+
+    def add(name, spec, dt, n, calls, **kw):
+        fams.append(ScaleFamily(name, *spec, dt, n, calls, **kw))
+
+    add("eval_slab2", _scale_spec((5, 3), (12, 40), 4, f32, 534), f32, (1 << 20) + 4_099,
+        [("eval", (0, 0), "eval_slab2"), ("eval", (1, 0), "eval_slab2"), ("eval", (4, 0), "eval_slab2"), ("eval", (0, 2), "eval_slab2")])
+    _, _, o, nc, k, cf, dt = bench_spline(2)
+    add("eval_uni / jac_uni", (o, nc, k, cf), f64, 20_011, _point_calls(o, "eval_uni", "jac_uni", [("normal", None, "jac_uni")]))
+    c = P["cfg2_bicubic_nonuniform"]
+    add("eval_rowrot / jac_rowrot / curv_rowrot", (c.order, c.nCoef, c.knots, c.coefs), f64, 20_011,
+        _point_calls(c.order, "eval_rowrot", "jac_rowrot", [("normal", None, "jac_rowrot"), ("curv", None, "curv_rowrot")]))
+    add("eval_rec32", _scale_spec((4, 4), (37, 16), 4, f32, 13, -2.0, 3.0), f32, 20_011, _point_calls((4, 4), "eval_rec32"))
+    add("eval_stream / jac_stream", _scale_spec((3, 3, 3), (6, 7, 5), 2, f64, 14), f64, 20_011,
+        _point_calls((3, 3, 3), "eval_stream", "jac_stream"), variant="4")
+    add("eval_stream_uni / jac_stream_uni, curve", _scale_spec((4,), (40,), 3, f64, 141, 0.0, 1.0, uniform=True), f64, 20_011,
+        [("eval", (0,), "eval_stream_uni"), ("eval", (1,), "eval_stream_uni"), ("eval", (3,), "eval_stream_uni"), ("jac", None, "jac_stream_uni")])
+    add("eval_stream_uni / jac_stream_uni, volume", _scale_spec((4, 4, 4), (8, 9, 10), 1, f64, 142, 0.0, 1.0, uniform=True), f64, 20_011,
+        _point_calls((4, 4, 4), "eval_stream_uni", "jac_stream_uni"))
+    add("eval_fixed / jac_fixed", (c.order, c.nCoef, c.knots, c.coefs), f64, 20_011,
+        _point_calls(c.order, "eval_fixed", "jac_fixed"), variant="1")
+    m = P["surface_o3x4"]
+    add("eval_mixed / jac_mixed", (m.order, m.nCoef, m.knots, m.coefs), f64, 20_011, _point_calls(m.order, "eval_mixed", "jac_mixed"))
+    add("eval_generic", _scale_spec((14,), (24,), 2, f64, 16), f64, 20_011,
+        [("eval", (0,), "eval_generic"), ("eval", (1,), "eval_generic"), ("eval", (13,), "eval_generic")])
+    add("eval_gather", _scale_spec((4, 4), (200, 150), 2, f64, 17), f64, 20_011, _point_calls((4, 4), "eval_gather*"))
+    _, _, o5, nc5, k5, cf5, _ = bench_spline(5)
+    for variant, kernel in (("0", "eval_cellsort, MFMA*"), ("12", "eval_cellsort, VALU*"), ("13", "eval_binned_lds*")):
+        add(kernel.rstrip("*"), (o5, nc5, k5, cf5), f32, 400_003, _point_calls(o5, kernel), variant=variant)
+    add("fused jacobian", _scale_spec((3, 3, 3), (38, 34, 40), 3, f32, 19, 0.0, 1.0), f32, 280_003, [("jac", None, "fused jacobian*")])
+    # grids and tessellation
+    g = _scale_spec((4, 4), (20, 18), 3, f64, 21)
+    for what, shape in (("grid_rows vector", (40, 128)), ("grid_rows scalar", (40, 77)), ("grid_surface", (40, 40))):
+        add(what, g, f64, 0, [("grid", (0, 0), what.split()[0]), ("grid", (1, 0), what.split()[0]), ("grid", (0, 3), what.split()[0])], grid=shape)
+    v = P["volume_o3x4x2"]
+    add("grid_generic", (v.order, v.nCoef, v.knots, v.coefs), f64, 0,
+        [("grid", (0, 0, 0), "grid_generic"), ("grid", (1, 0, 0), "grid_generic"), ("grid", (0, 3, 0), "grid_generic")], grid=(13, 17, 9))
+    for dt in (f32, f64):
+        for form in ("hoisted 512", "hoisted 256", "normals", "mixed"):
+            order = (3, 4) if form == "mixed" else (4, 4)
+            kind = "tessn" if form in ("normals", "mixed") else "tess"
+            add(f"tess_rows {form}, {'fp32' if dt == f32 else 'fp64'}", _scale_spec(order, (9, 8), 3, dt, 22, 0.0, 1.0), dt, 0,
+                [(kind, None, f"tess_rows {form}")], grid=(24, 128), env={"BSK_TESS_T": "256"} if form == "hoisted 256" else None)
+    # quadrature: one Gauss-Kronrod round in MEASURE mode
+    add("integral_regions", _scale_spec((3, 4), (7, 6), 3, f64, 23, 0.0, 1.0, uniform=True), f64, 0, [("integral", None, "integral_regions")])
+    return fams
+
+
+# (kc, kp): coefficients x 2^kc, knots and parameters x 2^kp; the rows pattern is cycled over the dependent variables
+SCALE_EXPONENTS = {"fp64": [(40, 0), (-40, 20), (0, -20)], "fp32": [(12, 0), (-12, 6), (-20, -8)]}
+SCALE_ROWS = {"fp64": (30, 0, -30), "fp32": (12, 0, -12)}
+
+
+def scale_fit_systems():
+    """(order, rows, cols, outer, inner, seed) of the banded least-squares systems: fit_sweep, fit_sweep turned (inner 1,
+    outer > 1) and fit_residual on each; the data scale 2^k."""
+    return [(4, 91, 23, 3, 37, 104), (4, 91, 23, 65, 1, 104), (6, 91, 23, 1, 200, 106), (2, 91, 23, 1000, 1, 102)], (40, -40)
+
+
+class ScaleSpline:
+    """A spline of the shifted-domain sweep, defined on [0, 1]^nInd; scale_ref.map_domain moves it."""
+
+    def __init__(self, name, order, ncoef, ndep, seed, uniform=True, dt=np.float64, general=("eval_stream", "jac_stream"),
+                 uni=("eval_stream_uni", "jac_stream_uni")):
+        self.name, self.dt, self.uniform = name, dt, uniform
+        self.order, self.nCoef, self.knots, self.coefs = _scale_spec(order, ncoef, ndep, dt, seed, 0.0, 1.0, uniform)
+        self.general, self.uni = general, uni
+
+
+def scale_splines():
+    rr, un = ("eval_rowrot", "jac_rowrot"), ("eval_uni", "jac_uni")
+    _, _, o, nc, k, cf, _ = bench_spline(2)
+    cfg2 = ScaleSpline("cfg2 bicubic", o, nc, 3, 0, general=rr, uni=un)
+    cfg2.knots, cfg2.coefs = k, cf
+    return [cfg2,
+            ScaleSpline("cubic curve, 64 coefficients", (4,), (64,), 2, 602),
+            ScaleSpline("order 3 volume", (3, 3, 3), (8, 9, 7), 2, 603),
+            ScaleSpline("order 5 surface", (5, 5), (12, 11), 3, 604),
+            ScaleSpline("cfg2 bicubic, non-uniform", (4, 4), (64, 64), 3, 605, uniform=False, general=rr, uni=un)]
+
+
+def scale_splines_f32():
+    """fp32 takes the uniform path at order 2 only (nothing to unclamp)."""
+    return [ScaleSpline("order 2 surface, fp32", (2, 2), (40, 33), 3, 606, dt=np.float32, general=("eval_rowrot", "jac_rowrot"),
+                        uni=("eval_uni", "jac_uni"))]
+
+
+# (lo, width) of the shifted and stretched domains
+SCALE_DOMAINS = [(0.0, 1.0), (8.0, 1.0), (33.0, 1.0), (1000.0, 64.0), (3.0, 0.125), (1000.0, 1.0), (1e6, 0.021), (-1001.0, 1.0),
+                 (0.1, 3e-7), (-5e8, 1e9)]
+SCALE_DOMAINS_F32 = [(0.0, 1.0), (100.0, 1.0), (0.0, 2.0 ** -10)]
+SCALE_SAMPLE = 2_000
+
+
+def scale_illscaled():
+    """Surfaces of order 3, 4, 5 and a volume on the unclamping paths; the outermost control-point layer x 2^20."""
+    return [ScaleSpline("order 3 surface", (3, 3), (9, 10), 2, 701),
+            ScaleSpline("order 4 surface", (4, 4), (12, 11), 3, 702, general=("eval_rowrot", "jac_rowrot"), uni=("eval_uni", "jac_uni")),
+            ScaleSpline("order 5 surface", (5, 5), (12, 13), 2, 703),
+            ScaleSpline("order 3 volume", (3, 3, 3), (8, 7, 9), 2, 704)]
+
+
+def scale_cases():
+    """Everything the scale tests share, by part: A families / exponents / fit systems, B splines / domains, C splines."""
+    return {"families": scale_families(), "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "fit": scale_fit_systems(),
+            "splines": scale_splines(), "domains": SCALE_DOMAINS, "splines_f32": scale_splines_f32(),
+            "domains_f32": SCALE_DOMAINS_F32, "sample": SCALE_SAMPLE, "illscaled": scale_illscaled()}

@@ -757,36 +757,7 @@ def test_reference_json_files_evaluate():
                 assert d_gpu <= max(4.0 * d_orc, 1e-11), (name, w, d_gpu, d_orc)
 
 
-def _curve_derivative_longdouble(order, knots, coefs, deriv, us):
-    """Reference bspy/_spline_evaluation.py:4-27 + :109-133 for a curve, every operation in np.longdouble."""
-    L = np.longdouble
-    k = knots.astype(L)
-    c = coefs.astype(L)
-    out = np.zeros((c.shape[0], len(us)), L)
-    ncoef = len(k) - order
-    for n, uf in enumerate(us):
-        u = L(uf)
-        ix = int(np.searchsorted(knots, uf, side="right"))
-        ix = min(max(ix, order), ncoef)
-        b = np.zeros(order, L)
-        if deriv < order:
-            b[-1] = 1
-            for degree in range(1, order - deriv):
-                bi = order - degree
-                for i in range(ix - degree, ix):
-                    alpha = (u - k[i]) / (k[i + degree] - k[i])
-                    b[bi - 1] += (1 - alpha) * b[bi]
-                    b[bi] *= alpha
-                    bi += 1
-            for degree in range(order - deriv, order):
-                bi = order - degree
-                for i in range(ix - degree, ix):
-                    alpha = L(degree) / (k[i + degree] - k[i])
-                    b[bi - 1] += -alpha * b[bi]
-                    b[bi] *= alpha
-                    bi += 1
-        out[:, n] = c[:, ix - order:ix] @ b
-    return out
+from scale_ref import _curve_derivative_longdouble  # noqa: E402  (moved there: the scale tests extend it to tensor products)
 
 
 NORMAL_CASES = [n for n, c in CASES.items() if abs(c.nInd - c.nDep) == 1 and max(c.nInd, c.nDep) <= 4]
