@@ -30,6 +30,7 @@ PRODUCT_SYMBOLS = (
     "bsk_multi_jacobian", "bsk_integral",
     "bsk_fit_create", "bsk_fit_destroy", "bsk_fit_info", "bsk_fit_solve_host", "bsk_fit_sweep", "bsk_fit_residual",
     "bsk_fit_last_kernel",
+    "bsk_band_create", "bsk_band_destroy", "bsk_band_apply_host", "bsk_band_apply", "bsk_band_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -120,6 +121,12 @@ def lib():
     L.bsk_fit_residual.argtypes = [_vp, ctypes.c_int, _vp, _vp, _i64, _i64, _vp, _vp]
     L.bsk_fit_last_kernel.argtypes = [_vp]
     L.bsk_fit_last_kernel.restype = ctypes.c_char_p
+    L.bsk_band_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _vp, ctypes.POINTER(_vp)]
+    L.bsk_band_destroy.argtypes = [_vp]
+    L.bsk_band_apply_host.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _vp]
+    L.bsk_band_apply.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _vp, _vp]
+    L.bsk_band_last_kernel.argtypes = [_vp]
+    L.bsk_band_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -127,7 +134,7 @@ def lib():
                                         ctypes.c_int, _ip]
     L.bsk_debug_fill_lds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _i64p, _vp]
     for name in SYMBOLS:
-        if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel"):
+        if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

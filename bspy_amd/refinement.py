@@ -1,0 +1,410 @@
+"""
+Spline to spline: ``insert_knots``, ``elevate``, ``elevate_and_insert_knots``, ``trim``, ``clamp`` and ``differentiate``
+(reference bspy/_spline_domain.py:32, :110, :341, :610 and bspy/_spline_operations.py:244).
+
+For one independent variable each of these is one small banded linear operator, the same for every line of the
+coefficient tensor along that variable: ``out[j] = sum_t w[j, t] * in[first[j] + t]`` (``BandMap``).  The knot-vector
+logic (the reference's checks, messages and resulting knots, bit for bit) and the construction of the operator are
+host work in this file; streaming the lines through the operator is the expensive part:
+
+    device path   ``bsk_band_apply``: band_apply (lanes along the inner extent) or band_apply_line (the last variable,
+                  whose lines are contiguous); a multi-variable call keeps the intermediate tensors on the device
+    host path     ``bsk_band_apply_host``: the same operator on the CPU, for small tensors and K above 8
+
+The refinement operator is exact linear algebra, built by blossoming: new coefficient j of the spline of order k + m
+on the knots tbar is the blossom of the order-elevated polynomial piece of one old knot cell mu inside the support of
+new basis function j, at tbar[j + 1 .. j + k + m - 1]; the elevated blossom is the mean over the (k - 1)-subsets of its
+arguments of the piece's own blossom, which the multi-affine de Boor recurrence on cell mu gives as weights on the old
+coefficients mu - k + 1 .. mu.  No derivative is taken and nothing is integrated back, so the operator's error is a
+few ulp whatever the knot spacing.
+
+``_path="device" | "host"`` (or ``refinement.FORCE_PATH``) pins the path; ``refinement.LAST_PATHS`` lists what every
+variable of the last call ran ("band_apply", "band_apply_line", "host band").
+"""
+import ctypes
+import itertools
+
+import numpy as np
+
+from . import _native as nv
+
+# Elements of the coefficient tensor (the larger of input and result) from which the device path is taken.  The key is
+# the total element count: see DESIGN.md section 13 for its standing.
+DEVICE_MIN_ELEMENTS = 1 << 16
+DEVICE_MIN_K, DEVICE_MAX_K = 2, 8
+FORCE_PATH = None          # None, "device" or "host"
+LAST_PATHS = []
+
+
+class BandMap:
+    """out[j] = sum_t w[j, t] * in[first[j] + t] (``bsk_band`` handle).  first: (nOut,) non-decreasing; w: (nOut, K)."""
+
+    def __init__(self, first, w, nIn):
+        self.first = np.ascontiguousarray(first, np.int32)
+        self.w = np.ascontiguousarray(w, np.float64)
+        self.nOut, self.K = self.w.shape
+        self.nIn = int(nIn)
+        handle = ctypes.c_void_p()
+        nv.check(nv.lib().bsk_band_create(self.nIn, self.nOut, self.K, self.first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          self.w.ctypes.data, ctypes.byref(handle)))
+        self._handle = handle
+
+    def close(self):
+        if self._handle is not None:
+            nv.lib().bsk_band_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_kernel(self):
+        return nv.lib().bsk_band_last_kernel(self._handle).decode()
+
+    def apply_line(self, x):
+        """One line in NumPy, the statement of what the library computes: fp64 products added in the order of t."""
+        x = np.asarray(x)
+        acc = np.zeros(self.nOut, np.float64)
+        for t in range(self.K):
+            acc += self.w[:, t] * x[self.first + t].astype(np.float64)
+        return acc.astype(x.dtype)
+
+    def apply_host(self, a, outer, inner):
+        """a: NumPy float32 / float64 of outer * nIn * inner values -> (outer, nOut, inner), same dtype."""
+        a = np.ascontiguousarray(a)
+        out = np.empty((outer, self.nOut, inner), a.dtype)
+        nv.check(nv.lib().bsk_band_apply_host(self._handle, nv.dtype_code(a.dtype), a.ctypes.data, outer, inner, out.ctypes.data))
+        return out
+
+    def apply_device(self, a, outer, inner):
+        """a: contiguous torch CUDA tensor of outer * nIn * inner float32 / float64 -> (outer, nOut, inner), same dtype."""
+        import torch
+        with torch.cuda.device(a.device):
+            out = torch.empty((outer, self.nOut, inner), dtype=a.dtype, device=a.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
+            nv.check(nv.lib().bsk_band_apply(self._handle, code, a.data_ptr(), outer, inner, out.data_ptr(), stream))
+        return out
+
+
+# ------------------------------------------------------------------------------------------ operators
+def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
+    """BandMap arrays (first, w) that take the coefficients on ``knots`` (order k) to those of the same function on
+    ``newKnots`` (order k + m), for the output rows ``rows`` (a slice; default all).  ``newKnots`` must hold every
+    distinct knot of ``knots`` with at least its multiplicity + m.  ``origin`` (m == 0): for every new knot the index
+    of the old knot it is, or -1 for an inserted one; a row whose blossom arguments are consecutive old knots is then
+    the exact unit row.
+    Rows whose support has no cell inside the domain take the domain's nearest cell: they hold the coefficients of
+    the polynomial extension of that piece."""
+    t = np.asarray(knots, np.float64)
+    tb = np.asarray(newKnots, np.float64)
+    k = int(order)
+    n = k + m - 1                                   # arguments of the elevated blossom
+    nIn, nOut = len(t) - k, len(tb) - k - m
+    j = np.arange(nOut)[rows if rows is not None else slice(None)]
+    # the non-empty new cell nearest the middle of the support (the lower one of two equally near)
+    cell = np.full(len(j), -1)
+    for off in sorted(range(n + 1), key=lambda o: (abs(o - 0.5 * n), o)):
+        c = j + off
+        take = (cell < 0) & (tb[c + 1] > tb[c])
+        cell[take] = c[take]
+    cell[cell < 0] = (j + n // 2)[cell < 0]
+    lo, hi = t[k - 1], t[nIn]
+    x = np.clip(0.5 * (tb[cell] + tb[cell + 1]), lo, hi)
+    mu = np.searchsorted(t, x, "right") - 1
+    mu[x >= hi] = np.searchsorted(t, hi, "left") - 1
+    mu = np.clip(mu, k - 1, nIn - 1)
+    first = mu - k + 1
+
+    # the recurrence runs in extended precision where the platform has it (x86: 64-bit mantissa), so that the
+    # weights are correctly rounded doubles but for rare ties; elsewhere it runs in double
+    t, tb = t.astype(np.longdouble), tb.astype(np.longdouble)
+    w = np.zeros((len(j), k), np.longdouble)
+    subsets = list(itertools.combinations(range(n), k - 1))
+    for subset in subsets:
+        D = np.broadcast_to(np.eye(k, dtype=np.longdouble), (len(j), k, k)).copy()        # D[row, p] = weights of d_p on the k old coefficients
+        for r, a in enumerate(subset, start=1):
+            u = tb[j + 1 + a]
+            for q in range(k - 1, r - 1, -1):
+                i = first + q
+                left, right = t[i], t[i + k - r]
+                den = right - left
+                D[:, q] = ((right - u) / den)[:, None] * D[:, q - 1] + ((u - left) / den)[:, None] * D[:, q]
+        w += D[:, k - 1]
+    w = (w / len(subsets)).astype(np.float64)
+    if m == 0 and origin is not None and k > 1:
+        # the blossom's arguments are k - 1 consecutive old knots: the value is the old coefficient in front of them
+        origin = np.asarray(origin)
+        old = origin[j + 1] - 1
+        unit = origin[j + 1] >= 0
+        for s in range(2, k):
+            unit &= origin[j + s] == old + s
+        unit &= (old >= first) & (old < first + k)
+        w[unit] = 0.0
+        w[unit, (old - first)[unit]] = 1.0
+    return first.astype(np.int32), w
+
+
+def differentiate_map(knots, order):
+    """(first, w) of the derivative's coefficients: K = 2, w = (-alpha_j, alpha_j), alpha_j = (k - 1) / (t[j + k] - t[j + 1]).
+    Two limits of this form: an interior knot of multiplicity k makes alpha_j infinite (``differentiate`` refuses such a
+    spline; the reference returns inf / nan), and -alpha c[j] + alpha c[j + 1] rounds two products where
+    alpha (c[j + 1] - c[j]) rounds one difference, so for coefficients with a large common offset the error relative to
+    the derivative's coefficients grows as eps |c| / |c[j + 1] - c[j]|; relative to alpha |c| it stays at eps."""
+    t = np.asarray(knots, np.float64)
+    k = int(order)
+    n = len(t) - k - 1
+    with np.errstate(divide="ignore"):
+        alpha = (k - 1) / (t[k:k + n] - t[1:1 + n])
+    return np.arange(n, dtype=np.int32), np.stack([-alpha, alpha], axis=1)
+
+
+# ------------------------------------------------------------------------------------------ application
+def _is_torch(a):
+    return type(a).__module__.startswith("torch")
+
+
+def apply(band, tensor, axis):
+    """Apply ``band`` along ``axis`` of a torch CUDA tensor (float32 / float64); returns a new CUDA tensor of the same
+    type whose extent along ``axis`` is band.nOut.  For pipelines that stay on the device.  ``LAST_PATHS`` holds this
+    call's kernel only (``band.last_kernel()`` says the same)."""
+    out = _apply(band, tensor, axis)
+    LAST_PATHS[:] = [band.last_kernel()] if out.numel() else []
+    return out
+
+
+def _apply(band, tensor, axis):
+    import torch
+    if not (_is_torch(tensor) and tensor.is_cuda):
+        raise TypeError("refinement.apply takes a torch CUDA tensor")
+    if tensor.dtype not in (torch.float32, torch.float64):
+        raise TypeError("refinement.apply takes float32 or float64")
+    axis = axis % tensor.dim()
+    shape = list(tensor.shape)
+    if shape[axis] != band.nIn:
+        raise ValueError(f"axis {axis} has {shape[axis]} entries, the map takes {band.nIn}")
+    if not (DEVICE_MIN_K <= band.K <= DEVICE_MAX_K):
+        raise ValueError(f"the device path covers K from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
+    outer = int(np.prod(shape[:axis], dtype=np.int64))
+    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    shape[axis] = band.nOut
+    if outer * inner == 0:
+        return torch.empty(shape, dtype=tensor.dtype, device=tensor.device)
+    return band.apply_device(tensor.contiguous(), outer, inner).reshape(shape)
+
+
+def _run(coefs, steps, path):
+    """coefs: NumPy (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step, the one that shrinks the tensor most
+    first and the one that grows it most last (the operators of different variables commute), and returns NumPy."""
+    path = path if path is not None else FORCE_PATH
+    if path not in (None, "device", "host"):
+        raise ValueError("_path must be None, 'device' or 'host'")
+    del LAST_PATHS[:]
+    if not steps:
+        return coefs
+    steps = sorted(steps, key=lambda s: len(s[1]) / coefs.shape[s[0]])
+    bands = [(axis, BandMap(first, w, coefs.shape[axis])) for axis, first, w in steps]
+    try:
+        if coefs.size == 0:
+            shape = list(coefs.shape)
+            for axis, band in bands:
+                shape[axis] = band.nOut
+            return np.empty(shape, coefs.dtype)
+        covered = all(DEVICE_MIN_K <= band.K <= DEVICE_MAX_K for _, band in bands)
+        if path is None:
+            size = coefs.size
+            for axis, band in bands:
+                size = max(size, size // band.nIn * band.nOut)
+            path = "device" if covered and size >= DEVICE_MIN_ELEMENTS else "host"
+        if path == "device":
+            if not covered:
+                raise ValueError(f"the device path covers K from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
+            import torch
+            data = torch.from_numpy(np.ascontiguousarray(coefs)).cuda()
+            for axis, band in bands:
+                data = _apply(band, data, axis)
+                LAST_PATHS.append(band.last_kernel())
+            return data.cpu().numpy()
+        data = coefs
+        for axis, band in bands:
+            shape = list(data.shape)
+            outer = int(np.prod(shape[:axis], dtype=np.int64))
+            inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+            shape[axis] = band.nOut
+            data = band.apply_host(data, outer, inner).reshape(shape)
+            LAST_PATHS.append(band.last_kernel())
+        return data
+    finally:
+        for _, band in bands:
+            band.close()
+
+
+# ------------------------------------------------------------------------------------------ knot vectors
+def merged_knots(knots, order, entries):
+    """Knots of one variable after insert_knots' ``entries`` (values or (value, multiplicity) pairs, taken in turn as the
+    reference takes them: a pair with multiplicity < 1 is skipped unseen, a value is cast to the knots' dtype, must lie
+    in the domain, and may not raise a knot's multiplicity, with what the list has added so far, above the order).
+    Returns (merged, origin): origin[i] is the index of the old knot that merged[i] is, or -1 for a new one; new knots
+    stand behind old knots of the same value.  ``knots`` itself comes back when the list adds nothing."""
+    lo, hi = knots[order - 1], knots[len(knots) - order]
+    added = {}
+    for entry in entries:
+        value, times = (entry, 1) if np.isscalar(entry) else (entry[0], entry[1])
+        if times < 1:
+            continue
+        value = knots.dtype.type(value)
+        if value < lo or value > hi:
+            raise ValueError(f"Knot insertion outside domain: {value}")
+        if int(np.count_nonzero(knots == value)) + added.get(value, 0) + times > order:
+            raise ValueError("Knot multiplicity > order")
+        added[value] = added.get(value, 0) + times
+    if not added:
+        return knots, np.arange(len(knots))
+    fresh = np.repeat(np.array(list(added), knots.dtype), list(added.values()))
+    both = np.concatenate((knots, fresh))
+    rank = np.argsort(both, kind="stable")              # stable: equal values keep old before new
+    return both[rank], np.where(rank < len(knots), rank, -1)
+
+
+def _rebuild(spline, order, knots, coefs):
+    return type(spline)(spline.nInd, spline.nDep, order, coefs.shape[1:], knots, coefs, spline.metadata)
+
+
+def insert_knots(self, newKnots, _path=None):
+    del LAST_PATHS[:]
+    if len(newKnots) != self.nInd:
+        raise ValueError("Invalid newKnots")
+    if self.nInd == 0:
+        return self
+    knots, steps = list(self.knots), []
+    for iv, entries in enumerate(newKnots):
+        merged, origin = merged_knots(self.knots[iv], self.order[iv], entries)
+        if merged is not self.knots[iv]:
+            knots[iv] = merged
+            steps.append((iv + 1, *refine_map(self.knots[iv], self.order[iv], merged, 0, origin=origin)))
+    return _rebuild(self, self.order, knots, _run(self.coefs, steps, _path))
+
+
+def _bound_plan(knots, order, value, eps, right):
+    """Where a trim bound lands and how many copies of it have to be inserted for full multiplicity: the bound snaps to
+    a distinct knot less than eps above it, else to one less than eps below it.  For a right bound that snaps downwards
+    the reference counts the copies of the FIRST distinct knot as present (its observable result, pinned by goldens)."""
+    distinct, counts = np.unique(knots, return_counts=True)
+    above = int(np.searchsorted(distinct, value))
+    if distinct[above] - value < eps:
+        return distinct[above], order - counts[above]
+    if above > 0 and value - distinct[above - 1] < eps:
+        return distinct[above - 1], order - (counts[0] if right else counts[above - 1])
+    return value, order
+
+
+def trim(self, newDomain, _path=None):
+    del LAST_PATHS[:]                        # also when the spline itself is returned: nothing ran
+    if len(newDomain) != self.nInd:
+        raise ValueError("Invalid newDomain")
+    if self.nInd < 1:
+        return self
+    box = np.array(newDomain, self.knots[0].dtype, copy=True)            # None becomes nan: that side is kept
+    eps = np.finfo(box.dtype).eps
+
+    entries, changed = [], False
+    for iv, bounds in enumerate(box):
+        if len(bounds) != 2:
+            raise ValueError("Invalid newDomain")
+        t, k = self.knots[iv], self.order[iv]
+        ends = (t[k - 1], t[len(t) - k])
+        wanted = []
+        for side in (0, 1):
+            if np.isnan(bounds[side]):
+                continue
+            if not (ends[0] <= bounds[side] <= ends[1]):
+                raise ValueError("Invalid newDomain")
+            if side == 1 and not np.isnan(bounds[0]) and not (bounds[0] < bounds[1]):
+                raise ValueError("Invalid newDomain")
+            bounds[side], missing = _bound_plan(t, k, bounds[side], eps, side == 1)
+            if missing > 0:
+                wanted.append((bounds[side], missing))
+            changed = changed or missing > 0 or bounds[side] != ends[side]
+        entries.append(wanted)
+    if not changed:
+        return self
+
+    # one operator per variable: the insertion at the bounds, restricted to the rows between them
+    knots, steps = [], []
+    for iv, (wanted, (lower, upper)) in enumerate(zip(entries, box)):
+        t, k = self.knots[iv], self.order[iv]
+        merged, origin = merged_knots(t, k, wanted)
+        row0 = 0 if np.isnan(lower) else int(np.searchsorted(merged, lower))
+        row1 = len(merged) - k if np.isnan(upper) else int(np.searchsorted(merged, upper))
+        knots.append(merged[row0:row1 + k])
+        if merged is not t or (row0, row1) != (0, len(t) - k):
+            steps.append((iv + 1, *refine_map(t, k, merged, 0, rows=slice(row0, row1), origin=origin)))
+    return _rebuild(self, self.order, knots, _run(self.coefs, steps, _path))
+
+
+def clamp(self, left, right, _path=None):
+    """A trim to the spline's own domain on the listed sides."""
+    variables = range(self.nInd)
+    left, right = {variables[i] for i in left}, {variables[i] for i in right}
+    ends = [(t[k - 1], t[n]) for t, k, n in zip(self.knots, self.order, self.nCoef)]
+    box = [[lo if iv in left else None, hi if iv in right else None] for iv, (lo, hi) in enumerate(ends)]
+    return trim(self, box, _path)
+
+
+def elevated_knots(knots, order, m, newKnots):
+    """Knots of a left-clamped variable after elevation by m with the plain values ``newKnots`` added (the reference's
+    rule): a distinct old knot gets multiplicity min(max(its count with the new values, its old count + m), order + m),
+    a distinct new value keeps its count.  The result has the dtype of the concatenation, as the reference's has."""
+    old, old_count = np.unique(knots, return_counts=True)
+    values, count = np.unique(np.concatenate((knots, np.ravel(newKnots))), return_counts=True)
+    at = np.searchsorted(values, old)
+    count[at] = np.minimum(np.maximum(count[at], old_count + m), order + m)
+    return np.repeat(values, count)
+
+
+def elevate_and_insert_knots(self, m, newKnots, _path=None):
+    del LAST_PATHS[:]
+    if len(m) != self.nInd:
+        raise ValueError("Invalid m")
+    if len(newKnots) != self.nInd:
+        raise ValueError("Invalid newKnots")
+    touched = []
+    for iv, (raise_by, values) in enumerate(zip(m, newKnots)):
+        if not (raise_by >= 0):
+            raise ValueError("Invalid m")
+        if raise_by + len(values) > 0:
+            touched.append(iv)
+    if not touched:
+        return self
+    base = clamp(self, touched, [], _path)               # the knot rule and the operator assume a clamped left end
+    clamp_paths = list(LAST_PATHS)
+    order, knots, steps = list(base.order), list(base.knots), []
+    for iv in touched:
+        k, raise_by = base.order[iv], int(m[iv])
+        knots[iv] = elevated_knots(base.knots[iv], k, raise_by, newKnots[iv])
+        order[iv] = k + raise_by
+        steps.append((iv + 1, *refine_map(base.knots[iv], k, knots[iv], raise_by)))
+    coefs = _run(base.coefs, steps, _path)
+    LAST_PATHS[:0] = clamp_paths
+    return _rebuild(base, order, knots, coefs)
+
+
+def elevate(self, m, _path=None):
+    return elevate_and_insert_knots(self, m, self.nInd * [[]], _path)
+
+
+def differentiate(self, with_respect_to=0, _path=None):
+    del LAST_PATHS[:]
+    if not (0 <= with_respect_to < self.nInd) or not (self.order[with_respect_to] > 1):
+        raise ValueError("Invalid with_respect_to")
+    iv = with_respect_to
+    first, w = differentiate_map(self.knots[iv], self.order[iv])
+    if not np.all(np.isfinite(w)):
+        raise ValueError("differentiate: an interior knot of full multiplicity (a discontinuous spline) has no derivative "
+                         "spline here; the reference returns inf / nan coefficients")
+    order, knots = list(self.order), list(self.knots)
+    order[iv] -= 1
+    knots[iv] = self.knots[iv][1:-1]
+    return _rebuild(self, order, knots, _run(self.coefs, [(iv + 1, first, w)], _path))

@@ -12,6 +12,9 @@ error messages for
     s.integral(integrand=None, domain=None)                       spline.py:1249 (nInd 1 - 3)
     Spline.bspline_values(knot, knots, splineOrder, u, ...)       spline.py:207-252
     Spline.least_squares(uValues, dataPoints, order, knots, ...)  spline.py:1402 (gridded data; not Spline-valued data)
+    s.insert_knots(newKnots) / s.trim(newDomain) / s.clamp(l, r)  spline.py:1219, :2386, :282
+    s.elevate(m) / s.elevate_and_insert_knots(m, newKnots)        spline.py:845-902
+    s.differentiate(with_respect_to=0)                            spline.py:772
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
@@ -26,6 +29,8 @@ Documented deviations from the reference:
   * of the ufunc keyword arguments of the reference's np.frompyfunc wrapper, where= and out= are
     honoured (out= also takes float arrays); the others (casting=, order=, ...) raise TypeError;
   * mixed float32/float64 inputs are computed in float64;
+  * differentiate() of a spline with an interior knot of full multiplicity raises ValueError (the reference
+    divides by the zero knot gap and returns inf / nan coefficients);
   * CUDA/HIP torch tensors are accepted as parameters (results stay on the GPU) and
     jacobian() accepts arrays of points (the reference's is single-point).
 """
@@ -233,6 +238,44 @@ class Spline:
         NotImplementedError.  ``_path="device"`` / ``"host"`` pins the path (tests, measurements)."""
         from . import fitting as _fitting
         return _fitting.least_squares(uValues, dataPoints, order, knots, compression, tolerance, fixEnds, metadata, **kwargs)
+
+    # ------------------------------------------------------------------ spline to spline (bspy_amd/refinement.py)
+    def insert_knots(self, newKnots, **kwargs):
+        """Insert knots: newKnots holds per independent variable an iterable of knots or (knot, multiplicity) pairs
+        (reference spline.py:1219, its checks and ValueError messages).  Returns a Spline of the same function on the
+        refined knots, coefficients in this spline's dtype.  Per variable the insertion is one banded operator built
+        on the host and applied to all lines of the coefficients by a GPU kernel (small tensors: on the host);
+        ``_path="device"`` / ``"host"`` pins the path."""
+        from . import refinement as _refinement
+        return _refinement.insert_knots(self, newKnots, **kwargs)
+
+    def elevate(self, m, **kwargs):
+        """Raise the order of variable i by m[i] (reference spline.py:845)."""
+        from . import refinement as _refinement
+        return _refinement.elevate(self, m, **kwargs)
+
+    def elevate_and_insert_knots(self, m, newKnots, **kwargs):
+        """Raise the order by m and insert the knots newKnots (plain values) in one step (reference spline.py:872);
+        returns self when there is nothing to do.  The spline is clamped on the left first; the resulting knots follow
+        the reference's rule.  The operator is built by blossoming, not by differentiating and integrating back."""
+        from . import refinement as _refinement
+        return _refinement.elevate_and_insert_knots(self, m, newKnots, **kwargs)
+
+    def trim(self, newDomain, **kwargs):
+        """Restrict the spline to newDomain (nInd x 2; None / nan keeps a bound; reference spline.py:2386): full
+        multiplicity knots at the bounds, which snap to a knot within eps.  Returns self when nothing changes."""
+        from . import refinement as _refinement
+        return _refinement.trim(self, newDomain, **kwargs)
+
+    def clamp(self, left, right, **kwargs):
+        """Full multiplicity at the domain's left / right end of the listed variables (reference spline.py:282)."""
+        from . import refinement as _refinement
+        return _refinement.clamp(self, left, right, **kwargs)
+
+    def differentiate(self, with_respect_to=0, **kwargs):
+        """The spline of the derivative with respect to one variable (reference spline.py:772)."""
+        from . import refinement as _refinement
+        return _refinement.differentiate(self, with_respect_to, **kwargs)
 
     def tangent_space(self, uvw):
         """Same as jacobian (reference spline.py:2238-2252)."""

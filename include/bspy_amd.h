@@ -213,6 +213,33 @@ bsk_status bsk_fit_residual(bsk_fit p, bsk_dtype dtype, const void *b, const dou
 const char *bsk_fit_last_kernel(bsk_fit p);
 
 /*
+ * Banded linear operators on coefficient tensors (Spline.insert_knots, elevate, elevate_and_insert_knots, trim, clamp,
+ * differentiate; bspy_amd/refinement.py).
+ * Replaces: the per-knot numpy.insert loop of insert_knots (bspy/_spline_domain.py:341), the derivative-and-integrate
+ * elevation (:110), the slicing of trim (:610) and the coefficient loop of differentiate (bspy/_spline_operations.py:244).
+ * A bsk_band handle holds one operator of one independent variable:
+ *   out[j] = sum over t < K of w[j * K + t] * in[first[j] + t],   j < nOut
+ *   first[j] : non-decreasing, 0 <= first[j] <= nIn - K
+ * bsk_band_create copies first and w and makes no HIP call.  The data of a call is viewed as in[outer][nIn][inner]
+ * (dtype BSK_F32 or BSK_F64); the result is out[outer][nOut][inner] in the same type.  The products of a row are added
+ * in fp64 in the order t = 0 .. K - 1 and rounded once; there are no atomics, results are bitwise reproducible.
+ *   bsk_band_apply_host : host buffers, the operator applied on the CPU (small tensors; also the statement of what the
+ *                         kernels compute).  Any K up to BSK_MAX_ORDER.
+ *   bsk_band_apply      : device buffers on the current device, one kernel enqueued on `stream`: band_apply (inner > 1,
+ *                         lanes along inner) or band_apply_line (inner == 1, lines staged through LDS).  in and out must
+ *                         not overlap.  K outside [2, 8] returns BSK_ERR_UNSUPPORTED.  The operator's tables are
+ *                         uploaded by the first device call.
+ *   bsk_band_last_kernel: "band_apply", "band_apply_line" or "host band": the path of the most recent call on this map.
+ * A map is used from one thread and one stream at a time.
+ */
+typedef struct bsk_band_s *bsk_band;
+bsk_status bsk_band_create(int nIn, int nOut, int K, const int32_t *first, const double *w, bsk_band *out);
+bsk_status bsk_band_destroy(bsk_band p);
+bsk_status bsk_band_apply_host(bsk_band p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, void *out);
+bsk_status bsk_band_apply(bsk_band p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, void *out, void *stream);
+const char *bsk_band_last_kernel(bsk_band p);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
