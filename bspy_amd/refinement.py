@@ -90,6 +90,45 @@ class BandMap:
 
 
 # ------------------------------------------------------------------------------------------ operators
+def support_cell(newKnots, j, n):
+    """For the rows j of an operator onto ``newKnots`` whose blossoms take n arguments: the non-empty new cell nearest
+    the middle of the support newKnots[j .. j + n + 1] (the lower one of two equally near)."""
+    tb = newKnots
+    cell = np.full(len(j), -1)
+    for off in sorted(range(n + 1), key=lambda o: (abs(o - 0.5 * n), o)):
+        c = j + off
+        take = (cell < 0) & (tb[c + 1] > tb[c])
+        cell[take] = c[take]
+    cell[cell < 0] = (j + n // 2)[cell < 0]
+    return cell
+
+
+def knot_cell(knots, order, x):
+    """The cell mu of ``knots`` (float64) that holds x, clipped to the domain's cells order - 1 .. nCoef - 1."""
+    t, k = knots, order
+    nIn = len(t) - k
+    hi = t[nIn]
+    mu = np.searchsorted(t, x, "right") - 1
+    mu[x >= hi] = np.searchsorted(t, hi, "left") - 1
+    return np.clip(mu, k - 1, nIn - 1)
+
+
+def blossom_weights(knots, order, first, args):
+    """Multi-affine de Boor recurrence: the weights (rows, k) on the coefficients first .. first + k - 1 of the blossom of
+    the polynomial piece on cell first + k - 1 at the k - 1 arguments args[row].  ``knots`` and ``args`` (rows, k - 1)
+    come in the precision the recurrence is to run in."""
+    t, k = knots, order
+    D = np.broadcast_to(np.eye(k, dtype=t.dtype), (len(first), k, k)).copy()              # D[row, p] = weights of d_p on the k old coefficients
+    for r in range(1, k):
+        u = args[:, r - 1]
+        for q in range(k - 1, r - 1, -1):
+            i = first + q
+            left, right = t[i], t[i + k - r]
+            den = right - left
+            D[:, q] = ((right - u) / den)[:, None] * D[:, q - 1] + ((u - left) / den)[:, None] * D[:, q]
+    return D[:, k - 1]
+
+
 def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     """BandMap arrays (first, w) that take the coefficients on ``knots`` (order k) to those of the same function on
     ``newKnots`` (order k + m), for the output rows ``rows`` (a slice; default all).  ``newKnots`` must hold every
@@ -104,19 +143,10 @@ def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     n = k + m - 1                                   # arguments of the elevated blossom
     nIn, nOut = len(t) - k, len(tb) - k - m
     j = np.arange(nOut)[rows if rows is not None else slice(None)]
-    # the non-empty new cell nearest the middle of the support (the lower one of two equally near)
-    cell = np.full(len(j), -1)
-    for off in sorted(range(n + 1), key=lambda o: (abs(o - 0.5 * n), o)):
-        c = j + off
-        take = (cell < 0) & (tb[c + 1] > tb[c])
-        cell[take] = c[take]
-    cell[cell < 0] = (j + n // 2)[cell < 0]
+    cell = support_cell(tb, j, n)
     lo, hi = t[k - 1], t[nIn]
     x = np.clip(0.5 * (tb[cell] + tb[cell + 1]), lo, hi)
-    mu = np.searchsorted(t, x, "right") - 1
-    mu[x >= hi] = np.searchsorted(t, hi, "left") - 1
-    mu = np.clip(mu, k - 1, nIn - 1)
-    first = mu - k + 1
+    first = knot_cell(t, k, x) - k + 1
 
     # the recurrence runs in extended precision where the platform has it (x86: 64-bit mantissa), so that the
     # weights are correctly rounded doubles but for rare ties; elsewhere it runs in double
@@ -124,15 +154,7 @@ def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     w = np.zeros((len(j), k), np.longdouble)
     subsets = list(itertools.combinations(range(n), k - 1))
     for subset in subsets:
-        D = np.broadcast_to(np.eye(k, dtype=np.longdouble), (len(j), k, k)).copy()        # D[row, p] = weights of d_p on the k old coefficients
-        for r, a in enumerate(subset, start=1):
-            u = tb[j + 1 + a]
-            for q in range(k - 1, r - 1, -1):
-                i = first + q
-                left, right = t[i], t[i + k - r]
-                den = right - left
-                D[:, q] = ((right - u) / den)[:, None] * D[:, q - 1] + ((u - left) / den)[:, None] * D[:, q]
-        w += D[:, k - 1]
+        w += blossom_weights(t, k, first, tb[j[:, None] + 1 + np.array(subset, np.int64)])
     w = (w / len(subsets)).astype(np.float64)
     if m == 0 and origin is not None and k > 1:
         # the blossom's arguments are k - 1 consecutive old knots: the value is the old coefficient in front of them

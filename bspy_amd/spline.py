@@ -15,6 +15,8 @@ error messages for
     s.insert_knots(newKnots) / s.trim(newDomain) / s.clamp(l, r)  spline.py:1219, :2386, :282
     s.elevate(m) / s.elevate_and_insert_knots(m, newKnots)        spline.py:845-902
     s.differentiate(with_respect_to=0)                            spline.py:772
+    s.multiply(other, indMap, productType) / dot / cross / scale  spline.py:1585, :821, :641, :2028
+    s.transform(matrix), s * x, x * s, s @ x, x @ s, -s, s / x    spline.py:2307, :97-147
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
@@ -276,6 +278,71 @@ class Spline:
         """The spline of the derivative with respect to one variable (reference spline.py:772)."""
         from . import refinement as _refinement
         return _refinement.differentiate(self, with_respect_to, **kwargs)
+
+    # ------------------------------------------------------------------ products (bspy_amd/product.py)
+    def multiply(self, other, indMap=None, productType='S', **kwargs):
+        """Product of two splines (reference spline.py:1585, its checks and ValueError messages).  indMap: indices n (variable
+        n of self is variable n of other) or pairs (n, m); mapped variables must have the same domain, the others stay
+        independent: the result has self's variables, the mapped ones in place, then other's unmapped ones.  productType
+        'S' scalar product (nDep equal, or 1 on one side), 'D' dot product, 'C' cross product (nDep 2 or 3).  A mapped
+        variable of orders k1 and k2 has order k1 + k2 - 1 and the reference's knots; the coefficients come from one
+        banded bilinear operator per mapped variable, applied by one GPU kernel (small results, three mapped variables
+        and orders outside 2 .. 6: on the host); more than three mapped variables raise NotImplementedError.
+        ``_path="device"`` / ``"host"`` pins the path."""
+        from . import product as _product
+        return _product.multiply(self, other, indMap, productType, **kwargs)
+
+    def dot(self, vector, **kwargs):
+        """Dot product with a vector or, over the common variables, with a Spline (reference spline.py:821)."""
+        from . import product as _product
+        return _product.dot(self, vector, **kwargs)
+
+    def cross(self, vector, **kwargs):
+        """Cross product with a vector or, over the common variables, with a Spline (reference spline.py:641)."""
+        from . import product as _product
+        return _product.cross(self, vector, **kwargs)
+
+    def scale(self, multiplier, **kwargs):
+        """Scale by a scalar, by a vector (per component; nDep == 1 broadcasts) or by a Spline (reference spline.py:2028)."""
+        from . import product as _product
+        return _product.scale(self, multiplier, **kwargs)
+
+    def transform(self, matrix):
+        """Apply a matrix (rows x nDep) to the dependent variables (reference spline.py:2307)."""
+        from . import product as _product
+        return _product.transform(self, matrix)
+
+    def _common(self, other):
+        return [(ix, ix) for ix in range(min(self.nInd, other.nInd))]
+
+    def __matmul__(self, other):
+        if isinstance(other, Spline):
+            return self.multiply(other, self._common(other), 'D')
+        other = np.atleast_1d(other)
+        return self.transform(other.T) if other.ndim > 1 else self.dot(other)
+
+    def __rmatmul__(self, other):
+        if isinstance(other, Spline):
+            return other.multiply(self, self._common(other), 'D')
+        other = np.atleast_1d(other)
+        return self.transform(other) if other.ndim > 1 else self.dot(other)
+
+    def __mul__(self, other):
+        return self.multiply(other, self._common(other), 'S') if isinstance(other, Spline) else self.scale(other)
+
+    def __rmul__(self, other):
+        return other.multiply(self, self._common(other), 'S') if isinstance(other, Spline) else self.scale(other)
+
+    def __neg__(self):
+        return self.scale(-1.0)
+
+    def __truediv__(self, other):
+        if not np.isscalar(other):
+            raise ValueError('Divisor must be a scalar')
+        return self * (1.0 / other)
+
+    # NumPy must hand `array @ spline` and `array * spline` to the methods above instead of broadcasting over the spline
+    __array_ufunc__ = None
 
     def tangent_space(self, uvw):
         """Same as jacobian (reference spline.py:2238-2252)."""

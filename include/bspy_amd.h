@@ -240,6 +240,43 @@ bsk_status bsk_band_apply(bsk_band p, bsk_dtype dtype, const void *in, int64_t o
 const char *bsk_band_last_kernel(bsk_band p);
 
 /*
+ * Products of splines (Spline.multiply, dot, cross, scale by a spline, the * and @ operators; bspy_amd/product.py).
+ * Replaces: multiplyAndConvolve's outer product over all variables followed by per-segment Taylor expansions
+ * (bspy/_spline_operations.py:318).
+ * A bsk_product handle holds, for each of M mapped pairs of variables (variable v: order k1[v], nIn1[v] coefficients
+ * of the first spline; order k2[v], nIn2[v] coefficients of the second), one banded bilinear operator
+ *   c[j] = sum over a < k1, b < k2 of W[(j * k1 + a) * k2 + b] * A[f[j] + a] * B[g[j] + b],   j < nOut[v]
+ *   f, g : non-decreasing, 0 <= f[j] <= nIn1 - k1, 0 <= g[j] <= nIn2 - k2
+ * The operator of several mapped variables is the tensor product of these.  bsk_product_create copies the tables and
+ * makes no HIP call.
+ * Data of a call (dtype BSK_F32 or BSK_F64, mapped variables last, contiguous):
+ *   a[PA][nIn1[0]]..[nIn1[M-1]],  b[PB][nIn2[0]]..[nIn2[M-1]]  ->  out[P][nOut[0]]..[nOut[M-1]]
+ *   terms : host array int32 [P][T][3]: output plane p is the sum over its T terms (planeA, planeB, sign = +1 / -1) of
+ *           sign * product(a[planeA], b[planeB]).  The table carries the dependent-variable rule (scalar, dot, cross)
+ *           and the unmapped variables of both splines.
+ * Arithmetic: data widened to fp64, fp64 weights and accumulation, rounded once to dtype.  Per term and output the sums
+ * run over the first mapped variable outermost, a before b; in the last variable V[b] = sum_a A[a] W[a][b] is formed
+ * first and then sum_b V[b] B[b].  Terms are added in table order.  No atomics; results are bitwise reproducible.
+ *   bsk_product_apply_host : host buffers, the sums above in plain C++, M = 1 .. 3, any order up to BSK_MAX_ORDER.
+ *   bsk_product_apply      : device buffers on the current device, one kernel enqueued on `stream`:
+ *                            band_product_line (M = 1) or band_product_tile (M = 2).  `terms` is a host array.  Orders of
+ *                            the mapped variables outside [2, 6] or M > 2 return BSK_ERR_UNSUPPORTED.  out must not
+ *                            overlap a or b.
+ *   bsk_product_last_kernel: "band_product_line", "band_product_tile" or "host product".
+ * A handle is used from one thread and one stream at a time.
+ */
+typedef struct bsk_product_s *bsk_product;
+bsk_status bsk_product_create(int M, const int32_t *nIn1, const int32_t *nIn2, const int32_t *nOut, const int32_t *k1,
+                              const int32_t *k2, const int32_t *const *f, const int32_t *const *g, const double *const *W,
+                              bsk_product *out);
+bsk_status bsk_product_destroy(bsk_product p);
+bsk_status bsk_product_apply_host(bsk_product p, bsk_dtype dtype, const void *a, int64_t PA, const void *b, int64_t PB,
+                                  const int32_t *terms, int64_t P, int T, void *out);
+bsk_status bsk_product_apply(bsk_product p, bsk_dtype dtype, const void *a, int64_t PA, const void *b, int64_t PB,
+                             const int32_t *terms, int64_t P, int T, void *out, void *stream);
+const char *bsk_product_last_kernel(bsk_product p);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
