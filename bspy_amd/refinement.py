@@ -18,6 +18,10 @@ arguments of the piece's own blossom, which the multi-affine de Boor recurrence 
 coefficients mu - k + 1 .. mu.  No derivative is taken and nothing is integrated back, so the operator's error is a
 few ulp whatever the knot spacing.
 
+``trim_plan``, ``clamp_box`` and ``elevate_plan`` are the knot logic of trim, clamp and elevate_and_insert_knots without the
+coefficients (they return the band steps); ``run_device`` applies steps to a CUDA tensor and returns one: bspy_amd/sums.py
+plans ``common_basis`` with them and keeps the intermediates of ``add`` on the device.
+
 ``_path="device" | "host"`` (or ``refinement.FORCE_PATH``) pins the path; ``refinement.LAST_PATHS`` lists what every
 variable of the last call ran ("band_apply", "band_apply_line", "host band").
 """
@@ -217,6 +221,32 @@ def _apply(band, tensor, axis):
     return band.apply_device(tensor.contiguous(), outer, inner).reshape(shape)
 
 
+def _ordered(steps, shape):
+    """The step that shrinks the tensor most first, the one that grows it most last (the operators of different
+    variables commute)."""
+    return sorted(steps, key=lambda s: len(s[1]) / shape[s[0]])
+
+
+def steps_covered(steps):
+    """Whether the band kernels cover every step (K of the device instantiations)."""
+    return all(DEVICE_MIN_K <= np.shape(w)[1] <= DEVICE_MAX_K for _, _, w in steps)
+
+
+def run_device(data, steps):
+    """data: torch CUDA tensor (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step with the band kernels and
+    returns the CUDA tensor: the intermediates of a pipeline stay on the device.  Returns (tensor, kernels that ran)."""
+    ran = []
+    for axis, first, w in _ordered(steps, data.shape):
+        band = BandMap(first, w, data.shape[axis])
+        try:
+            data = _apply(band, data, axis)
+            if data.numel():
+                ran.append(band.last_kernel())
+        finally:
+            band.close()
+    return data, ran
+
+
 def _run(coefs, steps, path):
     """coefs: NumPy (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step, the one that shrinks the tensor most
     first and the one that grows it most last (the operators of different variables commute), and returns NumPy."""
@@ -226,7 +256,7 @@ def _run(coefs, steps, path):
     del LAST_PATHS[:]
     if not steps:
         return coefs
-    steps = sorted(steps, key=lambda s: len(s[1]) / coefs.shape[s[0]])
+    steps = _ordered(steps, coefs.shape)
     bands = [(axis, BandMap(first, w, coefs.shape[axis])) for axis, first, w in steps]
     try:
         if coefs.size == 0:
@@ -322,20 +352,18 @@ def _bound_plan(knots, order, value, eps, right):
     return value, order
 
 
-def trim(self, newDomain, _path=None):
-    del LAST_PATHS[:]                        # also when the spline itself is returned: nothing ran
-    if len(newDomain) != self.nInd:
-        raise ValueError("Invalid newDomain")
-    if self.nInd < 1:
-        return self
-    box = np.array(newDomain, self.knots[0].dtype, copy=True)            # None becomes nan: that side is kept
+def trim_plan(order, knots, newDomain):
+    """What ``trim`` does to a spline with these orders and knots, without its coefficients: None when the spline itself
+    comes back, else (knots of the result, band steps [(axis, first, w)])."""
+    nInd = len(order)
+    box = np.array(newDomain, knots[0].dtype, copy=True)            # None becomes nan: that side is kept
     eps = np.finfo(box.dtype).eps
 
     entries, changed = [], False
     for iv, bounds in enumerate(box):
         if len(bounds) != 2:
             raise ValueError("Invalid newDomain")
-        t, k = self.knots[iv], self.order[iv]
+        t, k = knots[iv], order[iv]
         ends = (t[k - 1], t[len(t) - k])
         wanted = []
         for side in (0, 1):
@@ -351,28 +379,46 @@ def trim(self, newDomain, _path=None):
             changed = changed or missing > 0 or bounds[side] != ends[side]
         entries.append(wanted)
     if not changed:
-        return self
+        return None
 
     # one operator per variable: the insertion at the bounds, restricted to the rows between them
-    knots, steps = [], []
+    out, steps = [], []
     for iv, (wanted, (lower, upper)) in enumerate(zip(entries, box)):
-        t, k = self.knots[iv], self.order[iv]
+        t, k = knots[iv], order[iv]
         merged, origin = merged_knots(t, k, wanted)
         row0 = 0 if np.isnan(lower) else int(np.searchsorted(merged, lower))
         row1 = len(merged) - k if np.isnan(upper) else int(np.searchsorted(merged, upper))
-        knots.append(merged[row0:row1 + k])
+        out.append(merged[row0:row1 + k])
         if merged is not t or (row0, row1) != (0, len(t) - k):
             steps.append((iv + 1, *refine_map(t, k, merged, 0, rows=slice(row0, row1), origin=origin)))
+    assert len(out) == nInd
+    return out, steps
+
+
+def trim(self, newDomain, _path=None):
+    del LAST_PATHS[:]                        # also when the spline itself is returned: nothing ran
+    if len(newDomain) != self.nInd:
+        raise ValueError("Invalid newDomain")
+    if self.nInd < 1:
+        return self
+    plan = trim_plan(self.order, self.knots, newDomain)
+    if plan is None:
+        return self
+    knots, steps = plan
     return _rebuild(self, self.order, knots, _run(self.coefs, steps, _path))
+
+
+def clamp_box(order, knots, left, right):
+    """The trim box of ``clamp``: the spline's own domain on the listed sides, None elsewhere."""
+    variables = range(len(order))
+    left, right = {variables[i] for i in left}, {variables[i] for i in right}
+    ends = [(t[k - 1], t[len(t) - k]) for t, k in zip(knots, order)]
+    return [[lo if iv in left else None, hi if iv in right else None] for iv, (lo, hi) in enumerate(ends)]
 
 
 def clamp(self, left, right, _path=None):
     """A trim to the spline's own domain on the listed sides."""
-    variables = range(self.nInd)
-    left, right = {variables[i] for i in left}, {variables[i] for i in right}
-    ends = [(t[k - 1], t[n]) for t, k, n in zip(self.knots, self.order, self.nCoef)]
-    box = [[lo if iv in left else None, hi if iv in right else None] for iv, (lo, hi) in enumerate(ends)]
-    return trim(self, box, _path)
+    return trim(self, clamp_box(self.order, self.knots, left, right), _path)
 
 
 def elevated_knots(knots, order, m, newKnots):
@@ -386,11 +432,14 @@ def elevated_knots(knots, order, m, newKnots):
     return np.repeat(values, count)
 
 
-def elevate_and_insert_knots(self, m, newKnots, _path=None):
-    del LAST_PATHS[:]
-    if len(m) != self.nInd:
+def elevate_plan(order, knots, m, newKnots):
+    """What ``elevate_and_insert_knots`` does to a spline with these orders and knots, without its coefficients: None when
+    the spline itself comes back, else (orders, knots of the result, band steps of the left clamp, band steps of the
+    elevation and insertion)."""
+    nInd = len(order)
+    if len(m) != nInd:
         raise ValueError("Invalid m")
-    if len(newKnots) != self.nInd:
+    if len(newKnots) != nInd:
         raise ValueError("Invalid newKnots")
     touched = []
     for iv, (raise_by, values) in enumerate(zip(m, newKnots)):
@@ -399,18 +448,30 @@ def elevate_and_insert_knots(self, m, newKnots, _path=None):
         if raise_by + len(values) > 0:
             touched.append(iv)
     if not touched:
-        return self
-    base = clamp(self, touched, [], _path)               # the knot rule and the operator assume a clamped left end
-    clamp_paths = list(LAST_PATHS)
-    order, knots, steps = list(base.order), list(base.knots), []
+        return None
+    # the knot rule and the operator assume a clamped left end
+    clamped = trim_plan(order, knots, clamp_box(order, knots, touched, []))
+    base, clamp_steps = clamped if clamped is not None else (knots, [])
+    order, knots, steps = list(order), list(base), []
     for iv in touched:
-        k, raise_by = base.order[iv], int(m[iv])
-        knots[iv] = elevated_knots(base.knots[iv], k, raise_by, newKnots[iv])
+        k, raise_by = order[iv], int(m[iv])
+        knots[iv] = elevated_knots(base[iv], k, raise_by, newKnots[iv])
         order[iv] = k + raise_by
-        steps.append((iv + 1, *refine_map(base.knots[iv], k, knots[iv], raise_by)))
-    coefs = _run(base.coefs, steps, _path)
+        steps.append((iv + 1, *refine_map(base[iv], k, knots[iv], raise_by)))
+    return order, knots, clamp_steps, steps
+
+
+def elevate_and_insert_knots(self, m, newKnots, _path=None):
+    del LAST_PATHS[:]
+    plan = elevate_plan(self.order, self.knots, m, newKnots)
+    if plan is None:
+        return self
+    order, knots, clamp_steps, steps = plan
+    base = _run(self.coefs, clamp_steps, _path)
+    clamp_paths = list(LAST_PATHS)
+    coefs = _run(base, steps, _path)
     LAST_PATHS[:0] = clamp_paths
-    return _rebuild(base, order, knots, coefs)
+    return _rebuild(self, order, knots, coefs)
 
 
 def elevate(self, m, _path=None):

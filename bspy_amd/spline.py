@@ -17,6 +17,9 @@ error messages for
     s.differentiate(with_respect_to=0)                            spline.py:772
     s.multiply(other, indMap, productType) / dot / cross / scale  spline.py:1585, :821, :641, :2028
     s.transform(matrix), s * x, x * s, s @ x, x @ s, -s, s / x    spline.py:2307, :97-147
+    Spline.common_basis(splines, indMap) / s.add / s.subtract     spline.py:308, :149, :2199
+    s.translate(vector), s + x, x + s, s - x, x - s               spline.py:2335, :85-95, :132-143
+    s.integrate(with_respect_to=0) / s.contract(uvw)              spline.py:1290, :567
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
@@ -340,6 +343,64 @@ class Spline:
         if not np.isscalar(other):
             raise ValueError('Divisor must be a scalar')
         return self * (1.0 / other)
+
+    # ------------------------------------------------------------------ sums (bspy_amd/sums.py)
+    @staticmethod
+    def common_basis(splines, indMap=None, **kwargs):
+        """Align splines to one basis (reference spline.py:308): every spline is clamped in all its variables; per entry
+        (i0, .., iN) of indMap the variables take the largest order and the merged knots (multiplicities raised with the
+        order), by one elevate_and_insert_knots per spline.  indMap None aligns variable i of every spline.  A spline that
+        needs nothing comes back itself."""
+        from . import sums as _sums
+        return _sums.common_basis(splines, indMap, **kwargs)
+
+    def add(self, other, indMap=None, **kwargs):
+        """Sum of two splines of one nDep (reference spline.py:149).  indMap: indices n or pairs (n, m) of variables that
+        are the same variable; they are brought to a common basis first.  None: no variable in common (the outer sum,
+        nothing is clamped).  The result has self's variables, the mapped ones in place, then other's unmapped ones, and
+        self's metadata and coefficient dtype.  Large results: band kernels, then one broadcast-sum kernel, on the GPU.
+        ``_path="device"`` / ``"host"`` pins the path."""
+        from . import sums as _sums
+        return _sums.add(self, other, indMap, **kwargs)
+
+    def subtract(self, other, indMap=None, **kwargs):
+        """self - other (reference spline.py:2199): ``add`` with the sign of other's coefficients turned."""
+        from . import sums as _sums
+        return _sums.subtract(self, other, indMap, **kwargs)
+
+    def translate(self, translationVector):
+        """Add a vector to the dependent variables (reference spline.py:2335)."""
+        from . import sums as _sums
+        return _sums.translate(self, translationVector)
+
+    def integrate(self, with_respect_to=0, **kwargs):
+        """Antiderivative in one variable that vanishes at the left end of the domain (reference spline.py:1290): order and
+        coefficient count of that variable go up by one, both end knots are repeated once more, the coefficients are a
+        weighted running sum (large tensors: on the GPU).  ``_path="device"`` / ``"host"`` pins the path."""
+        from . import sums as _sums
+        return _sums.integrate(self, with_respect_to, **kwargs)
+
+    def contract(self, uvw, **kwargs):
+        """Fix the variables whose entry of uvw is not None at that value (reference spline.py:567); the others stay the
+        variables of the result, which may have none.  Returns self when nothing is fixed."""
+        from . import sums as _sums
+        return _sums.contract(self, uvw, **kwargs)
+
+    def __add__(self, other):
+        return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
+
+    def __radd__(self, other):
+        return other.add(self, self._common(other)) if isinstance(other, Spline) else self.translate(other)
+
+    def __sub__(self, other):
+        if isinstance(other, Spline):
+            return self.subtract(other, self._common(other))
+        return self.translate(-np.atleast_1d(other))
+
+    def __rsub__(self, other):
+        if isinstance(other, Spline):
+            return other.subtract(self, self._common(other))
+        return self.scale(-1.0).translate(other)
 
     # NumPy must hand `array @ spline` and `array * spline` to the methods above instead of broadcasting over the spline
     __array_ufunc__ = None

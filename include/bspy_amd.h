@@ -277,6 +277,51 @@ bsk_status bsk_product_apply(bsk_product p, bsk_dtype dtype, const void *a, int6
 const char *bsk_product_last_kernel(bsk_product p);
 
 /*
+ * Running sums and broadcast sums of coefficient tensors (Spline.integrate, add, subtract and the + and - operators;
+ * bspy_amd/sums.py).
+ * Replaces: the row-by-row coefficient loop of integrate (bspy/_spline_operations.py:290) and the zero-filled,
+ * transposed in-place additions of add (:14).
+ * A bsk_scan handle holds the weights g[0 .. n - 1] of one independent variable:
+ *   out[0] = 0,   out[j + 1] = sum over i <= j of g[i] * in[i],   j < n
+ * bsk_scan_create copies g and makes no HIP call.  The data of a call is viewed as in[outer][n][inner] (dtype BSK_F32
+ * or BSK_F64); the result is out[outer][n + 1][inner] in the same type.  The association is one, for every path and
+ * every launch geometry: each product g[i] * in[i] is rounded to fp64; rows are taken in chunks of 32; inside a chunk
+ * the products are added left to right from 0; the chunk totals are added left to right from 0 into the chunk's carry;
+ * an output is carry + the chunk's running sum, rounded once to dtype.  No atomics; results are bitwise reproducible
+ * and the host driver and the kernels give the same bits.
+ *   bsk_scan_apply_host : host buffers, the sums above in plain C++.
+ *   bsk_scan_apply      : device buffers on the current device, enqueued on `stream`: scan_apply (inner > 1, lanes
+ *                         along inner) or scan_line (inner == 1, tiles of lines staged through LDS).  A line is cut into
+ *                         `segments` pieces of whole chunks (0: the library chooses; the count is rounded to what whole
+ *                         chunks allow); more than one piece takes two launches: chunk totals into a workspace the
+ *                         handle owns, then every workgroup forms its carry from the totals in front of it.  No
+ *                         workgroup waits for another.  in and out must not overlap.
+ *   bsk_scan_last_kernel: "scan_apply", "scan_line" or "host scan": the path of the most recent call on this map.
+ * A map is used from one thread and one stream at a time.
+ *
+ * bsk_sum_apply(_host): out[idx] = a[idx . strideA] + sign * b[idx . strideB] over the contiguous result out of extents
+ * dim[0 .. rank - 1], 1 <= rank <= 8 (BSK_ERR_UNSUPPORTED above: merge adjacent axes first).  Strides are in elements and
+ * not negative; 0 broadcasts the operand along that axis.  sign is +1 or -1.  Both operands and the result have type
+ * dtype; the sum is formed in fp64 and rounded once.
+ *   bsk_sum_apply_host  : host buffers.
+ *   bsk_sum_apply       : device buffers on the current device, one kernel (sum_bcast) enqueued on `stream`; out must not
+ *                         overlap a or b.
+ *   bsk_sum_last_kernel : "sum_bcast" or "host sum": the most recent call of this thread.
+ */
+typedef struct bsk_scan_s *bsk_scan;
+bsk_status bsk_scan_create(int n, const double *g, bsk_scan *out);
+bsk_status bsk_scan_destroy(bsk_scan p);
+bsk_status bsk_scan_apply_host(bsk_scan p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, void *out);
+bsk_status bsk_scan_apply(bsk_scan p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, void *out, int segments,
+                          void *stream);
+const char *bsk_scan_last_kernel(bsk_scan p);
+bsk_status bsk_sum_apply_host(bsk_dtype dtype, int rank, const int64_t *dim, const void *a, const int64_t *strideA,
+                              const void *b, const int64_t *strideB, int sign, void *out);
+bsk_status bsk_sum_apply(bsk_dtype dtype, int rank, const int64_t *dim, const void *a, const int64_t *strideA, const void *b,
+                         const int64_t *strideB, int sign, void *out, void *stream);
+const char *bsk_sum_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
