@@ -34,6 +34,7 @@ PRODUCT_SYMBOLS = (
     "bsk_product_create", "bsk_product_destroy", "bsk_product_apply_host", "bsk_product_apply", "bsk_product_last_kernel",
     "bsk_scan_create", "bsk_scan_destroy", "bsk_scan_apply_host", "bsk_scan_apply", "bsk_scan_last_kernel",
     "bsk_sum_apply_host", "bsk_sum_apply", "bsk_sum_last_kernel",
+    "bsk_roots_extract_host", "bsk_roots_flag_host", "bsk_roots_flag", "bsk_roots_isolate_host", "bsk_roots_isolate", "bsk_roots_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -147,6 +148,15 @@ def lib():
     L.bsk_sum_apply.argtypes = [ctypes.c_int, ctypes.c_int, _i64p, _vp, _i64p, _vp, _i64p, ctypes.c_int, _vp, _vp]
     L.bsk_sum_last_kernel.argtypes = []
     L.bsk_sum_last_kernel.restype = ctypes.c_char_p
+    L.bsk_roots_extract_host.argtypes = [ctypes.c_int, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+    L.bsk_roots_flag_host.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
+    L.bsk_roots_flag.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
+    L.bsk_roots_isolate_host.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double,
+                                         _vp, _i64, _vp, _vp]
+    L.bsk_roots_isolate.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp,
+                                    _i64, _vp, _vp, _vp]
+    L.bsk_roots_last_kernel.argtypes = []
+    L.bsk_roots_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -155,7 +165,7 @@ def lib():
     L.bsk_debug_fill_lds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _i64p, _vp]
     for name in SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
-                        "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel"):
+                        "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

@@ -20,11 +20,12 @@ error messages for
     Spline.common_basis(splines, indMap) / s.add / s.subtract     spline.py:308, :149, :2199
     s.translate(vector), s + x, x + s, s - x, x - s               spline.py:2335, :85-95, :132-143
     s.integrate(with_respect_to=0) / s.contract(uvw)              spline.py:1290, :567
+    s.zeros() (curves: nInd == nDep == 1)                         spline.py:2470
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
-rest of the reference's Spline API (the other fitting calls - fit, contour, solve_ode, ... -, intersection, CSG,
-viewer) is out of scope.
+rest of the reference's Spline API (the other fitting calls - fit, contour, solve_ode, ... -, zeros for nInd > 1,
+intersect, contours, CSG, viewer) is out of scope.
 
 Documented deviations from the reference:
   * all-integer knots / coefs are promoted to float64 (the reference keeps int64 and
@@ -385,6 +386,21 @@ class Spline:
         variables of the result, which may have none.  Returns self when nothing is fixed."""
         from . import sums as _sums
         return _sums.contract(self, uvw, **kwargs)
+
+    # ------------------------------------------------------------------ roots (bspy_amd/roots.py)
+    def zeros(self, epsilon=None, initialScale=None, **kwargs):
+        """The real roots of a scalar curve (nInd == nDep == 1; reference spline.py:2470): a list, ascending, of scalars of
+        the knots' dtype for isolated roots and of (left, right) tuples for intervals on which the spline is zero.
+        ``epsilon`` and ``initialScale`` are accepted and ignored, as the reference's curve path ignores them.  Every knot
+        span is brought to Bernstein form by one band operator; spans whose coefficients show no sign change are rejected
+        by one kernel, the others are isolated by subdivision, one lane per span, and refined by bisection to adjacent
+        doubles (few spans and orders above 8: the same arithmetic on the host).  What counts as a root (zero spans,
+        roots at knots, touching roots, jumps) is stated in bspy_amd/roots.py.  Results are bitwise reproducible and the
+        same on both paths.  nInd != nDep raises the reference's ValueError; nInd == nDep > 1 raises NotImplementedError
+        (deliberate scope).  ``_path="device"`` / ``"host"`` pins the path.  ``bspy_amd.roots.zeros_batch`` does the same
+        for every component of a curve with any nDep."""
+        from . import roots as _roots
+        return _roots.zeros(self, epsilon, initialScale, **kwargs)
 
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)

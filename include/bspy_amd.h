@@ -322,6 +322,55 @@ bsk_status bsk_sum_apply(bsk_dtype dtype, int rank, const int64_t *dim, const vo
 const char *bsk_sum_last_kernel(void);
 
 /*
+ * Real roots of scalar spline curves (Spline.zeros, bspy_amd.roots.zeros_batch; bspy_amd/roots.py).
+ * Replaces: the recursive interval Newton iteration of bspy/_spline_intersection.py:12, which trims and reparametrizes
+ * a spline object per step.
+ * The caller brings every component to Bezier form first (one bsk_band_apply): rows[ncomp][rowlen] (dtype BSK_F32 or
+ * BSK_F64) holds, for span s of the nspans knot spans, the `order` Bernstein coefficients of the piece on
+ * [breaks[s], breaks[s + 1]] at rows[d][first[s] .. first[s] + order - 1].  mask[ncomp][nspans] (bytes): bit 0 the span
+ * is skipped (it lies in a run of zero spans), bit 1 / bit 2 the span to the left / right is a zero span (a root within
+ * `margin` of that end is dropped), bit 3 the last span (it owns the right end of the domain).
+ * Arithmetic: fp64 whatever dtype, every product and sum rounded on its own; de Casteljau steps are
+ * (1 - t) * a + t * b.  No atomics, no waiting between lanes; every loop has a compile-time bound.  Results are bitwise
+ * reproducible and the host drivers and the kernels give the same bits.
+ *   bsk_roots_flag(_host)   : flags[ncomp][nspans] (bytes) = the sign variations of the span's coefficients, zeros
+ *                             skipped, + 1 for a first coefficient that is exactly 0, + 1 for a last coefficient that is
+ *                             exactly 0 in the last span; 0 for a skipped span.  Device: one kernel (roots_flag), no LDS.
+ *   bsk_roots_isolate(_host): cand[ncand] (int64, flat indices d * nspans + s of the spans to work on, ncand >= 1: no
+ *                             candidates means no call); scale[ncomp] = max |coefficient| of the component.  Per
+ *                             candidate the roots inside the span, ascending, go to roots[ncand][order - 1] (doubles, NaN
+ *                             behind the last one) and their number to count[ncand] (int32): sub-intervals are halved
+ *                             (at most 50 times) while their control polygon has two or more sign variations; one
+ *                             variation is a bracket, refined by at most 60 bisection steps on the span's own
+ *                             coefficients; two or more at the depth limit is a touching root, reported at the
+ *                             midpoint when |f| <= 4 order eps scale there.  A root x in [0, 1] is returned as
+ *                             breaks[s] + x * (breaks[s + 1] - breaks[s]).  Device: one kernel (roots_isolate), one lane
+ *                             per candidate, registers only.
+ *   The device entry points take device buffers on the current device (first, mask, breaks, scale, cand included) and
+ *   enqueue on `stream`; orders 2 .. 8 (BSK_ERR_UNSUPPORTED above; the host drivers take orders up to BSK_MAX_ORDER).
+ *   bsk_roots_extract_host  : the Bezier extraction of the host path: out[ncomp][nOut] from in[ncomp][nIn] (doubles) by the
+ *                             band operator out[j] = sum_t w[j][t] * in[first[j] + t], t < K, formed as the chain
+ *                             acc = fma(w[j][t], in[first[j] + t], acc) from 0 in the order of t.  This is what the band
+ *                             kernels compute on the device (their sums are fused); bsk_band_apply_host rounds every
+ *                             product, so its rows differ from theirs in the last bit and the roots would too.
+ *   bsk_roots_last_kernel   : "roots_flag", "roots_isolate", "host roots_extract", "host roots_flag" or
+ *                             "host roots_isolate": the most recent call of this thread.
+ */
+bsk_status bsk_roots_extract_host(int K, int64_t nIn, int64_t nOut, const int32_t *first, const double *w, const double *in,
+                                  int64_t ncomp, double *out);
+bsk_status bsk_roots_flag_host(bsk_dtype dtype, int order, const void *rows, int64_t ncomp, int64_t rowlen, int64_t nspans,
+                               const int32_t *first, const uint8_t *mask, uint8_t *flags);
+bsk_status bsk_roots_flag(bsk_dtype dtype, int order, const void *rows, int64_t ncomp, int64_t rowlen, int64_t nspans,
+                          const int32_t *first, const uint8_t *mask, uint8_t *flags, void *stream);
+bsk_status bsk_roots_isolate_host(bsk_dtype dtype, int order, const void *rows, int64_t ncomp, int64_t rowlen, int64_t nspans,
+                                  const int32_t *first, const uint8_t *mask, const double *breaks, const double *scale,
+                                  double margin, const int64_t *cand, int64_t ncand, double *roots, int32_t *count);
+bsk_status bsk_roots_isolate(bsk_dtype dtype, int order, const void *rows, int64_t ncomp, int64_t rowlen, int64_t nspans,
+                             const int32_t *first, const uint8_t *mask, const double *breaks, const double *scale,
+                             double margin, const int64_t *cand, int64_t ncand, double *roots, int32_t *count, void *stream);
+const char *bsk_roots_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
