@@ -133,6 +133,39 @@ def blossom_weights(knots, order, first, args):
     return D[:, k - 1]
 
 
+def row_exists(newKnots, j, n, lo, hi):
+    """Rows j whose basis function on ``newKnots`` (blossoms of n arguments) has a non-empty cell inside [lo, hi]; the
+    others hold the coefficients of a polynomial extension."""
+    tb = newKnots
+    exists = np.zeros(len(j), bool)
+    for off in range(n + 1):
+        c = j + off
+        exists |= (tb[c + 1] > tb[c]) & (tb[c] >= lo) & (tb[c + 1] <= hi)
+    return exists
+
+
+def weight_support(knots, order, newKnots, m, j, first):
+    """(rows, k) mask of the weights w[row, q], on old coefficient i = first[row] + q, that are not zero in exact
+    arithmetic, from the knots alone (the support condition of the discrete B-spline).  Old basis function i, raised
+    by m, is a positive combination of exactly the new basis functions on the windows of k + m + 1 consecutive knots of
+    its own refined knots: t[i .. i + k], every distinct value m times more, and the new knots strictly inside.  Those
+    agree with ``newKnots`` inside (t[i], t[i + k]), so row j carries old coefficient i exactly when
+    newKnots[j .. j + k + m] lies in [t[i], t[i + k]] and holds no more copies of either end than that."""
+    t, tb, k = knots, newKnots, int(order)
+    n = k + m - 1
+    i = first[:, None] + np.arange(k)                                   # (rows, k)
+    tlo, thi = t[i], t[i + k]
+    # copies of t[i] (of t[i + k]) among t[i .. i + k]
+    span = t[i[:, :, None] + np.arange(k + 1)]
+    a = (span == tlo[:, :, None]).sum(axis=2)
+    b = (span == thi[:, :, None]).sum(axis=2)
+    window = tb[j[:, None] + np.arange(n + 2)]                          # (rows, k + m + 1)
+    head = (window == window[:, :1]).sum(axis=1)[:, None]
+    tail = (window == window[:, -1:]).sum(axis=1)[:, None]
+    wlo, whi = window[:, :1], window[:, -1:]
+    return (wlo >= tlo) & (whi <= thi) & ((wlo > tlo) | (head <= a + m)) & ((whi < thi) | (tail <= b + m))
+
+
 def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     """BandMap arrays (first, w) that take the coefficients on ``knots`` (order k) to those of the same function on
     ``newKnots`` (order k + m), for the output rows ``rows`` (a slice; default all).  ``newKnots`` must hold every
@@ -140,7 +173,14 @@ def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     of the old knot it is, or -1 for an inserted one; a row whose blossom arguments are consecutive old knots is then
     the exact unit row.
     Rows whose support has no cell inside the domain take the domain's nearest cell: they hold the coefficients of
-    the polynomial extension of that piece."""
+    the polynomial extension of that piece.
+    Every weight of a row that exists whose exact value is zero is stored as 0.0 and none is negative, for every m and
+    for the ``rows=`` and ``origin=`` forms (``weight_support``): an output never sees an input it has no weight on,
+    whatever that input's magnitude, and a row is a convex combination.  Should the recurrence round a weight that is
+    positive in exact arithmetic to zero or below (it has to be smaller than the recurrence's own rounding error for
+    that; no operator of the tests does it), the smallest positive double is stored in its place, so that the stored
+    pattern stays the exact one; the weights themselves still come from the recurrence on the chosen cell, whose
+    error grows with the ratio of the knot gaps involved."""
     t = np.asarray(knots, np.float64)
     tb = np.asarray(newKnots, np.float64)
     k = int(order)
@@ -153,13 +193,20 @@ def refine_map(knots, order, newKnots, m=0, rows=None, origin=None):
     first = knot_cell(t, k, x) - k + 1
 
     # the recurrence runs in extended precision where the platform has it (x86: 64-bit mantissa), so that the
-    # weights are correctly rounded doubles but for rare ties; elsewhere it runs in double
+    # weights are correctly rounded doubles but for rare ties while the knot gaps are of one scale; elsewhere it runs in double
     t, tb = t.astype(np.longdouble), tb.astype(np.longdouble)
     w = np.zeros((len(j), k), np.longdouble)
     subsets = list(itertools.combinations(range(n), k - 1))
     for subset in subsets:
         w += blossom_weights(t, k, first, tb[j[:, None] + 1 + np.array(subset, np.int64)])
     w = (w / len(subsets)).astype(np.float64)
+    # the recurrence leaves rounding residue (either sign) where cancellation gives an exact zero: those entries are
+    # decided by the knots alone.  A weight of a row that exists is positive where it is not zero; the recurrence
+    # can round a positive weight below 1e-19 to the other side, which is stored as the smallest positive double
+    exists = row_exists(tb, j, n, lo, hi)
+    zero = ~weight_support(np.asarray(knots, np.float64), k, np.asarray(newKnots, np.float64), m, j, first)
+    w[exists[:, None] & zero] = 0.0
+    w[exists[:, None] & ~zero & (w <= 0.0)] = np.finfo(np.float64).tiny
     if m == 0 and origin is not None and k > 1:
         # the blossom's arguments are k - 1 consecutive old knots: the value is the old coefficient in front of them
         origin = np.asarray(origin)

@@ -413,3 +413,151 @@ def scale_cases():
     return {"families": scale_families(), "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "fit": scale_fit_systems(),
             "splines": scale_splines(), "domains": SCALE_DOMAINS, "splines_f32": scale_splines_f32(),
             "domains_f32": SCALE_DOMAINS_F32, "sample": SCALE_SAMPLE, "illscaled": scale_illscaled()}
+
+
+# ---------------------------------------------------------------------------------------------
+# Scale tests of the operator families (tests/test_scale_host.py, tests/test_gpu_scale_ops.py): band (insert_knots,
+# elevate, trim, clamp, differentiate), product (multiply), scan / sum (integrate, add, subtract) and roots (zeros_batch).
+# ---------------------------------------------------------------------------------------------
+OPERATOR_KERNELS = {"band": {"band_apply", "band_apply_line"}, "product": {"band_product_line", "band_product_tile"},
+                    "sum": {"scan_apply", "scan_line", "sum_bcast"}, "roots": {"roots_flag", "roots_isolate"}}
+TRIM_CLEARANCE = 2.0 ** -10         # of the domain width: how far a trim bound of these cases stays from every knot
+
+
+class OpCase:
+    """One public call: ``operands`` [(order, knots, coefs)] on [0, 1] (or around it, unclamped), the operation, its
+    arguments, and the kernels ``LAST_PATHS`` must name on the device path, in order."""
+
+    def __init__(self, name, family, op, operands, kernels, **args):
+        self.name, self.family, self.op, self.operands, self.kernels, self.args = name, family, op, operands, list(kernels), args
+
+    @property
+    def dt(self):
+        return self.operands[0][2].dtype.type
+
+    @property
+    def kind(self):
+        return "fp32" if self.dt == np.float32 else "fp64"
+
+    def replaced(self, operands, **args):
+        return OpCase(self.name, self.family, self.op, operands, self.kernels, **{**self.args, **args})
+
+
+def operator_knots(rng, order, ncoef, unclamped=False):
+    """Sorted random knots with one double interior knot: clamped on [0, 1], or unclamped with the domain inside [-1, 2]."""
+    if unclamped:
+        return np.sort(rng.random(order + ncoef) * 3.0 - 1.0)
+    interior = np.sort(rng.random(ncoef - order))
+    if ncoef - order > 4 and order > 2:
+        interior[2] = interior[1]
+    return np.concatenate((order * [0.0], interior, order * [1.0]))
+
+
+def operator_spline(seed, order, ncoef, ndep, dt=np.float64, unclamped=()):
+    rng = np.random.default_rng(seed)
+    knots = [operator_knots(rng, o, c, iv in unclamped) for iv, (o, c) in enumerate(zip(order, ncoef))]
+    return tuple(order), knots, rng.standard_normal((ndep, *ncoef)).astype(dt)
+
+
+def clear_bound(knots, order, at):
+    """A trim bound near the fraction ``at`` of the domain: the middle of the widest knot cell whose middle lies within a
+    tenth of the width of it."""
+    t = np.unique(np.asarray(knots, np.float64)[order - 1:len(knots) - order + 1])
+    mid, gap = 0.5 * (t[1:] + t[:-1]), np.diff(t)
+    lo, width = t[0], t[-1] - t[0]
+    near = np.abs(mid - (lo + at * width)) <= 0.1 * width
+    return float(mid[near][np.argmax(gap[near])])
+
+
+def band_cases(tag, spline, loose, new, kernel, family="band"):
+    """The six band operations on variable 0 of ``spline`` (clamped) and ``loose`` (the same shape, variable 0 unclamped);
+    ``new``: knots to insert."""
+    order, knots, _ = spline
+    rest = len(order) - 1
+    pad = lambda first, fill: [first] + rest * [fill]
+    bounds = [clear_bound(knots[0], order[0], 0.3), clear_bound(knots[0], order[0], 0.7)]
+    k = [kernel]
+    return [OpCase(f"insert_knots {tag}", family, "insert_knots", [spline], k, new=pad(list(new), [])),
+            OpCase(f"elevate 1 {tag}", family, "elevate", [spline], k, m=pad(1, 0)),
+            OpCase(f"elevate_and_insert_knots 3 {tag}", family, "elevate_and_insert_knots", [spline], k, m=pad(3, 0), new=pad(list(new[:5]), [])),
+            OpCase(f"clamp {tag}", family, "clamp", [loose], k, left=[0], right=[0]),
+            OpCase(f"trim {tag}", family, "trim", [spline], k, domain=pad(bounds, [None, None])),
+            OpCase(f"differentiate {tag}", family, "differentiate", [spline], k, wrt=0)]
+
+
+def product_cases(tag, a, b, indMap, kernel, types=("S", "D", "C")):
+    return [OpCase(f"multiply {t} {tag}", "product", "multiply", [a, b], [kernel], indMap=indMap, productType=t) for t in types]
+
+
+def operator_scale_cases():
+    """Part A / C (the smallest shapes of the layout lists that still split every way) and part B (small enough for the
+    Fraction references) of the operator sweep, as {"A": [OpCase], "B": [OpCase], "roots_curve": ..., "roots_b": ...}.
+    A band: (5, 120, 37) odd inner extent and scalar lanes, (2, 120, 64) vector lanes, (3, 120) lines, (120, 1030) axis 0.
+    A product: a line pair (120, 75) with 37 planes; a tile pair (40, 37) x (33, 41), ragged last tiles both ways.
+    A scan: n = 1030, ragged chunks and more than one segment.  A sum: a surface plus a curve, broadcast."""
+    f32, f64 = np.float32, np.float64
+    new = np.random.default_rng(900).random(20)
+    A = []
+    for dt in (f64, f32):
+        for ndep, ncoef in [(5, (120, 37)), (2, (120, 64)), (3, (120,)), (1, (120, 1030))]:
+            order = (4, 3)[:len(ncoef)]
+            tag = f"({ndep}, {', '.join(map(str, ncoef))}) {np.dtype(dt).name}"
+            A += band_cases(tag, operator_spline(901, order, ncoef, ndep, dt), operator_spline(902, order, ncoef, ndep, dt, unclamped=(0,)),
+                            new, "band_apply" if len(ncoef) > 1 else "band_apply_line")
+    for dt in (f64, f32):
+        n = np.dtype(dt).name
+        A += product_cases(f"line (120, 75) x 37 planes {n}", operator_spline(903, (2, 4), (37, 120), 3, dt),
+                           operator_spline(904, (3,), (75,), 3, dt), [(1, 0)], "band_product_line")
+        A += product_cases(f"tile (40, 37) x (33, 41) {n}", operator_spline(905, (4, 3), (40, 37), 3, dt),
+                           operator_spline(906, (3, 4), (33, 41), 3, dt), [(0, 0), (1, 1)], "band_product_tile")
+        for segments in (1, 2, 5):
+            A.append(OpCase(f"integrate scan_apply n 1030 segments {segments} {n}", "sum", "integrate",
+                            [operator_spline(907, (4, 3), (1030, 5), 3, dt)], ["scan_apply"], wrt=0, segments=segments))
+            A.append(OpCase(f"integrate scan_line n 1030 segments {segments} {n}", "sum", "integrate",
+                            [operator_spline(908, (3, 4), (5, 1030), 3, dt)], ["scan_line"], wrt=1, segments=segments))
+        surf = operator_spline(909, (4, 3), (40, 37), 3, dt)
+        line = (surf[0][:1], surf[1][:1], np.random.default_rng(910).standard_normal((3, 40)).astype(dt))
+        for op in ("add", "subtract"):
+            A.append(OpCase(f"{op} surface (40, 37) and curve (40) {n}", "sum", op, [surf, line], ["sum_bcast"], indMap=[(0, 0)]))
+
+    # part B: curves of 30 and 25 coefficients, orders 4 and 3, two components; a surface of 12 x 11 and partners
+    B = []
+    for dt in (f64, f32):
+        n = np.dtype(dt).name
+        c4, c4u = operator_spline(1, (4,), (30,), 2, dt), operator_spline(2, (4,), (30,), 2, dt, unclamped=(0,))
+        c3 = operator_spline(3, (3,), (25,), 2, dt)
+        s, su = operator_spline(4, (4, 3), (12, 11), 2, dt), operator_spline(5, (4, 3), (12, 11), 2, dt, unclamped=(0,))
+        s2 = operator_spline(6, (3, 3), (11, 12), 2, dt)
+        c9 = operator_spline(7, (3,), (9,), 2, dt)
+        few = np.random.default_rng(911).random(6)
+        B += band_cases(f"curve 30 {n}", c4, c4u, few, "band_apply_line")
+        B += band_cases(f"surface 12 x 11 {n}", s, su, few, "band_apply")
+        B += product_cases(f"curves 30 x 25 {n}", c4, c3, [(0, 0)], "band_product_line")
+        B += product_cases(f"surfaces 12 x 11, 11 x 12 {n}", s, s2, [(0, 0), (1, 1)], "band_product_tile")
+        B.append(OpCase(f"integrate curve 30 {n}", "sum", "integrate", [c4], ["scan_line"], wrt=0, segments=None))
+        B.append(OpCase(f"integrate surface 12 x 11 {n}", "sum", "integrate", [s], ["scan_apply"], wrt=0, segments=None))
+        line = (s[0][:1], s[1][:1], np.random.default_rng(913).standard_normal((2, 12)).astype(dt))
+        for op in ("add", "subtract"):
+            B.append(OpCase(f"{op} surface 12 x 11 and curve 12 {n}", "sum", op, [s, line], ["sum_bcast"], indMap=[(0, 0)]))
+            if dt is f64:
+                # the curve is raised to the surface's order and both take each other's knots: band kernels, then the sum
+                # (float32 would round twice, which the one-rounding bar of part B does not cover)
+                B.append(OpCase(f"{op} surface 12 x 11 and curve 9 {n}", "sum", op, [s, c9],
+                                ["band_apply", "band_apply_line", "sum_bcast"], indMap=[(0, 0)]))
+    # part C, band: pure knot insertion where rounding residue in structurally zero weights showed (orders 4, 8, 6 with
+    # 20, 30 and 200 new knots), on lines and on a surface; parts B's cases (m = 0, 1, 3) are run as well
+    C = []
+    for order, ncoef, count in ((4, 40, 20), (8, 40, 30), (6, 120, 200)):
+        more = np.random.default_rng(920).random(count)
+        C.append(OpCase(f"insert_knots {count} into order {order} curve {ncoef}", "band", "insert_knots",
+                        [operator_spline(920, (order,), (ncoef,), 2)], ["band_apply_line"], new=[list(more)]))
+    C.append(OpCase("insert_knots 30 into order 8 x 3 surface 40 x 6", "band", "insert_knots",
+                    [operator_spline(921, (8, 3), (40, 6), 2)], ["band_apply"], new=[list(np.random.default_rng(921).random(30)), []]))
+    roots_b = {dt: operator_spline(1, (4,), (30,), 2, dt) for dt in (f64, f32)}
+
+    def many_spans(dt):
+        rng = np.random.default_rng(912)
+        t = np.concatenate((4 * [0.0], np.sort(rng.random(256)), 4 * [1.0]))
+        return (4,), [t], rng.standard_normal((3, len(t) - 4)).astype(dt)
+    return {"A": A, "B": B, "C": C, "roots_b": roots_b, "roots_curves": {dt: many_spans(dt) for dt in (f64, f32)},
+            "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "domains": SCALE_DOMAINS, "domains_f32": SCALE_DOMAINS_F32}

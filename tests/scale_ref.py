@@ -386,3 +386,103 @@ def fit_system(order, nrows, ncols, outer, inner, seed):
     first, values = fit_ref.banded_matrix(knots, order, u)                  # on the CPU: the host module builds it too
     b = np.random.default_rng(outer * 7 + inner).standard_normal((outer, nrows, inner))
     return fitting.Plan(first, values, ncols), np.asarray(first), np.asarray(values, np.float64), b
+
+
+# ------------------------------------------------------------------------------------------------- operator specs
+# A cases.OpCase is a public spline-to-spline call: operands [(order, knots, coefs)], an operation and its arguments.
+# With coefficient row d of operand i x 2^ks[i][d] and every knot, inserted knot and trim bound x 2^kp, the result's
+# knots are x 2^kp and row d of its coefficients x 2^op_exponent(...)[d], bit for bit: every weight of an operator is a
+# ratio of knot differences (unchanged), a derivative weight 1 / difference (x 2^-kp), an integral weight a difference
+# (x 2^kp), and every rounding commutes with a power of two.
+PARAMETER_ARGS = ("new", "domain")
+
+
+def _scale_arg(value, fn):
+    """fn on every number of a nested argument (lists, (value, multiplicity) pairs keep their multiplicity, None stays)."""
+    if value is None:
+        return None
+    if isinstance(value, tuple):
+        return (fn(value[0]), value[1])
+    if isinstance(value, (list, np.ndarray)):
+        return [_scale_arg(v, fn) for v in value]
+    return fn(value)
+
+
+def op_scaled(case, ks, kp):
+    operands = [(order, [_p2(t, kp) for t in knots], np.stack([_p2(row, k) for row, k in zip(coefs, rows)]))
+                for (order, knots, coefs), rows in zip(case.operands, ks)]
+    args = {key: _scale_arg(case.args[key], lambda v: float(np.ldexp(np.float64(v), kp))) for key in PARAMETER_ARGS if key in case.args}
+    return case.replaced(operands, **args)
+
+
+def op_exponent(case, ks, kp):
+    """Per dependent row of the result (or one for all rows): the exponent the law predicts for its coefficients."""
+    k0 = np.asarray(ks[0])
+    if case.op == "differentiate":
+        return k0 - kp
+    if case.op == "integrate":
+        return k0 + kp
+    if case.op in ("add", "subtract"):
+        assert list(ks[0]) == list(ks[1])
+        return k0
+    if case.op == "multiply":
+        k1 = np.asarray(ks[1])
+        if case.args["productType"] == "S":
+            return k0 + k1
+        assert len(set(k0)) == 1 and len(set(k1)) == 1, "a dot or cross product sums planes: one exponent per operand"
+        return np.array([int(k0[0] + k1[0])])
+    return k0
+
+
+def op_transforms(case, exponents, rows):
+    """[(label, per-operand per-row coefficient exponents, parameter exponent)]: the type's (kc, kp) pairs, then one
+    exponent per dependent plane (per operand where the operation sums planes)."""
+    ndep = [coefs.shape[0] for _, _, coefs in case.operands]
+    two = case.op == "multiply"
+    out = []
+    for kc, kp in exponents[case.kind]:
+        ks = [[kc] * ndep[0]] + ([[kc // 2] * ndep[1]] if two else [[kc] * n for n in ndep[1:]])
+        out.append((f"coefficients x 2^{[k[0] for k in ks]}, knots x 2^{kp}", ks, kp))
+    r = rows[case.kind]
+    cyc = lambda n, shift=0: [r[(d + shift) % len(r)] for d in range(n)]
+    if two and case.args["productType"] != "S":
+        ks = [[r[0]] * ndep[0], [r[-1] // 2] * ndep[1]]
+    elif two:
+        ks = [cyc(ndep[0]), cyc(ndep[1], 1)]
+    else:
+        ks = [cyc(n) for n in ndep]
+    out.append((f"dependent rows x 2^{ks}", ks, 0))
+    return out
+
+
+def map_axis(knots, order, lo, width, dtype, values=None):
+    """The knots of one variable under the affine map of its domain onto [lo, lo + width], as map_domain maps a
+    non-uniform axis (sorted, in ``dtype``; knots outside the domain of an unclamped variable go along); ``values``:
+    parameters to map the same way instead, clipped into the new domain."""
+    k = np.asarray(knots, np.float64)
+    k0, k1 = k[order - 1], k[len(k) - order]
+    m = np.sort(lo + width * ((k - k0) / (k1 - k0))).astype(dtype)
+    if values is None:
+        return m
+    a, b = m[order - 1], m[len(k) - order]
+    return _scale_arg(values, lambda v: float(np.clip(dtype(lo + width * ((np.float64(v) - k0) / (k1 - k0))), a, b)))
+
+
+def op_shifted(case, lo, width):
+    """The case with every operand's domain moved to [lo, lo + width] (knots in the coefficients' dtype), inserted knots
+    and trim bounds mapped as the knots of operand 0 and clipped into the domain."""
+    dt = case.dt
+    order0, knots0, _ = case.operands[0]
+    operands = [(order, [map_axis(t, k, lo, width, dt) for t, k in zip(knots, order)], coefs) for order, knots, coefs in case.operands]
+    args = {}
+    for key in PARAMETER_ARGS:
+        if key in case.args:
+            args[key] = [map_axis(t, k, lo, width, dt, values=v) for t, k, v in zip(knots0, order0, case.args[key])]
+    return case.replaced(operands, **args)
+
+
+def multiplied(coefs, index, k):
+    """coefs with the one entry ``index`` x 2^k."""
+    c = np.array(coefs)
+    c[index] = np.ldexp(c[index], k)
+    return c

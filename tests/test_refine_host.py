@@ -17,6 +17,7 @@ exact value and no influence inside the domain: they are left out of the coeffic
 compared with the original by evaluation over the domain.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -199,10 +200,24 @@ def check_operator(first, w, order, n_in, exists=None):
     assert w.shape[1] <= order
     assert np.all(np.diff(first) >= 0) and first[0] >= 0 and first[-1] + w.shape[1] <= n_in
     assert np.abs(w.sum(axis=1) - 1.0).max() <= 64 * EPS
-    assert (w if exists is None else w[exists]).min() >= -64 * EPS
+    assert (w if exists is None else w[exists]).min() >= 0.0
 
 
-def test_operator_properties_random():
+def check_zero_pattern(first, w, rows, n_in, label):
+    """(w != 0) is the pattern of the exact rows (refine_ref.refine_rows): a weight whose exact value is zero is stored as
+    0.0, and no weight that is not zero in exact arithmetic has gone.  Rows without an exact value are left out."""
+    k = w.shape[1]
+    for j, row in enumerate(rows):
+        if row is None:
+            continue
+        got, want = np.zeros(n_in, bool), np.zeros(n_in, bool)
+        got[first[j]:first[j] + k] = w[j] != 0.0
+        want[row[0]:row[0] + len(row[1])] = [v != 0 for v in row[1]]
+        assert np.array_equal(got, want), f"{label}, row {j}: stored non-zeros at {np.flatnonzero(got)}, exact ones at {np.flatnonzero(want)}"
+
+
+def random_operators():
+    """The sixty random operators of test_operator_properties_random: (trial, order, m, knots, new knots)."""
     rng = np.random.default_rng(11)
     for trial in range(60):
         order = int(rng.integers(1, 9))
@@ -210,6 +225,34 @@ def test_operator_properties_random():
         t = random_knots(rng, order, ncoef)
         m = int(rng.integers(0, 4))
         new = list(rng.random(int(rng.integers(0 if m else 1, 30))))
+        yield trial, order, m, t, new
+
+
+# Exact rows cost rows x subsets x order^2 Fraction operations.  Above this the pattern of an operator is not computed in
+# the test but read from tests/golden/refine_patterns.npz, which tests/golden/make_golden_refine_patterns.py wrote from
+# the same refine_ref.refine_rows (14 of the 60 operators, 1 to 23 s each, two minutes together).
+EXACT_ROWS_BUDGET = 40_000
+
+
+def exact_rows_cost(order, m, n_out):
+    return n_out * math.comb(order + m - 1, order - 1) * order * order
+
+
+def dense_pattern(rows, n_in):
+    """(rows, n_in) bool: where the exact rows are not zero (every row must exist)."""
+    out = np.zeros((len(rows), n_in), bool)
+    for j, (at, weights) in enumerate(rows):
+        out[j, at:at + len(weights)] = [v != 0 for v in weights]
+    return out
+
+
+def test_operator_properties_random():
+    """Every one of the sixty operators: the band's shape, rows that sum to one, no negative weight, and (w != 0) equal
+    to the exact rows' pattern, computed here or recorded (the recorded ones are tied to their knots bit for bit)."""
+    recorded = np.load(os.path.join(GOLDEN, "refine_patterns.npz"))
+    from_file = 0
+    for trial, order, m, t, new in random_operators():
+        ncoef = len(t) - order
         if m:
             tbar = refinement.elevated_knots(t, order, m, new)
             first, w = refinement.refine_map(t, order, tbar, m)
@@ -218,6 +261,44 @@ def test_operator_properties_random():
             first, w = refinement.refine_map(t, order, tbar, 0, origin=origin)
         assert len(first) == len(tbar) - order - m
         check_operator(first, w, order, ncoef)
+        label = f"trial {trial}: order {order}, m {m}"
+        if exact_rows_cost(order, m, len(first)) <= EXACT_ROWS_BUDGET:
+            assert f"{trial}/pattern" not in recorded.files
+            check_zero_pattern(first, w, refine_ref.refine_rows(t, order, tbar, m), ncoef, label)
+            continue
+        assert recorded[f"{trial}/knots"].tobytes() == t.tobytes() and recorded[f"{trial}/new_knots"].tobytes() == tbar.tobytes(), \
+            f"{label}: the recorded pattern belongs to other knots"
+        got = np.zeros((len(first), ncoef), bool)
+        for j in range(len(first)):
+            got[j, first[j]:first[j] + order] = w[j] != 0.0
+        want = recorded[f"{trial}/pattern"]
+        assert got.shape == want.shape
+        differ = np.flatnonzero((got != want).any(axis=1))
+        assert not len(differ), f"{label}: rows {differ} differ from the recorded exact pattern"
+        from_file += 1
+    assert from_file == len(recorded.files) // 3 == 14
+
+
+def test_zero_pattern_of_trim_rows_and_tiny_weights():
+    """The ``rows=`` / ``origin=`` form (trim, clamp) stores the same structural zeros; a weight that is tiny but not zero
+    (a new knot 1e-9 of a cell away from an old one) stays."""
+    rng = np.random.default_rng(12)
+    for order, unclamped in ((4, False), (6, True), (8, False)):
+        t = random_knots(rng, order, order + 25, unclamped)
+        lo, hi = t[order - 1], t[len(t) - order]
+        wanted = [(lo + 0.31 * (hi - lo), order), (lo + 0.72 * (hi - lo), order)]
+        merged, origin = refinement.merged_knots(t, order, wanted)
+        row0, row1 = int(np.searchsorted(merged, wanted[0][0])), int(np.searchsorted(merged, wanted[1][0]))
+        first, w = refinement.refine_map(t, order, merged, 0, rows=slice(row0, row1), origin=origin)
+        rows = refine_ref.refine_rows(t, order, merged, 0)[row0:row1]
+        check_operator(first, w, order, len(t) - order, np.array([row is not None for row in rows]))
+        check_zero_pattern(first, w, rows, len(t) - order, f"trim rows, order {order}")
+    t = random_knots(rng, 4, 12)
+    near = t[6] + 1e-9 * (t[7] - t[6])
+    merged, origin = refinement.merged_knots(t, 4, [near])
+    first, w = refinement.refine_map(t, 4, merged, 0, origin=origin)
+    check_zero_pattern(first, w, refine_ref.refine_rows(t, 4, merged, 0), 12, "a nearly coincident knot")
+    assert 0.0 < w[w > 0.0].min() < 1e-8
 
 
 def test_operator_properties_goldens(golden):
@@ -231,6 +312,7 @@ def test_operator_properties_goldens(golden):
             first, w = refinement.refine_map(t, k, t2, k2 - k)
             rows = refine_ref.refine_rows(t, k, t2, k2 - k)
             check_operator(first, w, k, len(t) - k, np.array([row is not None for row in rows]))
+            check_zero_pattern(first, w, rows, len(t) - k, name)
             dense = np.zeros((len(first), len(t) - k))
             for j in range(len(first)):
                 dense[j, first[j]:first[j] + k] = w[j]
