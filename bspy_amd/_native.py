@@ -39,6 +39,11 @@ PRODUCT_SYMBOLS = (
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
 SYMBOLS = PRODUCT_SYMBOLS + INTERNAL_SYMBOLS
+# ... and the family of Spline.zeros2, also product ABI.  Listed apart because of the digit in the names: the header scan of
+# tests/test_host_logic.py reads names of [a-z_] only and compares them with the tuples above; tests/test_roots2_host.py
+# compares these with the header, and build() checks that the library exports them
+ROOTS2_SYMBOLS = ("bsk_roots2_flag_host", "bsk_roots2_flag", "bsk_roots2_isolate_host", "bsk_roots2_isolate", "bsk_roots2_merge_host",
+                  "bsk_roots2_merge", "bsk_roots2_last_kernel")
 
 
 class NativeLibraryError(RuntimeError):
@@ -157,15 +162,25 @@ def lib():
                                     _i64, _vp, _vp, _vp]
     L.bsk_roots_last_kernel.argtypes = []
     L.bsk_roots_last_kernel.restype = ctypes.c_char_p
+    grid2 = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]
+    L.bsk_roots2_flag_host.argtypes = grid2 + [_vp, _vp]
+    L.bsk_roots2_flag.argtypes = grid2 + [_vp, _vp, _vp]
+    L.bsk_roots2_isolate_host.argtypes = grid2 + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.bsk_roots2_isolate.argtypes = grid2 + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.bsk_roots2_merge_host.argtypes = [ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]
+    L.bsk_roots2_merge.argtypes = [ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]
+    L.bsk_roots2_last_kernel.argtypes = []
+    L.bsk_roots2_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
     L.bsk_debug_stage_times.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, _ip]
     L.bsk_debug_fill_lds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _i64p, _vp]
-    for name in SYMBOLS:
+    for name in SYMBOLS + ROOTS2_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
-                        "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel"):
+                        "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
+                        "bsk_roots2_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

@@ -21,10 +21,11 @@ error messages for
     s.translate(vector), s + x, x + s, s - x, x - s               spline.py:2335, :85-95, :132-143
     s.integrate(with_respect_to=0) / s.contract(uvw)              spline.py:1290, :567
     s.zeros() (curves: nInd == nDep == 1)                         spline.py:2470
+    s.zeros2() (the same call for nInd == nDep == 2)              spline.py:2470
     to_dict / from_dict / load / save (JSON, as an input format)   spline.py:1099-1125, :1542-1583, :1998-2026, :2254-2267
 
 The arithmetic runs on the GPU (bspy_amd/_spline_evaluation.py -> libbspy_amd.so); the
-rest of the reference's Spline API (the other fitting calls - fit, contour, solve_ode, ... -, zeros for nInd > 1,
+rest of the reference's Spline API (the other fitting calls - fit, contour, solve_ode, ... -, zeros for nInd > 2,
 intersect, contours, CSG, viewer) is out of scope.
 
 Documented deviations from the reference:
@@ -401,6 +402,20 @@ class Spline:
         for every component of a curve with any nDep."""
         from . import roots as _roots
         return _roots.zeros(self, epsilon, initialScale, **kwargs)
+
+    def zeros2(self, **kwargs):
+        """The isolated common zeros of two scalar splines in two variables (nInd == nDep == 2; the reference reaches them
+        through ``zeros``, whose name here stays with curves): a list, sorted by (u, v), of length-2 arrays (u, v) of the
+        knots' dtype and, for every knot cell on which a component vanishes, a tuple ((u0, v0), (u1, v1)).  Both variables
+        are brought to Bezier form by the band operator; cells whose coefficients exclude a zero are rejected by one kernel,
+        the others are walked by dyadic subdivision, one lane per cell, and polished by Newton steps (few cells and orders 5
+        and 6: the same arithmetic on the host).  What counts as a zero is stated in bspy_amd/roots2.py.  Results are bitwise
+        reproducible and the same on both paths.  Raises the reference's ValueError for nInd != nDep, a ValueError that names
+        the cell when zeros could not be isolated there or a zero is tangential, NotImplementedError for nInd != 2 or an
+        order above 6.  ``_path="device"`` / ``"host"`` pins the path.  ``bspy_amd.roots2.zeros2_batch`` solves many systems
+        on the same knots in one launch sequence."""
+        from . import roots2 as _roots2
+        return _roots2.zeros2(self, **kwargs)
 
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)

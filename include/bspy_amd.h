@@ -371,6 +371,56 @@ bsk_status bsk_roots_isolate(bsk_dtype dtype, int order, const void *rows, int64
 const char *bsk_roots_last_kernel(void);
 
 /*
+ * Isolated common zeros of two scalar splines in two variables (Spline.zeros2; the statement of what a zero is and of the
+ * arithmetic is in bspy_amd/roots2.py and DESIGN.md section 17).  The family keeps no handle.  The caller brings both
+ * variables to Bezier form with the band operator: rows[nsys][2][R0][R1] (doubles) holds nsys systems of two components
+ * on the same knots, and cell (i, j), i < nc0, j < nc1, is the K0 x K1 window of both components at first0[i], first1[j];
+ * it covers [breaks0[i], breaks0[i + 1]] x [breaks1[j], breaks1[j + 1]].  A cell's flat index is
+ * (system * nc0 + i) * nc1 + j.  A window that leaves the rows, or a flat index that is no cell, gives no zero instead of
+ * a read out of bounds.
+ *   bsk_roots2_flag(_host)   : flags[nsys][nc0][nc1] (bytes) = 1 unless mask (same shape; a zero cell) is set or a
+ *                              component's K0 K1 Bernstein coefficients are all > 0 or all < 0.
+ *   bsk_roots2_isolate(_host): cand[ncand] (int64, flat indices of the flagged cells, ncand >= 1: no candidates means no
+ *                              call); scale[nsys][2] = max |coefficient| of the component.  Per candidate: the zeros go to
+ *                              roots[ncand][R][2] as (u, v), R = 2 (K0 - 1)(K1 - 1), NaN behind the last one; near[ncand][R]
+ *                              (bytes) = 1 for a zero within 2^-20 of an edge of its cell; count[ncand] (int32);
+ *                              status[ncand] (bytes): bit 1 = the walk visited more than its bound of nodes (zeros not
+ *                              isolated), bit 2 = more than R zeros, bit 4 = a tangential or singular zero, not reported;
+ *                              nodes[ncand] (int32) = the boxes the walk visited.  One lane per candidate walks the dyadic
+ *                              boxes of the cell depth first without a stack, 24 halvings per axis, dropping a box when a
+ *                              component's coefficients are strictly of one sign, and polishes a leaf with at most 8
+ *                              Newton steps.
+ *   bsk_roots2_merge(_host)  : which[nnear] (int64, flat indices candidate * R + slot of the zeros with near set,
+ *                              nnear >= 1); table[nsys][nc0][nc1] (int64) = cumsum(flags) - 1, the candidate of a flagged
+ *                              cell.  keep[ncand][R] (bytes): a lane clears its own byte when a neighbouring cell of the
+ *                              same system with a lower flat index holds a zero within 2^-20 of the lane's cell widths on
+ *                              both axes, and sets it otherwise; no other byte is written.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1 in 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above; the host drivers take 2 .. 6).  No atomics, no waiting, every loop has a compile-time
+ *   bound; the host drivers and the kernels give the same bits.
+ *   bsk_roots2_last_kernel   : "roots2_flag", "roots2_isolate", "roots2_merge" or the same behind "host ".
+ */
+bsk_status bsk_roots2_flag_host(int K0, int K1, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                                const int32_t *first0, const int32_t *first1, const uint8_t *mask, uint8_t *flags);
+bsk_status bsk_roots2_flag(int K0, int K1, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                           const int32_t *first0, const int32_t *first1, const uint8_t *mask, uint8_t *flags, void *stream);
+bsk_status bsk_roots2_isolate_host(int K0, int K1, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t nc0,
+                                   int64_t nc1, const int32_t *first0, const int32_t *first1, const double *breaks0,
+                                   const double *breaks1, const double *scale, const int64_t *cand, int64_t ncand, double *roots,
+                                   uint8_t *near, int32_t *count, uint8_t *status, int32_t *nodes);
+bsk_status bsk_roots2_isolate(int K0, int K1, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                              const int32_t *first0, const int32_t *first1, const double *breaks0, const double *breaks1,
+                              const double *scale, const int64_t *cand, int64_t ncand, double *roots, uint8_t *near,
+                              int32_t *count, uint8_t *status, int32_t *nodes, void *stream);
+bsk_status bsk_roots2_merge_host(int R, const double *roots, int64_t nsys, int64_t nc0, int64_t nc1, const double *breaks0,
+                                 const double *breaks1, const int64_t *cand, int64_t ncand, const uint8_t *flags,
+                                 const int64_t *table, const int64_t *which, int64_t nnear, uint8_t *keep);
+bsk_status bsk_roots2_merge(int R, const double *roots, int64_t nsys, int64_t nc0, int64_t nc1, const double *breaks0,
+                            const double *breaks1, const int64_t *cand, int64_t ncand, const uint8_t *flags, const int64_t *table,
+                            const int64_t *which, int64_t nnear, uint8_t *keep, void *stream);
+const char *bsk_roots2_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
