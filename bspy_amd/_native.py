@@ -31,6 +31,7 @@ PRODUCT_SYMBOLS = (
     "bsk_fit_create", "bsk_fit_destroy", "bsk_fit_info", "bsk_fit_solve_host", "bsk_fit_sweep", "bsk_fit_residual",
     "bsk_fit_last_kernel",
     "bsk_band_create", "bsk_band_destroy", "bsk_band_apply_host", "bsk_band_apply", "bsk_band_last_kernel",
+    "bsk_band_absmax", "bsk_band_absmax_host", "bsk_band_apply_fma_host",
     "bsk_product_create", "bsk_product_destroy", "bsk_product_apply_host", "bsk_product_apply", "bsk_product_last_kernel",
     "bsk_scan_create", "bsk_scan_destroy", "bsk_scan_apply_host", "bsk_scan_apply", "bsk_scan_last_kernel",
     "bsk_sum_apply_host", "bsk_sum_apply", "bsk_sum_last_kernel",
@@ -134,6 +135,9 @@ def lib():
     L.bsk_band_destroy.argtypes = [_vp]
     L.bsk_band_apply_host.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _vp]
     L.bsk_band_apply.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _vp, _vp]
+    L.bsk_band_absmax.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
+    L.bsk_band_absmax_host.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp]
+    L.bsk_band_apply_fma_host.argtypes = [_vp, ctypes.c_int, _vp, _i64, _i64, _vp]
     L.bsk_band_last_kernel.argtypes = [_vp]
     L.bsk_band_last_kernel.restype = ctypes.c_char_p
     L.bsk_product_create.argtypes = [ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, ctypes.POINTER(_i32p), ctypes.POINTER(_i32p),

@@ -15,6 +15,8 @@ error messages for
     s.insert_knots(newKnots) / s.trim(newDomain) / s.clamp(l, r)  spline.py:1219, :2386, :282
     s.elevate(m) / s.elevate_and_insert_knots(m, newKnots)        spline.py:845-902
     s.differentiate(with_respect_to=0)                            spline.py:772
+    s.remove_knot(iKnot, nLeft, nRight) / s.remove_knots(tol)     spline.py:1812, :1848 (its own statement: reduction.py)
+    s.range_bounds()                                              spline.py:1794
     s.multiply(other, indMap, productType) / dot / cross / scale  spline.py:1585, :821, :641, :2028
     s.transform(matrix), s * x, x * s, s @ x, x @ s, -s, s / x    spline.py:2307, :97-147
     Spline.common_basis(splines, indMap) / s.add / s.subtract     spline.py:308, :149, :2199
@@ -38,6 +40,9 @@ Documented deviations from the reference:
   * mixed float32/float64 inputs are computed in float64;
   * differentiate() of a spline with an interior knot of full multiplicity raises ValueError (the reference
     divides by the zero knot gap and returns inf / nan coefficients);
+  * remove_knot() raises ValueError where an operator weight is not finite (a fixed unknown, nLeft / nRight, whose
+    pivot is zero; the reference returns inf / nan); remove_knots() follows the statement of bspy_amd/reduction.py,
+    not the reference's serial loop, and always returns a new spline;
   * CUDA/HIP torch tensors are accepted as parameters (results stay on the GPU) and
     jacobian() accepts arrays of points (the reference's is single-point).
 """
@@ -283,6 +288,28 @@ class Spline:
         """The spline of the derivative with respect to one variable (reference spline.py:772)."""
         from . import refinement as _refinement
         return _refinement.differentiate(self, with_respect_to, **kwargs)
+
+    # ------------------------------------------------------------------ data reduction (bspy_amd/reduction.py)
+    def range_bounds(self):
+        """[[min, max]] of the coefficients per dependent variable, in the coefficients' dtype (reference
+        _spline_evaluation.py:248)."""
+        from . import reduction as _reduction
+        return _reduction.range_bounds(self)
+
+    def remove_knot(self, iKnot, nLeft=0, nRight=0):
+        """Remove knot iKnot of a curve: (spline, residual) with the least-squares coefficients of the window and the
+        per-component absolute residual (reference _spline_domain.py:452, its messages).  nLeft / nRight coefficients
+        at the ends are kept by exact substitution.  Raises ValueError where an operator weight is not finite."""
+        from . import reduction as _reduction
+        return _reduction.remove_knot(self, iKnot, nLeft, nRight)
+
+    def remove_knots(self, tolerance=1e-14, nLeft=0, nRight=0, **kwargs):
+        """Remove as many knots as the tolerance (relative to max |coefficient| per dependent variable) allows, with a
+        certified bound on the sup-norm error against this spline (the statement in bspy_amd/reduction.py; the
+        reference's signature, spline.py:1848, not its serial loop).  Always returns a new spline.
+        ``_path="device"`` / ``"host"`` pins the path."""
+        from . import reduction as _reduction
+        return _reduction.remove_knots(self, tolerance, nLeft, nRight, **kwargs)
 
     # ------------------------------------------------------------------ products (bspy_amd/product.py)
     def multiply(self, other, indMap=None, productType='S', **kwargs):

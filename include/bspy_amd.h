@@ -240,6 +240,33 @@ bsk_status bsk_band_apply(bsk_band p, bsk_dtype dtype, const void *in, int64_t o
 const char *bsk_band_last_kernel(bsk_band p);
 
 /*
+ * Maxima of a band operator over all lines (Spline.remove_knots: the residual of every interior knot and the error
+ * certificate of a removal; bspy_amd/reduction.py).
+ * Replaces: the trial removal of one knot at a time on a folded spline, each a Givens solve in Python, of
+ * bspy/_spline_domain.py:518.
+ * The data is viewed as in[outer][nIn][inner] as for bsk_band_apply; `groups` divides `outer` and the group of a line is
+ * the leading part of its outer index, g = o / (outer / groups).  minus is null or a buffer of the operator's result
+ * shape [outer][nOut][inner] in the same dtype.  out[groups][nOut] is fp64:
+ *   out[g][j] = max over the lines (o, i) of group g of | round_dtype(sum_t w[j][t] * in[o][first[j] + t][i]) - minus[o][j][i] |
+ * The sum is the chain acc = fma(w[j][t], in[..], acc) from 0 in the order of t in fp64, rounded once to dtype; the
+ * difference and the maximum are taken in fp64.  A NaN anywhere in a row's lines gives +inf for that row.  A maximum is
+ * exact, so the result does not depend on the launch geometry and the host driver and the kernels give the same bits.
+ *   bsk_band_absmax        : device buffers (in, minus, out) on the current device, two launches enqueued on `stream`:
+ *                            band_absmax (inner > 1) or band_absmax_line (inner == 1) write one partial maximum per
+ *                            (workgroup, group, row) into a workspace the handle owns, band_absmax_fold folds them.  No
+ *                            atomics; no workgroup waits for another.  K outside [2, 8] returns BSK_ERR_UNSUPPORTED.
+ *   bsk_band_absmax_host   : host buffers, the same values on the CPU, any K.
+ *   bsk_band_apply_fma_host: bsk_band_apply_host with the sums formed as the fused chain above: the bits of
+ *                            bsk_band_apply (bsk_band_apply_host rounds every product and can differ in the last bit).
+ * bsk_band_last_kernel additionally reports "band_absmax", "band_absmax_line" or "host band_absmax".
+ */
+bsk_status bsk_band_absmax(bsk_band p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, int64_t groups,
+                           const void *minus, double *out, void *stream);
+bsk_status bsk_band_absmax_host(bsk_band p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, int64_t groups,
+                                const void *minus, double *out);
+bsk_status bsk_band_apply_fma_host(bsk_band p, bsk_dtype dtype, const void *in, int64_t outer, int64_t inner, void *out);
+
+/*
  * Products of splines (Spline.multiply, dot, cross, scale by a spline, the * and @ operators; bspy_amd/product.py).
  * Replaces: multiplyAndConvolve's outer product over all variables followed by per-segment Taylor expansions
  * (bspy/_spline_operations.py:318).
