@@ -45,6 +45,9 @@ SYMBOLS = PRODUCT_SYMBOLS + INTERNAL_SYMBOLS
 # compares these with the header, and build() checks that the library exports them
 ROOTS2_SYMBOLS = ("bsk_roots2_flag_host", "bsk_roots2_flag", "bsk_roots2_isolate_host", "bsk_roots2_isolate", "bsk_roots2_merge_host",
                   "bsk_roots2_merge", "bsk_roots2_last_kernel")
+# ... and the family of Spline.zeros3, listed apart for the same reason; tests/test_roots3_host.py compares it with the header
+ROOTS3_SYMBOLS = ("bsk_roots3_flag_host", "bsk_roots3_flag", "bsk_roots3_isolate_host", "bsk_roots3_isolate", "bsk_roots3_merge_host",
+                  "bsk_roots3_merge", "bsk_roots3_last_kernel", "bsk_roots3_walk_bound")
 
 
 class NativeLibraryError(RuntimeError):
@@ -175,16 +178,27 @@ def lib():
     L.bsk_roots2_merge.argtypes = [ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]
     L.bsk_roots2_last_kernel.argtypes = []
     L.bsk_roots2_last_kernel.restype = ctypes.c_char_p
+    grid3 = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]
+    merge3 = [ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]
+    L.bsk_roots3_flag_host.argtypes = grid3 + [_vp, _vp]
+    L.bsk_roots3_flag.argtypes = grid3 + [_vp, _vp, _vp]
+    L.bsk_roots3_isolate_host.argtypes = grid3 + [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.bsk_roots3_isolate.argtypes = grid3 + [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.bsk_roots3_merge_host.argtypes = merge3
+    L.bsk_roots3_merge.argtypes = merge3 + [_vp]
+    L.bsk_roots3_last_kernel.argtypes = []
+    L.bsk_roots3_last_kernel.restype = ctypes.c_char_p
+    L.bsk_roots3_walk_bound.argtypes = []
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
     L.bsk_debug_stage_times.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, _ip]
     L.bsk_debug_fill_lds.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _i64p, _vp]
-    for name in SYMBOLS + ROOTS2_SYMBOLS:
+    for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel"):
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

@@ -36,7 +36,9 @@ class _Lease:
 class ResultPool:
     def __init__(self):
         self._free = []              # touched uint8 arrays, any size
-        self._lock = threading.Lock()
+        # reentrant: a lease's finalizer (_give_back) can run on this thread while empty() holds the lock, when the
+        # garbage collector frees a dead lease during one of empty()'s own allocations
+        self._lock = threading.RLock()
         self.recycled = 0            # statistics (tests, bench)
         self.allocated = 0
 

@@ -407,7 +407,9 @@ def _run_device(rows, plan, mask, scale):
     L = nv.lib()
     K0, K1 = plan.order
     R = slots(K0, K1)
-    B = rows.shape[0]
+    B = mask.shape[0]                                  # systems: the rows come as (2 B, ...), components unfolded
+    if rows.shape[0] != 2 * B:
+        raise ValueError("the rows must hold 2 components per system of the mask")
     dev = rows.device
     with torch.cuda.device(dev):
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -444,6 +444,21 @@ class Spline:
         from . import roots2 as _roots2
         return _roots2.zeros2(self, **kwargs)
 
+    def zeros3(self, **kwargs):
+        """The isolated common zeros of three scalar splines in three variables (nInd == nDep == 3, for example
+        ``surface.subtract(curve)``; the reference reaches them through ``zeros``): a list, sorted by (u, v, w), of length-3
+        arrays (u, v, w) of the knots' dtype and, for every knot cell on which a component vanishes, a tuple
+        ((u0, v0, w0), (u1, v1, w1)).  The three variables are brought to Bezier form by the band operator; cells whose
+        coefficients exclude a zero are rejected by one kernel, every other cell is walked by dyadic subdivision by one
+        wave, a lane per coefficient, and its leaves are polished by Newton steps (few cells: the same arithmetic on the
+        host).  What counts as a zero is stated in bspy_amd/roots3.py.  Results are bitwise reproducible and the same on
+        both paths.  Raises the reference's ValueError for nInd != nDep, a ValueError that names the cell when zeros could
+        not be isolated there or a zero is tangential, NotImplementedError for nInd != 3 or an order outside 2 .. 4.
+        ``_path="device"`` / ``"host"`` pins the path.  ``bspy_amd.roots3.zeros3_batch`` solves many systems on the same
+        knots in one launch sequence."""
+        from . import roots3 as _roots3
+        return _roots3.zeros3(self, **kwargs)
+
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
 

@@ -448,6 +448,65 @@ bsk_status bsk_roots2_merge(int R, const double *roots, int64_t nsys, int64_t nc
 const char *bsk_roots2_last_kernel(void);
 
 /*
+ * Isolated common zeros of three scalar splines in three variables (Spline.zeros3; the statement of what a zero is and of
+ * the arithmetic is in bspy_amd/roots3.py and DESIGN.md section 19).  The family keeps no handle.  The caller brings the
+ * three variables to Bezier form with the band operator: rows[nsys][3][R0][R1][R2] (doubles) holds nsys systems of three
+ * components on the same knots, and cell (i, j, k) is the K0 x K1 x K2 window of the components at first0[i], first1[j],
+ * first2[k]; it covers [breaks0[i], breaks0[i + 1]] x [breaks1[j], breaks1[j + 1]] x [breaks2[k], breaks2[k + 1]].  A
+ * cell's flat index is ((system * nc0 + i) * nc1 + j) * nc2 + k.  A window that leaves the rows, or a flat index that is
+ * no cell, gives no zero instead of a read out of bounds.
+ *   bsk_roots3_flag(_host)   : flags[nsys][nc0][nc1][nc2] (bytes) = 1 unless mask (same shape; a zero cell) is set or a
+ *                              component's K0 K1 K2 Bernstein coefficients are all > 0 or all < 0.
+ *   bsk_roots3_isolate(_host): cand[ncand] (int64, flat indices of the flagged cells, 1 <= ncand < 2^31: no candidates
+ *                              means no call); scale[nsys][3] = max |coefficient| of the component.  Per candidate: the
+ *                              zeros go to roots[ncand][R][3] as (u, v, w), R = min(6 (K0 - 1)(K1 - 1)(K2 - 1), 32), NaN
+ *                              behind the last one; near[ncand][R] (bytes) = 1 for a zero within 2^-20 of a face of its
+ *                              cell; count[ncand] (int32); status[ncand] (bytes): bit 1 = the walk visited more than its
+ *                              bound of nodes (zeros not isolated), bit 2 = more than R zeros, bit 4 = a tangential or
+ *                              singular zero, not reported; nodes[ncand] (int32) = the boxes the walk visited.  One wave
+ *                              (a workgroup of 64 lanes, lane = coefficient of the window) per candidate walks the dyadic
+ *                              boxes of the cell depth first without a stack, 19 halvings per axis, dropping a box when a
+ *                              component's coefficients are strictly of one sign, and polishes a leaf with at most 8
+ *                              Newton steps.
+ *   bsk_roots3_merge(_host)  : which[nnear] (int64, flat indices candidate * R + slot of the zeros with near set,
+ *                              nnear >= 1); table[nsys][nc0][nc1][nc2] (int64) = cumsum(flags) - 1, the candidate of a
+ *                              flagged cell.  keep[ncand][R] (bytes): a lane clears its own byte when one of the 13
+ *                              neighbouring cells of the same system with a lower flat index holds a zero within 2^-20 of
+ *                              the lane's cell widths on all axes, and sets it otherwise; no other byte is written.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1, K2 in 2 .. 4 on
+ *   both sides (BSK_ERR_UNSUPPORTED above).  No atomics, no waiting, no LDS, every loop has a compile-time bound; the host
+ *   drivers and the kernels give the same bits.
+ *   bsk_roots3_last_kernel   : "roots3_flag", "roots3_isolate", "roots3_merge" or the same behind "host ".
+ *   bsk_roots3_walk_bound    : the number of nodes a walk may visit before status bit 1 is set, as compiled.
+ */
+bsk_status bsk_roots3_flag_host(int K0, int K1, int K2, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t R2,
+                                int64_t nc0, int64_t nc1, int64_t nc2, const int32_t *first0, const int32_t *first1,
+                                const int32_t *first2, const uint8_t *mask, uint8_t *flags);
+bsk_status bsk_roots3_flag(int K0, int K1, int K2, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t R2,
+                           int64_t nc0, int64_t nc1, int64_t nc2, const int32_t *first0, const int32_t *first1,
+                           const int32_t *first2, const uint8_t *mask, uint8_t *flags, void *stream);
+bsk_status bsk_roots3_isolate_host(int K0, int K1, int K2, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t R2,
+                                   int64_t nc0, int64_t nc1, int64_t nc2, const int32_t *first0, const int32_t *first1,
+                                   const int32_t *first2, const double *breaks0, const double *breaks1, const double *breaks2,
+                                   const double *scale, const int64_t *cand, int64_t ncand, double *roots, uint8_t *near,
+                                   int32_t *count, uint8_t *status, int32_t *nodes);
+bsk_status bsk_roots3_isolate(int K0, int K1, int K2, const double *rows, int64_t nsys, int64_t R0, int64_t R1, int64_t R2,
+                              int64_t nc0, int64_t nc1, int64_t nc2, const int32_t *first0, const int32_t *first1,
+                              const int32_t *first2, const double *breaks0, const double *breaks1, const double *breaks2,
+                              const double *scale, const int64_t *cand, int64_t ncand, double *roots, uint8_t *near,
+                              int32_t *count, uint8_t *status, int32_t *nodes, void *stream);
+bsk_status bsk_roots3_merge_host(int R, const double *roots, int64_t nsys, int64_t nc0, int64_t nc1, int64_t nc2,
+                                 const double *breaks0, const double *breaks1, const double *breaks2, const int64_t *cand,
+                                 int64_t ncand, const uint8_t *flags, const int64_t *table, const int64_t *which, int64_t nnear,
+                                 uint8_t *keep);
+bsk_status bsk_roots3_merge(int R, const double *roots, int64_t nsys, int64_t nc0, int64_t nc1, int64_t nc2,
+                            const double *breaks0, const double *breaks1, const double *breaks2, const int64_t *cand,
+                            int64_t ncand, const uint8_t *flags, const int64_t *table, const int64_t *which, int64_t nnear,
+                            uint8_t *keep, void *stream);
+const char *bsk_roots3_last_kernel(void);
+int bsk_roots3_walk_bound(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
