@@ -1,0 +1,407 @@
+// Closest points on curves and surfaces (bspy_amd/project.py): the bsk_project_* family.
+//
+// The caller has brought every variable to Bezier form (the band operator of bsk_refine.hpp, once per axis): rows is
+// [ndep, R0, R1] in fp64 and cell (i, j) is the K0 x K1 window of every component at first0[i], first1[j].  A curve is
+// the same with K1 = R1 = nc1 = 1: its axis 1 is never free.  One more band step per axis has sampled every cell:
+// samples is [ndep, M], M = (nc0 g0)(nc1 g1).
+//
+//   project_seed    lane = one query point, its coordinates in registers; grid = (point blocks, chunks of the samples).
+//                   Every lane of a wave needs the same sample at the same time, so the samples are read through
+//                   wave-uniform addresses (kernel arguments, blockIdx and the loop counter only): the compiler turns them
+//                   into scalar loads, one instruction serves the wave and the operand arrives in SGPRs.  No LDS, no
+//                   barrier.  The chunk is walked in tiles of PROJECT_SEED_TILE samples (unrolled, the loads of a tile
+//                   issue together), then sample by sample.  Squared distance: r_0 r_0 + r_1 r_1 (+ r_2 r_2), summed in
+//                   component order, every product and sum rounded on its own; a sample wins when its squared distance is
+//                   strictly below the best so far, so ties go to the lowest index.  Partials (d2, index) per point and
+//                   chunk; (+inf, -1) when nothing is below +inf.
+//   project_newton  lane = one query point.  The prologue reduces the chunk partials in chunk order by the same rule (or
+//                   takes the guess, clamped to the domain), then at most PROJECT_EVALS trips of one loop; every trip is
+//                   one evaluation at a trial parameter t:
+//                     the cell of t by a bisection over the breaks with a trip count given by the launch; local x = (t -
+//                     left) / width; per component S and its first and second local derivatives by de Casteljau in
+//                     registers, the K0 x K1 coefficients read from global memory (they sit in L2); d2 = sum r r,
+//                     G = J^T r, A = J^T J, B = sum r_d Hess S_d, all in local coordinates and summed in component order;
+//                     the trial is taken when it is the first one, when its step is within PROJECT_TRUST of the domain
+//                     width on every axis, when d2 did not grow, or after PROJECT_HALVINGS halvings; otherwise the step
+//                     is halved and tried again;
+//                     a taken trial whose step is within PROJECT_TRUST ends the walk converged when the step is within
+//                     PROJECT_SMALL_STEP of the domain width or not smaller than the small step before it;
+//                     an axis is fixed when the iterate sits on a domain bound and the gradient points outward; all axes
+//                     fixed: converged.  On the free axes the Newton step by Cramer's rule with IEEE division when the
+//                     restricted A + B is positive definite, else the Gauss-Newton step with A, else status bit 4 and stop;
+//                     the local step times the cell's width is the step, the new trial is clamped to the domain.
+//                   Status: 1 evaluation bound reached, 2 the foot point is on a domain bound, 4 singular step or a window
+//                   that leaves the rows, 8 the point is not finite or has no seed (not iterated, NaN out).
+//
+// fp64, no contraction, lerp(s, t, a, b) = s a + t b as in bsk_roots.hpp: one association for the host drivers and the
+// kernels; project.seed_point and project.newton_point state it in Python.  No atomics, no waiting, and every loop has a
+// compile-time or launch-uniform trip bound.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "bsk_roots.hpp"
+
+#pragma clang fp contract(off)
+
+namespace bskproject {
+
+using bskroots::lerp;
+
+constexpr int PROJECT_BLOCK = 256;                  // project_seed
+constexpr int PROJECT_NEWTON_BLOCK = 64;            // one wave: the evaluation may use the whole register file
+constexpr int PROJECT_SEED_TILE = 8;                // samples whose loads issue together
+constexpr int PROJECT_EVALS = 32;                   // evaluations per point
+constexpr int PROJECT_HALVINGS = 20;                // 2^-20 of a clamped step is within PROJECT_TRUST
+constexpr double PROJECT_TRUST = 0x1p-20;           // of the domain width: steps this small are taken as they are
+constexpr double PROJECT_SMALL_STEP = 0x1p-40;      // of the domain width: the next Newton step is below fp64 resolution
+constexpr int PROJECT_MAX_SAMPLES = 8;              // per cell and axis
+constexpr unsigned STATUS_EVALS = 1, STATUS_BOUND = 2, STATUS_SINGULAR = 4, STATUS_SKIPPED = 8;
+
+// ------------------------------------------------------------------------------------------ seed
+template <int NDEP>
+BSK_HD void seed_one(const double *samples, long long M, const double *p, long long m, double &best, int32_t &idx)
+{
+    double acc = 0.0;
+#pragma unroll
+    for (int d = 0; d < NDEP; ++d) {
+        const double r = samples[d * M + m] - p[d];
+        const double rr = r * r;
+        acc = d == 0 ? rr : acc + rr;
+    }
+    if (acc < best) {
+        best = acc;
+        idx = (int32_t)m;
+    }
+}
+
+// the best sample of [begin, end), begin <= end <= M
+template <int NDEP>
+BSK_HD void seed_range(const double *samples, long long M, const double *p, long long begin, long long end, double &best,
+                       int32_t &idx)
+{
+    best = __builtin_inf();
+    idx = -1;
+    long long m = begin;
+    for (; m + PROJECT_SEED_TILE <= end; m += PROJECT_SEED_TILE) {
+#pragma unroll
+        for (int e = 0; e < PROJECT_SEED_TILE; ++e) seed_one<NDEP>(samples, M, p, m + e, best, idx);
+    }
+    for (; m < end; ++m) seed_one<NDEP>(samples, M, p, m, best, idx);
+}
+
+// points: [ndep, npts]; part_d2, part_idx: [nchunks, npts]
+template <int NDEP>
+BSK_HD void seed_lane(const double *samples, long long M, const double *points, long long npts, long long chunk, long long c,
+                      long long lane, double *part_d2, int32_t *part_idx)
+{
+    double p[NDEP];
+#pragma unroll
+    for (int d = 0; d < NDEP; ++d) p[d] = points[d * npts + lane];
+    const long long begin = c * chunk;
+    const long long end = begin + chunk < M ? begin + chunk : M;
+    double best;
+    int32_t idx;
+    seed_range<NDEP>(samples, M, p, begin, end, best, idx);
+    part_d2[c * npts + lane] = best;
+    part_idx[c * npts + lane] = idx;
+}
+
+// ------------------------------------------------------------------------------------------ newton
+// value, first and second derivative of K Bernstein coefficients at x (local coordinate)
+template <int K>
+BSK_HD void eval1(const double *c, double x, double &val, double &d1, double &d2)
+{
+    double b[K];
+    const double s = 1.0 - x;
+#pragma unroll
+    for (int i = 0; i < K; ++i) b[i] = c[i];
+#pragma unroll
+    for (int r = 1; r < K - 2; ++r)
+#pragma unroll
+        for (int i = 0; i < K - r; ++i) b[i] = lerp(s, x, b[i], b[i + 1]);
+    d1 = 0.0;
+    d2 = 0.0;
+    if constexpr (K >= 3) {
+        d2 = (double)((K - 1) * (K - 2)) * ((b[2] - b[1]) - (b[1] - b[0]));
+        b[0] = lerp(s, x, b[0], b[1]);
+        b[1] = lerp(s, x, b[1], b[2]);
+    }
+    if constexpr (K >= 2) {
+        d1 = (double)(K - 1) * (b[1] - b[0]);
+        b[0] = lerp(s, x, b[0], b[1]);
+    }
+    val = b[0];
+}
+
+// The tables of a launch.  rows: [ndep, R0, R1]; first0: [nc0]; first1: [nc1]; breaks0: [nc0 + 1]; breaks1: [nc1 + 1];
+// trips0, trips1: steps of the bisection over the breaks, the bit length of nc - 1.
+struct Tables {
+    const double *rows;
+    long long R0, R1, nc0, nc1;
+    const int32_t *first0, *first1;
+    const double *breaks0, *breaks1;
+    int trips0, trips1, g0, g1;
+};
+
+BSK_HD int bisection_trips(long long nc)
+{
+    int trips = 0;
+    for (long long n = nc - 1; n > 0; n >>= 1) ++trips;
+    return trips;
+}
+
+// the last cell whose left break is <= u (cell 0 for a u below the domain or a NaN): never outside 0 .. nc - 1
+BSK_HD long long find_cell(const double *breaks, long long nc, int trips, double u)
+{
+    long long lo = 0, hi = nc - 1;
+    for (int t = 0; t < trips; ++t) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (breaks[mid] <= u) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+struct Eval {
+    double d2, g0, g1, a00, a01, a11, b00, b01, b11, h0, h1;
+    bool ok;
+};
+
+// everything the iteration needs at (u0, u1), in the local coordinates of the cell that holds it, one component at a time
+template <int NIND, int K0, int K1, int NDEP>
+BSK_HD Eval evaluate(const Tables &T, const double *p, double u0, double u1)
+{
+    Eval e;
+    e.d2 = e.g0 = e.g1 = e.a00 = e.a01 = e.a11 = e.b00 = e.b01 = e.b11 = 0.0;
+    const long long i = find_cell(T.breaks0, T.nc0, T.trips0, u0);
+    const double left0 = T.breaks0[i];
+    e.h0 = T.breaks0[i + 1] - left0;
+    const double x0 = (u0 - left0) / e.h0;
+    long long j = 0;
+    double x1 = 0.0;
+    e.h1 = 1.0;
+    if constexpr (NIND == 2) {
+        j = find_cell(T.breaks1, T.nc1, T.trips1, u1);
+        const double left1 = T.breaks1[j];
+        e.h1 = T.breaks1[j + 1] - left1;
+        x1 = (u1 - left1) / e.h1;
+    }
+    const long long f0 = T.first0[i], f1 = T.first1[j];
+    e.ok = !(f0 < 0 || f0 + K0 > T.R0 || f1 < 0 || f1 + K1 > T.R1);
+    if (!e.ok) return e;
+#pragma unroll
+    for (int d = 0; d < NDEP; ++d) {
+        const double *base = T.rows + (d * T.R0 + f0) * T.R1 + f1;
+        double pv[K0], qv[K0], wv[K0];
+#pragma unroll
+        for (int r = 0; r < K0; ++r) {
+            double line[K1];
+#pragma unroll
+            for (int c = 0; c < K1; ++c) line[c] = base[r * T.R1 + c];
+            eval1<K1>(line, x1, pv[r], qv[r], wv[r]);
+        }
+        double f, fu, fuu;
+        eval1<K0>(pv, x0, f, fu, fuu);
+        const double r = f - p[d];
+        e.d2 = e.d2 + r * r;
+        e.g0 = e.g0 + r * fu;
+        e.a00 = e.a00 + fu * fu;
+        e.b00 = e.b00 + r * fuu;
+        if constexpr (NIND == 2) {
+            double fv, fuv, fvv, unused1, unused2;
+            eval1<K0>(qv, x0, fv, fuv, unused1);
+            eval1<K0>(wv, x0, fvv, unused1, unused2);
+            e.g1 = e.g1 + r * fv;
+            e.a01 = e.a01 + fu * fv;
+            e.a11 = e.a11 + fv * fv;
+            e.b01 = e.b01 + r * fuv;
+            e.b11 = e.b11 + r * fvv;
+        }
+    }
+    return e;
+}
+
+BSK_HD double clamp_to(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+BSK_HD bool is_finite(double x) { return fabs(x) < __builtin_inf(); }
+
+// the local step (dx0, dx1) on the free axes; false: no positive definite matrix to take it from
+BSK_HD bool solve_step(const Eval &e, bool fixed0, bool fixed1, double &dx0, double &dx1)
+{
+    dx0 = 0.0;
+    dx1 = 0.0;
+    if (!fixed0 && !fixed1) {
+        const double h00 = e.a00 + e.b00, h01 = e.a01 + e.b01, h11 = e.a11 + e.b11;
+        double det = h00 * h11 - h01 * h01;
+        if (h00 > 0.0 && det > 0.0) {
+            dx0 = (e.g0 * h11 - h01 * e.g1) / det;
+            dx1 = (h00 * e.g1 - e.g0 * h01) / det;
+            return true;
+        }
+        det = e.a00 * e.a11 - e.a01 * e.a01;
+        if (e.a00 > 0.0 && det > 0.0) {
+            dx0 = (e.g0 * e.a11 - e.a01 * e.g1) / det;
+            dx1 = (e.a00 * e.g1 - e.g0 * e.a01) / det;
+            return true;
+        }
+        return false;
+    }
+    if (!fixed0) {
+        const double h = e.a00 + e.b00;
+        if (h > 0.0) dx0 = e.g0 / h;
+        else if (e.a00 > 0.0) dx0 = e.g0 / e.a00;
+        else return false;
+        return true;
+    }
+    const double h = e.a11 + e.b11;
+    if (h > 0.0) dx1 = e.g1 / h;
+    else if (e.a11 > 0.0) dx1 = e.g1 / e.a11;
+    else return false;
+    return true;
+}
+
+// points: [ndep, npts]; part_d2, part_idx: [nchunks, npts]; guess: [nind, npts] or NULL; uvw: [nind, npts]
+template <int NIND, int K0, int K1, int NDEP>
+BSK_HD void newton_lane(const Tables &T, const double *points, long long npts, const double *part_d2, const int32_t *part_idx,
+                        long long nchunks, const double *guess, long long lane, double *uvw, double *distance, uint8_t *status,
+                        int32_t *steps)
+{
+    double p[NDEP];
+    bool have = true;
+#pragma unroll
+    for (int d = 0; d < NDEP; ++d) {
+        p[d] = points[d * npts + lane];
+        have = have && is_finite(p[d]);
+    }
+    const double lo0 = T.breaks0[0], hi0 = T.breaks0[T.nc0];
+    const double lo1 = NIND == 2 ? T.breaks1[0] : 0.0, hi1 = NIND == 2 ? T.breaks1[T.nc1] : 1.0;
+    double s0 = lo0, s1 = lo1;
+    if (guess) {
+        s0 = guess[lane];
+        if constexpr (NIND == 2) s1 = guess[npts + lane];
+        have = have && is_finite(s0) && is_finite(s1);
+    } else {
+        double best = __builtin_inf();
+        long long idx = -1;
+        for (long long c = 0; c < nchunks; ++c) {
+            const double d = part_d2[c * npts + lane];
+            const long long k = part_idx[c * npts + lane];
+            if (d < best) {
+                best = d;
+                idx = k;
+            }
+        }
+        const long long M1 = T.nc1 * T.g1;
+        if (idx < 0 || idx >= T.nc0 * T.g0 * M1) {
+            have = false;
+        } else {
+            const long long m0 = idx / M1, m1 = idx - m0 * M1;
+            const long long i = m0 / T.g0, a = m0 - i * T.g0;
+            s0 = T.breaks0[i] + (((double)a + 0.5) / (double)T.g0) * (T.breaks0[i + 1] - T.breaks0[i]);
+            if constexpr (NIND == 2) {
+                const long long j = m1 / T.g1, b = m1 - j * T.g1;
+                s1 = T.breaks1[j] + (((double)b + 0.5) / (double)T.g1) * (T.breaks1[j + 1] - T.breaks1[j]);
+            }
+        }
+    }
+    if (!have) {
+        uvw[lane] = __builtin_nan("");
+        if constexpr (NIND == 2) uvw[npts + lane] = __builtin_nan("");
+        distance[lane] = __builtin_nan("");
+        status[lane] = (uint8_t)STATUS_SKIPPED;
+        steps[lane] = 0;
+        return;
+    }
+    const double w0 = hi0 - lo0, w1 = hi1 - lo1;
+    double u0 = clamp_to(s0, lo0, hi0), u1 = clamp_to(s1, lo1, hi1);
+    double t0 = u0, t1 = u1, du0 = 0.0, du1 = 0.0;
+    double f = __builtin_inf(), prev = __builtin_inf();
+    int halvings = 0, n = 0;
+    unsigned st = 0;
+    bool conv = false, stop = false;
+    for (int trip = 0; trip < PROJECT_EVALS && !stop; ++trip) {
+        const Eval e = evaluate<NIND, K0, K1, NDEP>(T, p, t0, t1);
+        ++n;
+        if (!e.ok) {
+            st |= STATUS_SINGULAR;
+            stop = true;
+            continue;
+        }
+        const double rel0 = fabs(t0 - u0) / w0, rel1 = NIND == 2 ? fabs(t1 - u1) / w1 : 0.0;
+        const double last = rel0 > rel1 ? rel0 : rel1;
+        const bool first = trip == 0, small = last <= PROJECT_TRUST;
+        if (!(first || small || halvings == PROJECT_HALVINGS || e.d2 <= f)) {
+            ++halvings;
+            du0 = 0.5 * du0;
+            du1 = 0.5 * du1;
+            t0 = clamp_to(u0 - du0, lo0, hi0);
+            t1 = clamp_to(u1 - du1, lo1, hi1);
+            continue;
+        }
+        u0 = t0;
+        u1 = t1;
+        f = e.d2;
+        bool done = false;
+        if (!first && small) {
+            done = last <= PROJECT_SMALL_STEP || !(last < prev);
+            prev = last;
+        } else {
+            prev = __builtin_inf();
+        }
+        const bool fixed0 = (u0 <= lo0 && e.g0 > 0.0) || (u0 >= hi0 && e.g0 < 0.0);
+        const bool fixed1 = NIND == 1 || (u1 <= lo1 && e.g1 > 0.0) || (u1 >= hi1 && e.g1 < 0.0);
+        if (done || (fixed0 && fixed1)) {
+            conv = true;
+            stop = true;
+            continue;
+        }
+        double dx0, dx1;
+        if (!solve_step(e, fixed0, fixed1, dx0, dx1)) {
+            st |= STATUS_SINGULAR;
+            stop = true;
+            continue;
+        }
+        du0 = dx0 * e.h0;
+        du1 = dx1 * e.h1;
+        halvings = 0;
+        t0 = clamp_to(u0 - du0, lo0, hi0);
+        t1 = clamp_to(u1 - du1, lo1, hi1);
+    }
+    if (!conv && !(st & STATUS_SINGULAR)) st |= STATUS_EVALS;
+    if (u0 <= lo0 || u0 >= hi0 || (NIND == 2 && (u1 <= lo1 || u1 >= hi1))) st |= STATUS_BOUND;
+    uvw[lane] = u0;
+    if constexpr (NIND == 2) uvw[npts + lane] = u1;
+    distance[lane] = sqrt(f);
+    status[lane] = (uint8_t)st;
+    steps[lane] = n;
+}
+
+#ifdef __HIPCC__
+template <int NDEP>
+__global__ __launch_bounds__(PROJECT_BLOCK) void project_seed(const double *__restrict__ samples, long long M,
+                                                             const double *__restrict__ points, long long npts, long long chunk,
+                                                             double *__restrict__ part_d2, int32_t *__restrict__ part_idx)
+{
+    const long long gid = (long long)blockIdx.x * PROJECT_BLOCK + threadIdx.x;
+    if (gid >= npts) return;
+    seed_lane<NDEP>(samples, M, points, npts, chunk, (long long)blockIdx.y, gid, part_d2, part_idx);
+}
+
+template <int NIND, int K0, int K1, int NDEP>
+__global__ __launch_bounds__(PROJECT_NEWTON_BLOCK) void project_newton(Tables T, const double *__restrict__ points, long long npts,
+                                                                      const double *__restrict__ part_d2,
+                                                                      const int32_t *__restrict__ part_idx, long long nchunks,
+                                                                      const double *__restrict__ guess, double *__restrict__ uvw,
+                                                                      double *__restrict__ distance, uint8_t *__restrict__ status,
+                                                                      int32_t *__restrict__ steps)
+{
+    const long long gid = (long long)blockIdx.x * PROJECT_NEWTON_BLOCK + threadIdx.x;
+    if (gid >= npts) return;
+    newton_lane<NIND, K0, K1, NDEP>(T, points, npts, part_d2, part_idx, nchunks, guess, gid, uvw, distance, status, steps);
+}
+#endif
+
+}  // namespace bskproject

@@ -459,6 +459,21 @@ class Spline:
         from . import roots3 as _roots3
         return _roots3.zeros3(self, **kwargs)
 
+    def project(self, points, guess=None, samples=None, **kwargs):
+        """The closest point of the spline to each of N query points (an extension: the reference has no counterpart).
+        ``points``: (nDep, *shape), NumPy float32 / float64 or a torch CUDA tensor of those types.  Returns ``(uvw,
+        distance)``: the parameters (nInd, *shape) in the knots' dtype and the Euclidean distances (*shape) in float64;
+        CUDA in gives CUDA out.  Curves (nInd 1) of order 2 .. 6 and surfaces (nInd 2) of orders 2 .. 4, nDep 2 or 3;
+        anything else raises NotImplementedError.  Every knot cell is sampled ``samples`` times per axis (default: the
+        order of the axis; 1 .. 8), the nearest sample of a point is found by brute force, one lane per point, and refined
+        by Newton steps on the squared distance; ``guess`` (nInd, *shape) takes the place of the search.  The result is the
+        local minimiser reached from the nearest sample: the closest point whenever that sample lies in its basin; it is
+        NOT certified global.  What is computed is stated in bspy_amd/project.py; results are bitwise reproducible and
+        the same on both paths.  One RuntimeWarning when a point did not converge (bspy_amd.project.project_batch returns
+        the status of every point).  ``_path="device"`` / ``"host"`` pins the path."""
+        from . import project as _project
+        return _project.project(self, points, guess=guess, samples=samples, **kwargs)
+
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
 

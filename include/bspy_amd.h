@@ -507,6 +507,45 @@ const char *bsk_roots3_last_kernel(void);
 int bsk_roots3_walk_bound(void);
 
 /*
+ * Closest points on curves and surfaces (Spline.project; the statement of the seed, of the Newton iteration and of the
+ * arithmetic is in bspy_amd/project.py and DESIGN.md section 20).  The family keeps no handle.  The caller brings every
+ * variable to Bezier form with the band operator: rows[ndep][R0][R1] (doubles; a curve has R1 = K1 = nc1 = g1 = 1,
+ * first1 = {0} and breaks1 = {0, 1}), cell (i, j) is the K0 x K1 window of every component at first0[i], first1[j] and
+ * covers [breaks0[i], breaks0[i + 1]] x [breaks1[j], breaks1[j + 1]].  One more band step per variable gives the sample
+ * grid samples[ndep][nsamples], nsamples = (nc0 g0)(nc1 g1): flat sample (i g0 + a)(nc1 g1) + (j g1 + b) lies at the local
+ * coordinates ((a + 1/2) / g0, (b + 1/2) / g1) of cell (i, j).  points[ndep][npts] are the query points.
+ *   seed   : the samples are cut into nchunks = ceil(nsamples / chunk) ranges of `chunk` samples, nchunks <= 65535.
+ *            part_d2[nchunks][npts] (doubles) and part_idx[nchunks][npts] (int32) receive, per point and range, the
+ *            smallest squared distance (summed in component order, every product and sum rounded on its own) and the flat
+ *            index of the first sample that has it; +inf and -1 where no sample's squared distance is below +inf (a point
+ *            with a NaN or an infinite coordinate).
+ *   newton : per point the partials are reduced in range order by the same rule (guess == NULL), or the start is
+ *            guess[nind][npts] clamped to the domain.  Then Newton on |S(u) - p|^2 / 2 as project.newton_point states it.
+ *            uvw[nind][npts] and distance[npts] (doubles), status[npts] (bytes: 1 evaluation bound reached, 2 foot point
+ *            on a domain bound, 4 singular step or a window that leaves the rows, 8 point not finite or no seed:
+ *            not iterated, NaN out) and steps[npts] (int32, evaluations made).
+ *   nind = 1: K0 in 2 .. 6, K1 = 1; nind = 2: K0, K1 in 2 .. 4; ndep = 2 or 3; anything else is BSK_ERR_UNSUPPORTED.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`.  No atomics, no waiting,
+ *   every loop has a compile-time or launch-uniform bound; the host drivers and the kernels give the same bits.
+ *   The name of the last call: "project_seed", "project_newton" or the same behind "host ".
+ */
+bsk_status bsk_project_seed_host(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts,
+                                 int64_t chunk, double *part_d2, int32_t *part_idx);
+bsk_status bsk_project_seed(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts, int64_t chunk,
+                            double *part_d2, int32_t *part_idx, void *stream);
+bsk_status bsk_project_newton_host(int nind, int K0, int K1, int ndep, const double *rows, int64_t R0, int64_t R1, int64_t nc0,
+                                   int64_t nc1, const int32_t *first0, const int32_t *first1, const double *breaks0,
+                                   const double *breaks1, int g0, int g1, const double *points, int64_t npts,
+                                   const double *part_d2, const int32_t *part_idx, int64_t nchunks, const double *guess,
+                                   double *uvw, double *distance, uint8_t *status, int32_t *steps);
+bsk_status bsk_project_newton(int nind, int K0, int K1, int ndep, const double *rows, int64_t R0, int64_t R1, int64_t nc0,
+                              int64_t nc1, const int32_t *first0, const int32_t *first1, const double *breaks0,
+                              const double *breaks1, int g0, int g1, const double *points, int64_t npts, const double *part_d2,
+                              const int32_t *part_idx, int64_t nchunks, const double *guess, double *uvw, double *distance,
+                              uint8_t *status, int32_t *steps, void *stream);
+const char *bsk_project_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
