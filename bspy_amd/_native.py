@@ -37,6 +37,7 @@ PRODUCT_SYMBOLS = (
     "bsk_sum_apply_host", "bsk_sum_apply", "bsk_sum_last_kernel",
     "bsk_roots_extract_host", "bsk_roots_flag_host", "bsk_roots_flag", "bsk_roots_isolate_host", "bsk_roots_isolate", "bsk_roots_last_kernel",
     "bsk_project_seed_host", "bsk_project_seed", "bsk_project_newton_host", "bsk_project_newton", "bsk_project_last_kernel",
+    "bsk_contour_flag_host", "bsk_contour_flag", "bsk_contour_march_host", "bsk_contour_march", "bsk_contour_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -198,6 +199,14 @@ def lib():
     L.bsk_project_newton.argtypes = newton + [_vp]
     L.bsk_project_last_kernel.argtypes = []
     L.bsk_project_last_kernel.restype = ctypes.c_char_p
+    grid_c = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]
+    march_c = grid_c + [_vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _vp, _vp, _vp, _vp]
+    L.bsk_contour_flag_host.argtypes = grid_c + [_vp, _vp]
+    L.bsk_contour_flag.argtypes = grid_c + [_vp, _vp, _vp]
+    L.bsk_contour_march_host.argtypes = march_c
+    L.bsk_contour_march.argtypes = march_c + [_vp]
+    L.bsk_contour_last_kernel.argtypes = []
+    L.bsk_contour_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -207,7 +216,7 @@ def lib():
     for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel"):
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

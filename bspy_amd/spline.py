@@ -474,6 +474,19 @@ class Spline:
         from . import project as _project
         return _project.project(self, points, guess=guess, samples=samples, **kwargs)
 
+    def contours(self, tolerance=None, depth=None, **kwargs):
+        """The level curves {f = 0} of a scalar spline in two variables (nInd == 2, nDep == 1; reference spline.py
+        ``contours``, whose other shapes are not built): a list of curves (nInd 1, nDep 2, on [0, 1], order 4, f >= 0 on
+        their left), one per connected piece, a closed piece with equal end points, and a tuple ((u0, v0), (u1, v1)) for
+        every knot cell on which f vanishes; sorted by their first vertex.  Every knot cell is marched on a lattice of
+        2^depth x 2^depth leaves (depth 0 .. 8; default 4, or chosen from ``tolerance``, which is also the tolerance of the
+        fit): the contour is decided on that lattice, features smaller than a leaf are missed without a flag and nothing is
+        certified; what is computed is stated in bspy_amd/contours.py.  Results are bitwise reproducible and the same on
+        both paths.  ``_path="device"`` / ``"host"`` pins the path.  ``bspy_amd.contours.trace_batch`` traces many fields
+        or many levels of one field in one launch sequence and returns the raw polylines."""
+        from . import contours as _contours
+        return _contours.contours(self, tolerance=tolerance, depth=depth, **kwargs)
+
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
 

@@ -546,6 +546,48 @@ bsk_status bsk_project_newton(int nind, int K0, int K1, int ndep, const double *
 const char *bsk_project_last_kernel(void);
 
 /*
+ * Level curves {f = 0} of scalar splines in two variables (Spline.contours; the statement of the lattice, the vertices
+ * and the arithmetic is in bspy_amd/contours.py and DESIGN.md section 21).  The family keeps no handle.  The caller brings
+ * both variables to Bezier form with the band operator: rows[nrows][R0][R1] (doubles), cell (i, j), i < nc0, j < nc1, is
+ * the K0 x K1 window at first0[i], first1[j] and covers [breaks0[i], breaks0[i + 1]] x [breaks1[j], breaks1[j + 1]]; no
+ * knot is a jump, so adjacent cells share their end row or column.  There are nfields fields: field b is rows[b]
+ * (levels NULL, nrows == nfields) or rows[0] - levels[b] (nrows == 1); scale[nfields] = max |coefficient| of the field.
+ * A cell's flat index is (field * nc0 + i) * nc1 + j.  A window that leaves the rows, or a flat index that is no cell,
+ * gives no segment instead of a read out of bounds.
+ *   bsk_contour_flag(_host) : zero[nfields][nc0][nc1] (bytes) = 1 where every coefficient of the cell is below scale eps;
+ *                             cand (same shape) = 1 unless the cell is a zero cell or its coefficients are all above tau
+ *                             or all below -tau, tau = 32 (K0 + K1) eps scale.
+ *   bsk_contour_march(_host): cand[ncand] (int64, flat indices of the flagged cells, ncand >= 1).  Every cell carries
+ *                             2^depth x 2^depth leaves, depth in 0 .. 8; lane = candidate * 4^split + top box, split in
+ *                             0 .. depth.  emit == 0: counts[lanes] (int32) = the segments of the lane, lane_status[lanes]
+ *                             (bytes): bit 1 = a leaf with four crossings.  emit != 0: offsets[lanes] (int64, the
+ *                             exclusive sum of counts), total = the sum (>= 1: no segments means no call); segment n is
+ *                             keys[n][2] (int64 lattice-edge keys of its two vertices, f >= 0 on the left from the first to
+ *                             the second) and xy[n][4] = (u, v) of both.  Pointers of the other pass may be NULL.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1 in 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above).  No atomics, no waiting, every loop has a compile-time bound; the host drivers and the
+ *   kernels give the same bits, and the segments do not depend on split.
+ *   bsk_contour_last_kernel : "contour_flag", "contour_march count", "contour_march emit" or the same behind "host ".
+ */
+bsk_status bsk_contour_flag_host(int K0, int K1, const double *rows, int64_t nrows, int64_t R0, int64_t R1, int64_t nc0,
+                                 int64_t nc1, const int32_t *first0, const int32_t *first1, const double *levels,
+                                 int64_t nfields, const double *scale, uint8_t *cand, uint8_t *zero);
+bsk_status bsk_contour_flag(int K0, int K1, const double *rows, int64_t nrows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                            const int32_t *first0, const int32_t *first1, const double *levels, int64_t nfields,
+                            const double *scale, uint8_t *cand, uint8_t *zero, void *stream);
+bsk_status bsk_contour_march_host(int K0, int K1, const double *rows, int64_t nrows, int64_t R0, int64_t R1, int64_t nc0,
+                                  int64_t nc1, const int32_t *first0, const int32_t *first1, const double *levels,
+                                  int64_t nfields, const double *scale, const double *breaks0, const double *breaks1,
+                                  const int64_t *cand, int64_t ncand, int depth, int split, int emit, const int64_t *offsets,
+                                  int64_t total, int32_t *counts, uint8_t *lane_status, int64_t *keys, double *xy);
+bsk_status bsk_contour_march(int K0, int K1, const double *rows, int64_t nrows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                             const int32_t *first0, const int32_t *first1, const double *levels, int64_t nfields,
+                             const double *scale, const double *breaks0, const double *breaks1, const int64_t *cand,
+                             int64_t ncand, int depth, int split, int emit, const int64_t *offsets, int64_t total,
+                             int32_t *counts, uint8_t *lane_status, int64_t *keys, double *xy, void *stream);
+const char *bsk_contour_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.
