@@ -1,0 +1,305 @@
+"""
+What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``) share, written once: the path switch, the
+host band loop, the per-axis Bezier plan, the zero-cell table, and two backends, ``Host`` (NumPy, the ``*_host`` entry
+points) and ``Device`` (torch CUDA tensors, the kernels on the current stream), on which a driver is written once.
+
+A driver is a function of a backend: it allocates with ``be.empty``, hands ``be.ptr(a)`` to ``be.call(name, ...)`` and uses
+the few array operations below.  The families differ in their kernels and in the plain-Python statement that says what a
+kernel computes; those stay in their modules.  ``isolate_cells`` (flag, isolate, merge) and ``collect`` are the drivers of
+``zeros2_batch`` and ``zeros3_batch``.
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from . import _native as nv
+from . import refinement
+
+EPS = float(np.finfo(np.float64).eps)
+
+
+def is_torch(a):
+    return type(a).__module__.startswith("torch")
+
+
+def pick_path(path, forced):
+    """``_path`` of a call, else the module's ``FORCE_PATH``."""
+    path = path if path is not None else forced
+    if path not in (None, "device", "host"):
+        raise ValueError("_path must be None, 'device' or 'host'")
+    return path
+
+
+def band_host(data, steps, log):
+    """NumPy (M, ...) float64 through band steps [(axis, first, w)] in the order the device path takes them, each summed as
+    the band kernels sum it (``bsk_roots_extract_host`` on the lines of that axis); ``log`` receives one entry per step."""
+    L = nv.lib()
+    for axis, first, w in refinement._ordered(steps, data.shape):
+        first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
+        lines = np.ascontiguousarray(np.moveaxis(data, axis, -1))
+        out = np.empty(lines.shape[:-1] + (len(first),), np.float64)
+        nv.check(L.bsk_roots_extract_host(w.shape[1], lines.shape[-1], len(first), first.ctypes.data, w.ctypes.data,
+                                          lines.ctypes.data, lines.size // lines.shape[-1], out.ctypes.data))
+        log.append(L.bsk_roots_last_kernel().decode())
+        data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
+    return data
+
+
+# ------------------------------------------------------------------------------------------ plans and tables
+class BezierPlan:
+    """Bezier extraction of one variable: ``steps`` (band steps on axis 1; empty when the knots are in Bezier form
+    already), ``breaks`` (the distinct knots of the domain, in the knots' dtype), ``first`` (where span s starts in the
+    extracted row), ``rowlen``, and ``cell`` (the knot cell of span s in the spline's own knots)."""
+
+    def __init__(self, order, knots):
+        k, t = int(order), knots
+        n = len(t) - k
+        lo, hi = t[k - 1], t[n]
+        # merged knots as refinement.merged_knots forms them (new knots behind old ones of the same value), vectorised:
+        # every distinct knot of the domain is raised to K - 1, the two ends to K
+        values, counts = np.unique(t, return_counts=True)
+        want = np.where((values == lo) | (values == hi), k, np.maximum(k - 1, counts))
+        add = np.where((values >= lo) & (values <= hi), want - counts, 0)
+        merged, origin = t, np.arange(len(t))
+        if add.any():
+            both = np.concatenate((t, np.repeat(values, add)))
+            rank = np.argsort(both, kind="stable")
+            merged, origin = both[rank], np.where(rank < len(t), rank, -1)
+        row0 = int(np.searchsorted(merged, lo))
+        row1 = int(np.searchsorted(merged, hi))
+        self.steps = []
+        if merged is not t or (row0, row1) != (0, n):
+            self.steps = [(1, *refinement.refine_map(t, k, merged, 0, rows=slice(row0, row1), origin=origin))]
+        bezier = merged[row0:row1 + k]
+        self.order = k
+        self.breaks = np.unique(bezier)
+        self.nspans = len(self.breaks) - 1
+        self.first = (np.searchsorted(bezier, self.breaks[:-1], "right") - k).astype(np.int32)
+        self.rowlen = len(bezier) - k
+        self.cell = np.clip(np.searchsorted(t, self.breaks[:-1], "right") - 1, k - 1, n - 1)
+        self.margin = math.sqrt(EPS) * (float(hi) - float(lo))
+
+
+class TensorPlan:
+    """Bezier extraction of every variable: one ``BezierPlan`` per axis and the band steps on the axes 1 .. nInd of a
+    tensor (M, *nCoef)."""
+
+    def __init__(self, order, knots):
+        self.nind = len(order)
+        self.axes = [BezierPlan(order[d], knots[d]) for d in range(self.nind)]
+        self.order = tuple(int(k) for k in order)
+        self.steps = [(d + 1, first, w) for d in range(self.nind) for _, first, w in self.axes[d].steps]
+        self.breaks = [p.breaks for p in self.axes]
+        self.first = [p.first for p in self.axes]
+        self.rowlen = [p.rowlen for p in self.axes]
+        self.ncells = [p.nspans for p in self.axes]
+
+
+def zero_cells(small, plan):
+    """small: bool (B, nDep, *nCoef), |coefficient| < S_d eps.  -> bool (B, *ncells): all K0 x ... coefficients of the cell
+    are small, for any component."""
+    total = small.astype(np.int64)
+    for a, K in enumerate(plan.order):                                   # windowed sums, one axis at a time
+        run = np.concatenate((np.zeros_like(np.take(total, [0], axis=a + 2)), np.cumsum(total, axis=a + 2)), axis=a + 2)
+        hi = plan.axes[a].cell + 1
+        total = np.take(run, hi, axis=a + 2) - np.take(run, hi - K, axis=a + 2)
+    return (total == int(np.prod(plan.order))).any(axis=1)
+
+
+# ------------------------------------------------------------------------------------------ the backends
+class Host:
+    """NumPy arrays and the ``*_host`` entry points."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+    def empty(self, shape, dtype):
+        return np.empty(shape, dtype)
+
+    def zeros(self, shape, dtype):
+        return np.zeros(shape, dtype)
+
+    def put(self, a, dtype):
+        return np.ascontiguousarray(a, dtype)
+
+    def get(self, a):
+        return a
+
+    def ptr(self, a):
+        return None if a is None else a.ctypes.data
+
+    def code(self, a):
+        return nv.dtype_code(a.dtype)
+
+    def cast(self, a, dtype):
+        return a.astype(dtype)
+
+    def nonzero(self, a):
+        return np.flatnonzero(a).astype(np.int64)
+
+    def cumsum(self, a):
+        return np.cumsum(a, dtype=np.int64)
+
+    def isnan(self, a):
+        return np.isnan(a)
+
+    def amax(self, a, axes):
+        return a.max(axis=axes)
+
+    def sum(self, a, axis):
+        return a.sum(axis=axis)
+
+    def repeat(self, a, n):
+        return np.repeat(a, n)
+
+    def lexsort(self, columns):
+        return np.lexsort(columns)
+
+    def searchsorted(self, a, n):
+        return np.searchsorted(a, np.arange(n)).astype(np.int64)
+
+    def call(self, name, *args):
+        nv.check(getattr(nv.lib(), name + "_host")(*args))
+
+
+class Device:
+    """The same on contiguous torch CUDA tensors of ``dev``, the kernels on the stream that is current on entry."""
+
+    def __init__(self, dev):
+        import torch
+        self.torch, self.dev = torch, dev
+
+    def __enter__(self):
+        self._guard = self.torch.cuda.device(self.dev)
+        self._guard.__enter__()
+        self.stream = ctypes.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+        return self
+
+    def __exit__(self, *exc):
+        return self._guard.__exit__(*exc)
+
+    def _dtype(self, dtype):
+        return getattr(self.torch, np.dtype(dtype).name)
+
+    def empty(self, shape, dtype):
+        return self.torch.empty(shape, dtype=self._dtype(dtype), device=self.dev)
+
+    def zeros(self, shape, dtype):
+        return self.torch.zeros(shape, dtype=self._dtype(dtype), device=self.dev)
+
+    def put(self, a, dtype):
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.dev)
+
+    def get(self, a):
+        return a.cpu().numpy()
+
+    def ptr(self, a):
+        return None if a is None else a.data_ptr()
+
+    def code(self, a):
+        return nv.BSK_F32 if a.dtype == self.torch.float32 else nv.BSK_F64
+
+    def cast(self, a, dtype):
+        return a.to(self._dtype(dtype)).contiguous()
+
+    def nonzero(self, a):
+        return self.torch.nonzero(a.reshape(-1)).reshape(-1)             # int64, in index order
+
+    def cumsum(self, a):
+        return self.torch.cumsum(a, 0, dtype=self.torch.int64)
+
+    def isnan(self, a):
+        return self.torch.isnan(a)
+
+    def amax(self, a, axes):
+        return a.amax(dim=axes)
+
+    def sum(self, a, axis):
+        return a.sum(dim=axis)
+
+    def repeat(self, a, n):
+        return self.torch.repeat_interleave(a, n) if is_torch(n) else a[:, None].expand(-1, n).reshape(-1)
+
+    def lexsort(self, columns):
+        order = self.torch.argsort(columns[0], stable=True)
+        for column in columns[1:]:
+            order = order[self.torch.argsort(column[order], stable=True)]
+        return order
+
+    def searchsorted(self, a, n):
+        return self.torch.searchsorted(a.contiguous(), self.torch.arange(n, device=self.dev))
+
+    def call(self, name, *args):
+        nv.check(getattr(nv.lib(), name)(*args, self.stream))
+
+
+# ------------------------------------------------------------------------------------------ the drivers of zeros2 and zeros3
+def isolate_cells(be, prefix, rows, plan, mask, scale, R, log):
+    """Flag the cells, isolate the zeros of the candidates, merge the ones near a cell boundary: the entry points
+    ``prefix`` + ``_flag``, ``_isolate``, ``_merge`` for a plan of any number of axes n.  rows: float64 in Bezier form,
+    the backend's contiguous array; mask: NumPy (B, *ncells); scale: float64 (B, n), the backend's; R: the slots per cell.
+    -> dict of flags, cand, roots (ncand, R, n), near, count, status, nodes, keep, the backend's arrays; ``log`` receives
+    what ran.  No candidates: the last two launches are skipped; no zero near a boundary: the last one is."""
+    last = getattr(nv.lib(), prefix + "_last_kernel")
+
+    def run(name, *args):
+        be.call(prefix + name, *args)
+        log.append(last().decode())
+
+    B = mask.shape[0]
+    if int(np.prod(rows.shape)) != B * plan.nind * int(np.prod(plan.rowlen)):
+        raise ValueError(f"the rows must hold {plan.nind} components per system of the mask")
+    with be:
+        first = [be.put(f, np.int32) for f in plan.first]
+        grid = plan.order + (be.ptr(rows), B) + tuple(plan.rowlen) + tuple(plan.ncells) + tuple(be.ptr(f) for f in first)
+        mask = be.put(mask, np.uint8)
+        flags = be.empty(mask.shape, np.uint8)
+        run("_flag", *grid, be.ptr(mask), be.ptr(flags))
+        cand = be.nonzero(flags)
+        n = len(cand)
+        out = dict(flags=flags, cand=cand, roots=be.empty((n, R, plan.nind), np.float64), near=be.empty((n, R), np.uint8),
+                   count=be.empty(n, np.int32), status=be.empty(n, np.uint8), nodes=be.empty(n, np.int32))
+        if n:
+            breaks = [be.put(b, np.float64) for b in plan.breaks]
+            run("_isolate", *grid, *map(be.ptr, breaks), be.ptr(scale), be.ptr(cand), n, be.ptr(out["roots"]), be.ptr(out["near"]),
+                be.ptr(out["count"]), be.ptr(out["status"]), be.ptr(out["nodes"]))
+        keep = be.cast(~be.isnan(out["roots"][:, :, 0]), np.uint8)
+        which = be.nonzero(out["near"])
+        if len(which):
+            table = be.cumsum(flags.reshape(-1)) - 1
+            run("_merge", R, be.ptr(out["roots"]), B, *plan.ncells, *map(be.ptr, breaks), be.ptr(cand), n, be.ptr(flags), be.ptr(table),
+                be.ptr(which), len(which), be.ptr(keep))
+        out["keep"] = keep
+    return out
+
+
+def collect(be, plan, kdtype, B, R=0, res=None, mask=None, numpy_out=True):
+    """The result of ``zeros2_batch`` / ``zeros3_batch`` from what ``isolate_cells`` returned: (values, offsets, cells,
+    status).  The kept zeros sorted by (system, u, v, ...) and rounded to ``kdtype``, where each system starts, one row
+    (system, u0, u1, v0, v1, ...) per zero cell of ``mask`` and the status bits per cell; ``numpy_out`` brings the backend's
+    arrays to the host.  B == 0: the empty result."""
+    n, nc = plan.nind, tuple(plan.ncells)
+    if B == 0:
+        return be.empty((0, n), kdtype), be.zeros(1, np.int64), np.empty((0, 2 * n + 1)), be.zeros((0,) + nc, np.uint8)
+    ncell = int(np.prod(nc))
+    kept = be.cast(res["keep"].reshape(-1), bool)
+    system = be.repeat(res["cand"] // ncell, R)[kept]
+    values = res["roots"].reshape(-1, n)[kept]
+    order = be.lexsort([values[:, a] for a in reversed(range(n))] + [system])
+    values = be.cast(values[order], kdtype)
+    offsets = be.searchsorted(system[order], B + 1)
+    status = be.zeros(B * ncell, np.uint8)
+    status[res["cand"]] = res["status"]
+    status = status.reshape((B,) + nc)
+    if numpy_out:
+        values, offsets, status = be.get(values), be.get(offsets), be.get(status)
+    at = np.argwhere(mask)
+    cols = [at[:, 0].astype(np.float64)]
+    for a, b in enumerate(plan.breaks):
+        b = np.asarray(b, np.float64)
+        cols += [b[at[:, a + 1]], b[at[:, a + 1] + 1]]
+    return values, offsets, np.stack(cols, axis=1).reshape(-1, 2 * n + 1), status

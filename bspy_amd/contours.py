@@ -69,14 +69,12 @@ farther from the curve.  (Interpolating all vertices is not an option: vertices 
 ``_path="device" | "host"`` (or ``contours.FORCE_PATH``) pins the path; ``contours.LAST_PATHS`` lists what the last call
 ran.
 """
-import ctypes
-
 import numpy as np
 
+from . import _cells
 from . import _native as nv
 from . import refinement
 from . import roots
-from . import roots2
 
 # Leaves (fields x cells x 4^depth) from which the device path is taken: read off the table of tools/contours_time.py on an
 # MI355X (DESIGN.md section 21): bicubic, depth 4, 1024 leaves 0.85 ms on the host against 1.2 ms, 4096 leaves 1.36 against 1.26.
@@ -330,29 +328,13 @@ def link(keys, field, B):
 
 
 # ------------------------------------------------------------------------------------------ the launches
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
-
-
 def _last():
     return nv.lib().bsk_contour_last_kernel().decode()
 
 
 def extract_host(data, plan):
-    """NumPy (M, n0, n1) float64 -> (M, R0, R1) in Bezier form, as ``roots2.extract_host`` (the band steps in the order of
-    the device path, each summed as the band kernels sum it)."""
-    for axis, first, w in refinement._ordered(plan.steps, data.shape):
-        first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
-        lines = np.ascontiguousarray(np.moveaxis(data, axis, -1))
-        out = np.empty(lines.shape[:-1] + (len(first),), np.float64)
-        nv.check(nv.lib().bsk_roots_extract_host(w.shape[1], lines.shape[-1], len(first), first.ctypes.data, w.ctypes.data,
-                                                 lines.ctypes.data, lines.size // lines.shape[-1], out.ctypes.data))
-        LAST_PATHS.append(roots._last())
-        data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
-    return data
+    """NumPy (M, n0, n1) float64 -> (M, R0, R1) in Bezier form (``_cells.band_host``)."""
+    return _cells.band_host(data, plan.steps, LAST_PATHS)
 
 
 def _grid(plan, rows, ptr, levels, B, scale, first0, first1):
@@ -361,93 +343,55 @@ def _grid(plan, rows, ptr, levels, B, scale, first0, first1):
             None if levels is None else ptr(levels), B, ptr(scale))
 
 
-def _run_host(rows, plan, levels, scale, depth, split):
-    """rows: NumPy float64 (nrows, R0, R1) in Bezier form; levels: float64 (B) or None; scale: float64 (B).  -> dict of
-    cand, zero (B, nc0, nc1), keys (n, 2), xy (n, 4), field (n), status (B, nc0, nc1), split."""
-    L = nv.lib()
-    B = len(scale)
-    nc0, nc1 = plan.ncells
-    rows, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(scale, np.float64)
-    levels = None if levels is None else np.ascontiguousarray(levels, np.float64)
-    first0, first1 = plan.first
-    grid = _grid(plan, rows, lambda a: a.ctypes.data, levels, B, scale, first0, first1)
-    cand, zero = np.empty((B, nc0, nc1), np.uint8), np.empty((B, nc0, nc1), np.uint8)
-    nv.check(L.bsk_contour_flag_host(*grid, cand.ctypes.data, zero.ctypes.data))
-    LAST_PATHS.append(_last())
-    idx = np.flatnonzero(cand).astype(np.int64)
-    n = len(idx)
-    P = split_of(n, depth) if split is None else int(split)
-    out = dict(cand=cand, zero=zero, keys=np.empty((0, 2), np.int64), xy=np.empty((0, 4), np.float64), field=np.empty(0, np.int64),
-               status=np.zeros((B, nc0, nc1), np.uint8), split=P)
-    if not n:
-        return out
-    breaks0, breaks1 = (np.ascontiguousarray(b, np.float64) for b in plan.breaks)
-    lanes = n << (2 * P)
-    counts, lane_status = np.empty(lanes, np.int32), np.empty(lanes, np.uint8)
-    march = grid + (breaks0.ctypes.data, breaks1.ctypes.data, idx.ctypes.data, n, depth, P)
-    nv.check(L.bsk_contour_march_host(*march, 0, None, 0, counts.ctypes.data, lane_status.ctypes.data, None, None))
-    LAST_PATHS.append(_last())
-    out["status"].reshape(-1)[idx] = lane_status.reshape(n, -1).max(axis=1)
-    ends = np.cumsum(counts, dtype=np.int64)
-    total = int(ends[-1])
-    if not total:
-        return out
-    offsets = np.ascontiguousarray(ends - counts)
-    keys, xy = np.empty((total, 2), np.int64), np.empty((total, 4), np.float64)
-    nv.check(L.bsk_contour_march_host(*march, 1, offsets.ctypes.data, total, None, None, keys.ctypes.data, xy.ctypes.data))
-    LAST_PATHS.append(_last())
-    out.update(keys=keys, xy=xy, field=np.repeat(idx // (nc0 * nc1), counts.reshape(n, -1).sum(axis=1)))
-    return out
-
-
-def _run_device(rows, plan, levels, scale, depth, split):
-    """The same with contiguous torch CUDA tensors; every array of the result is a CUDA tensor."""
-    import torch
-    L = nv.lib()
+def _run(be, rows, plan, levels, scale, depth, split):
+    """rows: float64 (nrows, R0, R1) in Bezier form; levels: float64 (B) or None; scale: float64 (B): the backend's
+    contiguous arrays.  -> dict of cand, zero (B, nc0, nc1), keys (n, 2), xy (n, 4), field (n), status (B, nc0, nc1), the
+    backend's, and split."""
     B = int(scale.shape[0])
     nc0, nc1 = plan.ncells
-    dev = rows.device
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        first0, first1 = (torch.from_numpy(f).to(dev) for f in plan.first)
-        grid = _grid(plan, rows, lambda a: a.data_ptr(), levels, B, scale, first0, first1)
-        cand = torch.empty((B, nc0, nc1), dtype=torch.uint8, device=dev)
-        zero = torch.empty((B, nc0, nc1), dtype=torch.uint8, device=dev)
-        nv.check(L.bsk_contour_flag(*grid, cand.data_ptr(), zero.data_ptr(), stream))
+
+    def call(name, *args):
+        be.call(name, *args)
         LAST_PATHS.append(_last())
-        idx = torch.nonzero(cand.reshape(-1)).reshape(-1)               # int64, in index order
-        n = int(idx.numel())
+
+    with be:
+        first0, first1 = (be.put(f, np.int32) for f in plan.first)
+        grid = _grid(plan, rows, be.ptr, levels, B, scale, first0, first1)
+        cand, zero = be.empty((B, nc0, nc1), np.uint8), be.empty((B, nc0, nc1), np.uint8)
+        call("bsk_contour_flag", *grid, be.ptr(cand), be.ptr(zero))
+        idx = be.nonzero(cand)
+        n = len(idx)
         P = split_of(n, depth) if split is None else int(split)
-        out = dict(cand=cand, zero=zero, keys=torch.empty((0, 2), dtype=torch.int64, device=dev),
-                   xy=torch.empty((0, 4), dtype=torch.float64, device=dev), field=torch.empty(0, dtype=torch.int64, device=dev),
-                   status=torch.zeros((B, nc0, nc1), dtype=torch.uint8, device=dev), split=P)
+        out = dict(cand=cand, zero=zero, keys=be.empty((0, 2), np.int64), xy=be.empty((0, 4), np.float64), field=be.empty(0, np.int64),
+                   status=be.zeros((B, nc0, nc1), np.uint8), split=P)
         if not n:
             return out
-        breaks0, breaks1 = (torch.from_numpy(np.ascontiguousarray(b, np.float64)).to(dev) for b in plan.breaks)
+        breaks0, breaks1 = (be.put(b, np.float64) for b in plan.breaks)
         lanes = n << (2 * P)
-        counts = torch.empty(lanes, dtype=torch.int32, device=dev)
-        lane_status = torch.empty(lanes, dtype=torch.uint8, device=dev)
-        march = grid + (breaks0.data_ptr(), breaks1.data_ptr(), idx.data_ptr(), n, depth, P)
-        nv.check(L.bsk_contour_march(*march, 0, None, 0, counts.data_ptr(), lane_status.data_ptr(), None, None, stream))
-        LAST_PATHS.append(_last())
-        out["status"].reshape(-1)[idx] = lane_status.reshape(n, -1).amax(dim=1)
-        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        counts, lane_status = be.empty(lanes, np.int32), be.empty(lanes, np.uint8)
+        march = grid + (be.ptr(breaks0), be.ptr(breaks1), be.ptr(idx), n, depth, P)
+        call("bsk_contour_march", *march, 0, None, 0, be.ptr(counts), be.ptr(lane_status), None, None)
+        out["status"].reshape(-1)[idx] = be.amax(lane_status.reshape(n, -1), 1)
+        ends = be.cumsum(counts)
         total = int(ends[-1])
         if not total:
             return out
-        offsets = (ends - counts).contiguous()
-        keys = torch.empty((total, 2), dtype=torch.int64, device=dev)
-        xy = torch.empty((total, 4), dtype=torch.float64, device=dev)
-        nv.check(L.bsk_contour_march(*march, 1, offsets.data_ptr(), total, None, None, keys.data_ptr(), xy.data_ptr(), stream))
-        LAST_PATHS.append(_last())
-        per_cell = counts.reshape(n, -1).sum(dim=1)
-        out.update(keys=keys, xy=xy, field=torch.repeat_interleave(torch.div(idx, nc0 * nc1, rounding_mode="floor"), per_cell))
+        offsets = ends - counts                                        # int64, a fresh contiguous array
+        keys, xy = be.empty((total, 2), np.int64), be.empty((total, 4), np.float64)
+        call("bsk_contour_march", *march, 1, be.ptr(offsets), total, None, None, be.ptr(keys), be.ptr(xy))
+        out.update(keys=keys, xy=xy, field=be.repeat(idx // (nc0 * nc1), be.sum(counts.reshape(n, -1), 1)))
     return out
 
 
+def _run_host(rows, plan, levels, scale, depth, split):
+    """``_run`` on NumPy arrays."""
+    rows, levels, scale = (None if a is None else np.ascontiguousarray(a, np.float64) for a in (rows, levels, scale))
+    return _run(_cells.Host(), rows, plan, levels, scale, depth, split)
+
+
 # ------------------------------------------------------------------------------------------ public
-class Plan(roots2.Plan2):
-    """``roots2.Plan2`` that refuses a jump: an interior knot of multiplicity >= K."""
+class Plan(_cells.TensorPlan):
+    """``_cells.TensorPlan`` that refuses a jump: an interior knot of multiplicity >= K."""
 
     def __init__(self, order, knots):
         for d in range(2):
@@ -496,13 +440,13 @@ def trace_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=
     the vertices never leave the device (the integer keys of the segments do: linking is a host sort).
     ``_split`` pins the split level P of the march launches (0 .. depth); the result does not depend on it."""
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = _cells.pick_path(_path, FORCE_PATH)
     _check_spline(spline)
     K0, K1 = (int(k) for k in spline.order)
     n0, n1 = (len(spline.knots[d]) - spline.order[d] for d in range(2))
     if levels is not None and coefs is not None:
         raise ValueError("trace_batch takes levels or coefs, not both")
-    on_device = coefs is not None and roots._is_torch(coefs)
+    on_device = coefs is not None and _cells.is_torch(coefs)
     if coefs is None:
         if spline.nDep != 1:
             raise ValueError("trace_batch takes one dependent variable, or coefs (B, n0, n1)")
@@ -552,7 +496,7 @@ def trace_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=
         if plan.steps:
             rows, ran = refinement.run_device(rows, plan.steps)
             LAST_PATHS.extend(ran)
-        res = _run_device(rows.contiguous(), plan, d_levels, d_scale, depth, _split)
+        res = _run(_cells.Device(dev), rows.contiguous(), plan, d_levels, d_scale, depth, _split)
         points, offsets, closed, comp_field = link(res["keys"].cpu().numpy(), res["field"].cpu().numpy(), B)
         vertices = res["xy"].reshape(-1, 2)[torch.from_numpy(points).to(dev)].to(getattr(torch, kdtype.name))
         zero, status = res["zero"].cpu().numpy(), res["status"]
@@ -608,7 +552,7 @@ def contours(self, tolerance=None, depth=None, _path=None):
     if tolerance is None:
         tolerance = FIT_TOLERANCE * max(float(b[-1]) - float(b[0]) for b in plan.breaks)
     vertices, offsets, closed, _, cells, _ = trace_batch(self, depth=depth, _path=_path)
-    if roots._is_torch(vertices):
+    if _cells.is_torch(vertices):
         vertices = vertices.cpu().numpy()
     found = []
     for m in range(len(offsets) - 1):

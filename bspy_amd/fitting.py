@@ -23,6 +23,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nv
+from ._cells import pick_path
 from .collocation import collocation_matrix
 from .device_spline import _is_torch
 
@@ -216,9 +217,7 @@ def least_squares(uValues, dataPoints, order=None, knots=None, compression=0.0, 
                   metadata={}, _path=None):
     from .spline import Spline
 
-    path = _path if _path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
+    path = pick_path(_path, FORCE_PATH)
     del LAST_PATHS[:]
 
     if _is_torch(dataPoints):

@@ -32,6 +32,7 @@ import math
 import numpy as np
 
 from . import _native as nv
+from ._cells import is_torch as _is_torch, pick_path
 from .refinement import knot_cell, support_cell
 
 # Elements of the result from which the device path is taken.  AN ESTIMATE, not a measurement: refinement's threshold
@@ -239,10 +240,6 @@ def plane_table(dep_terms, UA=1, UB=1):
 
 
 # ------------------------------------------------------------------------------------------ application
-def _is_torch(a):
-    return type(a).__module__.startswith("torch")
-
-
 def apply(maps, a, b, terms):
     """The product operator ``maps`` (a ProductMap) on torch CUDA tensors a (PA, *nIn1) and b (PB, *nIn2) of one type
     (float32 / float64), mapped variables last; ``terms`` (P, T, 3): NumPy plane table.  Returns a new CUDA tensor
@@ -286,8 +283,7 @@ def _canonical(coefs, mapped):
 
 def multiply(self, other, indMap=None, productType="S", _path=None):
     del LAST_PATHS[:]
-    if _path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
+    pick_path(_path, None)
     if productType not in ("C", "D", "S"):
         raise ValueError("productType must be 'C', 'D' or 'S'")
     if productType == "D" and self.nDep != other.nDep:

@@ -44,15 +44,14 @@ No atomics, no waiting: two runs give the same bytes.
 
 ``_path="device" | "host"`` (or ``project.FORCE_PATH``) pins the path; ``project.LAST_PATHS`` lists what the last call ran.
 """
-import ctypes
 import math
 import warnings
 
 import numpy as np
 
+from . import _cells
 from . import _native as nv
 from . import refinement
-from . import roots
 
 # Points x samples from which the device path is taken; a Newton solve counts as NEWTON_WORK squared distances.  Read off the
 # table of tools/project_time.py on an MI355X (DESIGN.md section 20): the host path takes about 0.8 ns per squared distance
@@ -325,20 +324,13 @@ def sample_weights(order, G):
     return w.astype(np.float64)
 
 
-class Plan:
-    """Bezier extraction of every variable (one ``roots.BezierPlan`` per axis, the band steps on the axes 1 .. nInd of a
-    tensor (nDep, *nCoef)) and the band steps of the sample grid on the extracted rows."""
+class Plan(_cells.TensorPlan):
+    """``_cells.TensorPlan`` (Bezier extraction of every variable, the band steps on the axes 1 .. nInd of a tensor
+    (nDep, *nCoef)) and the band steps of the sample grid on the extracted rows."""
 
     def __init__(self, order, knots, samples):
-        self.nind = len(order)
-        self.axes = [roots.BezierPlan(order[d], knots[d]) for d in range(self.nind)]
-        self.order = tuple(int(k) for k in order)
+        super().__init__(order, knots)
         self.G = tuple(int(g) for g in samples)
-        self.steps = [(d + 1, first, w) for d in range(self.nind) for _, first, w in self.axes[d].steps]
-        self.breaks = [p.breaks for p in self.axes]
-        self.first = [p.first for p in self.axes]
-        self.rowlen = [p.rowlen for p in self.axes]
-        self.ncells = [p.nspans for p in self.axes]
         self.sample_steps = [self.sample_step(d) for d in range(self.nind)]
         self.nsamples = int(np.prod([nc * g for nc, g in zip(self.ncells, self.G)], dtype=np.int64))
 
@@ -350,30 +342,14 @@ class Plan:
         return Tables(self.nind, rows, self.first, self.breaks, self.order, self.G)
 
 
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
-
-
 def _last():
     return nv.lib().bsk_project_last_kernel().decode()
 
 
 # ------------------------------------------------------------------------------------------ the launches
 def band_host(data, steps):
-    """NumPy (nDep, ...) float64 through band steps in the order the device path takes them, each summed as the band
-    kernels sum it (``bsk_roots_extract_host`` on the lines of that axis)."""
-    for axis, first, w in refinement._ordered(steps, data.shape):
-        first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
-        lines = np.ascontiguousarray(np.moveaxis(data, axis, -1))
-        out = np.empty(lines.shape[:-1] + (len(first),), np.float64)
-        nv.check(nv.lib().bsk_roots_extract_host(w.shape[1], lines.shape[-1], len(first), first.ctypes.data, w.ctypes.data,
-                                                 lines.ctypes.data, lines.size // lines.shape[-1], out.ctypes.data))
-        LAST_PATHS.append(roots._last())
-        data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
-    return data
+    """NumPy (nDep, ...) float64 through band steps (``_cells.band_host``)."""
+    return _cells.band_host(data, steps, LAST_PATHS)
 
 
 def _grid(plan, rows_ptr, tables):
@@ -394,62 +370,32 @@ def _axis_tables(plan):
     return first + breaks
 
 
-def run_host(plan, rows, samples, points, guess, chunk):
-    """rows (nDep, R0[, R1]), samples (nDep, M0[, M1]), points (nDep, N), guess (nInd, N) or None: NumPy float64.
-    -> uvw (nInd, N), distance, status, steps."""
-    L = nv.lib()
+def run(be, plan, rows, samples, points, guess, chunk):
+    """rows (nDep, R0[, R1]), samples (nDep, M0[, M1]), points (nDep, N), guess (nInd, N) or None: the backend's contiguous
+    float64 arrays.  -> uvw (nInd, N), distance, status, steps, the backend's."""
     nDep, N = points.shape
-    rows, points = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(points, np.float64)
     M = plan.nsamples
     C = -(-M // chunk)
-    part_d2, part_idx = np.empty((C, N), np.float64), np.empty((C, N), np.int32)
-    if guess is None:
-        samples = np.ascontiguousarray(samples, np.float64)
-        nv.check(L.bsk_project_seed_host(nDep, samples.ctypes.data, M, points.ctypes.data, N, chunk, part_d2.ctypes.data,
-                                         part_idx.ctypes.data))
-        LAST_PATHS.append(_last())
-    else:
-        guess = np.ascontiguousarray(guess, np.float64)
-    tabs = _axis_tables(plan)
-    args = list(_grid(plan, rows.ctypes.data, [t.ctypes.data for t in tabs]))
-    args[3] = nDep
-    uvw, distance = np.empty((plan.nind, N), np.float64), np.empty(N, np.float64)
-    status, steps = np.empty(N, np.uint8), np.empty(N, np.int32)
-    nv.check(L.bsk_project_newton_host(*args, points.ctypes.data, N, part_d2.ctypes.data, part_idx.ctypes.data, C,
-                                       None if guess is None else guess.ctypes.data, uvw.ctypes.data, distance.ctypes.data,
-                                       status.ctypes.data, steps.ctypes.data))
-    LAST_PATHS.append(_last())
-    return uvw, distance, status, steps
-
-
-def run_device(plan, rows, samples, points, guess, chunk):
-    """The same with contiguous float64 torch CUDA tensors; every entry of the result is a CUDA tensor."""
-    import torch
-    L = nv.lib()
-    nDep, N = points.shape
-    dev = points.device
-    M = plan.nsamples
-    C = -(-M // chunk)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        part_d2 = torch.empty((C, N), dtype=torch.float64, device=dev)
-        part_idx = torch.empty((C, N), dtype=torch.int32, device=dev)
+    with be:
+        part_d2, part_idx = be.empty((C, N), np.float64), be.empty((C, N), np.int32)
         if guess is None:
-            nv.check(L.bsk_project_seed(nDep, samples.data_ptr(), M, points.data_ptr(), N, chunk, part_d2.data_ptr(),
-                                        part_idx.data_ptr(), stream))
+            be.call("bsk_project_seed", nDep, be.ptr(samples), M, be.ptr(points), N, chunk, be.ptr(part_d2), be.ptr(part_idx))
             LAST_PATHS.append(_last())
-        tabs = [torch.from_numpy(t).to(dev) for t in _axis_tables(plan)]
-        args = list(_grid(plan, rows.data_ptr(), [t.data_ptr() for t in tabs]))
+        tabs = [be.put(t, t.dtype) for t in _axis_tables(plan)]
+        args = list(_grid(plan, be.ptr(rows), [be.ptr(t) for t in tabs]))
         args[3] = nDep
-        uvw = torch.empty((plan.nind, N), dtype=torch.float64, device=dev)
-        distance = torch.empty(N, dtype=torch.float64, device=dev)
-        status = torch.empty(N, dtype=torch.uint8, device=dev)
-        steps = torch.empty(N, dtype=torch.int32, device=dev)
-        nv.check(L.bsk_project_newton(*args, points.data_ptr(), N, part_d2.data_ptr(), part_idx.data_ptr(), C,
-                                      None if guess is None else guess.data_ptr(), uvw.data_ptr(), distance.data_ptr(),
-                                      status.data_ptr(), steps.data_ptr(), stream))
+        uvw, distance = be.empty((plan.nind, N), np.float64), be.empty(N, np.float64)
+        status, steps = be.empty(N, np.uint8), be.empty(N, np.int32)
+        be.call("bsk_project_newton", *args, be.ptr(points), N, be.ptr(part_d2), be.ptr(part_idx), C, be.ptr(guess), be.ptr(uvw),
+                be.ptr(distance), be.ptr(status), be.ptr(steps))
         LAST_PATHS.append(_last())
     return uvw, distance, status, steps
+
+
+def run_host(plan, rows, samples, points, guess, chunk):
+    """``run`` on NumPy arrays."""
+    rows, samples, points, guess = (None if a is None else np.ascontiguousarray(a, np.float64) for a in (rows, samples, points, guess))
+    return run(_cells.Host(), plan, rows, samples, points, guess, chunk)
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -486,11 +432,11 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
     8: point not finite, not iterated) and the evaluations made (int32) per point.  CUDA in gives CUDA out; nothing leaves
     the device.  A flagged point never raises: it holds the best iterate."""
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = _cells.pick_path(_path, FORCE_PATH)
     _check_spline(spline)
     G = _samples(spline, samples)
     nInd, nDep = spline.nInd, spline.nDep
-    on_device = roots._is_torch(points)
+    on_device = _cells.is_torch(points)
     if on_device:
         import torch
         if not points.is_cuda or points.dtype not in (torch.float32, torch.float64):
@@ -506,7 +452,7 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
         raise ValueError(f"points must have the shape ({nDep}, ...)")
     shape = tuple(points.shape[1:])
     if guess is not None:
-        if roots._is_torch(guess) != on_device:
+        if _cells.is_torch(guess) != on_device:
             raise TypeError("guess must be of the same kind as the points (NumPy, or a torch CUDA tensor)")
         if on_device:
             if not guess.is_cuda or guess.dtype not in (torch.float32, torch.float64):
@@ -551,7 +497,7 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
             grid, ran = refinement.run_device(rows, plan.sample_steps)
             LAST_PATHS.extend(ran)
             grid = grid.contiguous()
-        uvw, distance, status, steps = run_device(plan, rows, grid, pts, start, chunk)
+        uvw, distance, status, steps = run(_cells.Device(dev), plan, rows, grid, pts, start, chunk)
         uvw = uvw.to(getattr(torch, kdtype.name))
         if not on_device:
             uvw, distance, status, steps = (a.cpu().numpy() for a in (uvw, distance, status, steps))
@@ -574,7 +520,7 @@ def project(self, points, guess=None, samples=None, _path=None, _chunk=None):
     count = int(flagged.sum())                                         # a status summary: the only thing that leaves the device
     if count:
         where = flagged.reshape(-1)
-        index = int(where.nonzero()[0][0]) if roots._is_torch(where) else int(np.flatnonzero(where)[0])
+        index = int(where.nonzero()[0][0]) if _cells.is_torch(where) else int(np.flatnonzero(where)[0])
         warnings.warn(f"project: {count} of {where.shape[0]} points did not converge or were not iterated "
                       f"(project_batch returns the status bits); the first one has the flat index {index}", RuntimeWarning, stacklevel=3)
     return uvw, distance

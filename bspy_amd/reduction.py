@@ -51,6 +51,7 @@ import ctypes
 
 import numpy as np
 
+from . import _cells
 from . import _native as nv
 from . import refinement
 from .refinement import BandMap
@@ -203,7 +204,7 @@ def absmax(band, tensor, axis, groups=1, minus=None):
     (float32 / float64); groups divides the product of the extents in front of ``axis``; minus: None or a CUDA tensor of
     the result's shape.  Returns a (groups, band.nOut) float64 CUDA tensor.  ``LAST_PATHS`` holds this call's kernel."""
     import torch
-    if not (refinement._is_torch(tensor) and tensor.is_cuda):
+    if not (_cells.is_torch(tensor) and tensor.is_cuda):
         raise TypeError("reduction.absmax takes a torch CUDA tensor")
     if tensor.dtype not in (torch.float32, torch.float64):
         raise TypeError("reduction.absmax takes float32 or float64")
@@ -345,9 +346,7 @@ def _finite_or_inf(a):
 
 
 def remove_knots(self, tolerance=1e-14, nLeft=0, nRight=0, _path=None):
-    path = _path if _path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
+    path = _cells.pick_path(_path, FORCE_PATH)
     del LAST_PATHS[:]
     LAST_ROUNDS[:] = [[] for _ in range(self.nInd)]
     coefs = np.ascontiguousarray(self.coefs)

@@ -31,6 +31,7 @@ import itertools
 import numpy as np
 
 from . import _native as nv
+from . import _cells          # (it imports this module too: use its names at call time only)
 
 # Elements of the coefficient tensor (the larger of input and result) from which the device path is taken.  The key is
 # the total element count: see DESIGN.md section 13 for its standing.
@@ -235,10 +236,6 @@ def differentiate_map(knots, order):
 
 
 # ------------------------------------------------------------------------------------------ application
-def _is_torch(a):
-    return type(a).__module__.startswith("torch")
-
-
 def apply(band, tensor, axis):
     """Apply ``band`` along ``axis`` of a torch CUDA tensor (float32 / float64); returns a new CUDA tensor of the same
     type whose extent along ``axis`` is band.nOut.  For pipelines that stay on the device.  ``LAST_PATHS`` holds this
@@ -250,7 +247,7 @@ def apply(band, tensor, axis):
 
 def _apply(band, tensor, axis):
     import torch
-    if not (_is_torch(tensor) and tensor.is_cuda):
+    if not (_cells.is_torch(tensor) and tensor.is_cuda):
         raise TypeError("refinement.apply takes a torch CUDA tensor")
     if tensor.dtype not in (torch.float32, torch.float64):
         raise TypeError("refinement.apply takes float32 or float64")
@@ -297,9 +294,7 @@ def run_device(data, steps):
 def _run(coefs, steps, path):
     """coefs: NumPy (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step, the one that shrinks the tensor most
     first and the one that grows it most last (the operators of different variables commute), and returns NumPy."""
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
+    path = _cells.pick_path(path, FORCE_PATH)
     del LAST_PATHS[:]
     if not steps:
         return coefs

@@ -31,30 +31,24 @@ ends and, at t = 1/2, never leaves [min(a, b), max(a, b)].  A root is rounded on
 ``_path="device" | "host"`` (or ``roots.FORCE_PATH``) pins the path; ``roots.LAST_PATHS`` lists what the last call ran
 ("band_apply_line", "roots_flag", "roots_isolate", "host roots_extract", "host roots_flag", "host roots_isolate").
 """
-import ctypes
-import math
-
 import numpy as np
 
+from . import _cells
 from . import _native as nv
 from . import refinement
+from ._cells import EPS, BezierPlan
 
-# Components x spans from which the device path is taken.  AN ESTIMATE, not a measurement: tools/roots_time.py prints the
-# host / device crossover table that is to replace it (DESIGN.md section 16).
+# Components x spans from which the device path is taken.  An estimate that the first table of tools/roots_time.py --quick
+# (DESIGN.md section 16) does not move: whole calls take the same time on both paths up to 64 000 coefficients.
 DEVICE_MIN_SPANS = 16384
 DEVICE_MIN_K, DEVICE_MAX_K = 2, 8
 FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 
-EPS = float(np.finfo(np.float64).eps)
 DEPTH = 50                 # halvings of a span
 BISECT = 60                # steps of the sign bisection
 WALK = 128                 # intervals a walk may visit, per K
 MASK_SKIP, MASK_LEFT, MASK_RIGHT, MASK_LAST = 1, 2, 4, 8
-
-
-def _is_torch(a):
-    return type(a).__module__.startswith("torch")
 
 
 # ------------------------------------------------------------------------------------------ the statement
@@ -207,40 +201,6 @@ def statement(rows, order, first, mask, breaks, scale, margin, live=None):
 
 
 # ------------------------------------------------------------------------------------------ plans and tables
-class BezierPlan:
-    """Bezier extraction of one variable: ``steps`` (band steps on axis 1; empty when the knots are in Bezier form
-    already), ``breaks`` (the distinct knots of the domain, in the knots' dtype), ``first`` (where span s starts in the
-    extracted row), ``rowlen``, and ``cell`` (the knot cell of span s in the spline's own knots)."""
-
-    def __init__(self, order, knots):
-        k, t = int(order), knots
-        n = len(t) - k
-        lo, hi = t[k - 1], t[n]
-        # merged knots as refinement.merged_knots forms them (new knots behind old ones of the same value), vectorised:
-        # every distinct knot of the domain is raised to K - 1, the two ends to K
-        values, counts = np.unique(t, return_counts=True)
-        want = np.where((values == lo) | (values == hi), k, np.maximum(k - 1, counts))
-        add = np.where((values >= lo) & (values <= hi), want - counts, 0)
-        merged, origin = t, np.arange(len(t))
-        if add.any():
-            both = np.concatenate((t, np.repeat(values, add)))
-            rank = np.argsort(both, kind="stable")
-            merged, origin = both[rank], np.where(rank < len(t), rank, -1)
-        row0 = int(np.searchsorted(merged, lo))
-        row1 = int(np.searchsorted(merged, hi))
-        self.steps = []
-        if merged is not t or (row0, row1) != (0, n):
-            self.steps = [(1, *refinement.refine_map(t, k, merged, 0, rows=slice(row0, row1), origin=origin))]
-        bezier = merged[row0:row1 + k]
-        self.order = k
-        self.breaks = np.unique(bezier)
-        self.nspans = len(self.breaks) - 1
-        self.first = (np.searchsorted(bezier, self.breaks[:-1], "right") - k).astype(np.int32)
-        self.rowlen = len(bezier) - k
-        self.cell = np.clip(np.searchsorted(t, self.breaks[:-1], "right") - 1, k - 1, n - 1)
-        self.margin = math.sqrt(EPS) * (float(hi) - float(lo))
-
-
 def zero_spans(small, plan):
     """small: bool (nDep, nCoef), |coefficient| < S eps.  -> bool (nDep, nspans): all K coefficients of the span are small."""
     k = plan.order
@@ -264,13 +224,6 @@ def span_masks(zero, plan):
     return mask, np.array(rows, np.float64).reshape(-1, 3)
 
 
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
-
-
 def _last():
     return nv.lib().bsk_roots_last_kernel().decode()
 
@@ -278,62 +231,36 @@ def _last():
 # ------------------------------------------------------------------------------------------ the launches
 def extract_host(coefs, plan):
     """NumPy (nDep, nCoef) -> float64 (nDep, rowlen) in Bezier form: the plan's band step, summed as the band kernels do."""
-    _, first, w = plan.steps[0]
-    data = np.ascontiguousarray(coefs, np.float64)                      # float32 is widened BEFORE the extraction
-    first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
-    out = np.empty((data.shape[0], len(first)), np.float64)
-    nv.check(nv.lib().bsk_roots_extract_host(w.shape[1], data.shape[1], len(first), first.ctypes.data, w.ctypes.data,
-                                             data.ctypes.data, data.shape[0], out.ctypes.data))
-    return out
+    return _cells.band_host(np.ascontiguousarray(coefs, np.float64), plan.steps, [])   # float32 is widened BEFORE the extraction
+
+
+def _run(be, rows, plan, mask, scale):
+    """rows: the backend's contiguous array (nDep, rowlen), float32 / float64 in Bezier form; mask: NumPy; scale: the
+    backend's float64 (nDep).  -> the backend's arrays (cand, roots (ncand, K - 1), count)."""
+    k, nDep = plan.order, rows.shape[0]
+    with be:
+        first, mask = be.put(plan.first, np.int32), be.put(mask, np.uint8)
+        grid = (be.code(rows), k, be.ptr(rows), nDep, plan.rowlen, plan.nspans, be.ptr(first), be.ptr(mask))
+        flags = be.empty((nDep, plan.nspans), np.uint8)
+        be.call("bsk_roots_flag", *grid, be.ptr(flags))
+        LAST_PATHS.append(_last())
+        cand = be.nonzero(flags)
+        roots = be.empty((len(cand), k - 1), np.float64)
+        count = be.empty(len(cand), np.int32)
+        if len(cand):
+            breaks = be.put(plan.breaks, np.float64)
+            be.call("bsk_roots_isolate", *grid, be.ptr(breaks), be.ptr(scale), plan.margin, be.ptr(cand), len(cand), be.ptr(roots),
+                    be.ptr(count))
+            LAST_PATHS.append(_last())
+    return cand, roots, count
 
 
 def _run_host(rows, plan, mask, scale):
-    """rows: NumPy (nDep, rowlen) float32 / float64 in Bezier form.  -> (cand, roots (ncand, K - 1), count)."""
-    k, nDep = plan.order, rows.shape[0]
-    rows = np.ascontiguousarray(rows)
-    code = nv.dtype_code(rows.dtype)
-    flags = np.empty((nDep, plan.nspans), np.uint8)
-    nv.check(nv.lib().bsk_roots_flag_host(code, k, rows.ctypes.data, nDep, plan.rowlen, plan.nspans, plan.first.ctypes.data,
-                                          mask.ctypes.data, flags.ctypes.data))
-    LAST_PATHS.append(_last())
-    cand = np.flatnonzero(flags).astype(np.int64)
-    roots = np.empty((len(cand), k - 1), np.float64)
-    count = np.empty(len(cand), np.int32)
-    if len(cand):
-        breaks = np.ascontiguousarray(plan.breaks, np.float64)
-        nv.check(nv.lib().bsk_roots_isolate_host(code, k, rows.ctypes.data, nDep, plan.rowlen, plan.nspans, plan.first.ctypes.data,
-                                                 mask.ctypes.data, breaks.ctypes.data, scale.ctypes.data, plan.margin,
-                                                 cand.ctypes.data, len(cand), roots.ctypes.data, count.ctypes.data))
-        LAST_PATHS.append(_last())
-    return cand, roots, count
+    return _run(_cells.Host(), np.ascontiguousarray(rows), plan, mask, scale)
 
 
 def _run_device(rows, plan, mask, scale):
-    """rows: contiguous torch CUDA tensor (nDep, rowlen) float32 / float64 in Bezier form; mask: NumPy; scale: CUDA
-    float64 (nDep).  -> CUDA tensors (cand, roots (ncand, K - 1), count)."""
-    import torch
-    k, nDep = plan.order, rows.shape[0]
-    dev = rows.device
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        code = nv.BSK_F32 if rows.dtype == torch.float32 else nv.BSK_F64
-        first = torch.from_numpy(plan.first).to(dev)
-        d_mask = torch.from_numpy(mask).to(dev)
-        flags = torch.empty((nDep, plan.nspans), dtype=torch.uint8, device=dev)
-        nv.check(nv.lib().bsk_roots_flag(code, k, rows.data_ptr(), nDep, plan.rowlen, plan.nspans, first.data_ptr(), d_mask.data_ptr(),
-                                         flags.data_ptr(), stream))
-        LAST_PATHS.append(_last())
-        cand = torch.nonzero(flags.reshape(-1)).reshape(-1)            # int64, in index order
-        ncand = int(cand.numel())
-        roots = torch.empty((ncand, k - 1), dtype=torch.float64, device=dev)
-        count = torch.empty(ncand, dtype=torch.int32, device=dev)
-        if ncand:
-            breaks = torch.from_numpy(np.ascontiguousarray(plan.breaks, np.float64)).to(dev)
-            nv.check(nv.lib().bsk_roots_isolate(code, k, rows.data_ptr(), nDep, plan.rowlen, plan.nspans, first.data_ptr(),
-                                                d_mask.data_ptr(), breaks.data_ptr(), scale.data_ptr(), plan.margin, cand.data_ptr(),
-                                                ncand, roots.data_ptr(), count.data_ptr(), stream))
-            LAST_PATHS.append(_last())
-    return cand, roots, count
+    return _run(_cells.Device(rows.device), rows, plan, mask, scale)
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -346,11 +273,11 @@ def zeros_batch(spline, coefs=None, _path=None):
     spline gives the order and the knots); values and offsets are then CUDA tensors.  The table of zero spans (one byte
     per component and span) is formed on the device and read back; nothing else leaves the device."""
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = _cells.pick_path(_path, FORCE_PATH)
     if spline.nInd != 1:
         raise ValueError("zeros_batch takes a curve (nInd == 1)")
     k, t = spline.order[0], spline.knots[0]
-    on_device = coefs is not None and _is_torch(coefs)
+    on_device = coefs is not None and _cells.is_torch(coefs)
     if coefs is None:
         coefs = spline.coefs
     if on_device:
@@ -412,8 +339,7 @@ def zeros_batch(spline, coefs=None, _path=None):
         raise NotImplementedError(f"zeros: orders above {nv.BSK_MAX_ORDER} are out of scope")
     rows = coefs
     if plan.steps:
-        rows = extract_host(coefs, plan)
-        LAST_PATHS.append(_last())
+        rows = _cells.band_host(np.ascontiguousarray(coefs, np.float64), plan.steps, LAST_PATHS)   # widened BEFORE the extraction
     cand, roots, count = _run_host(rows, plan, mask, scale)
     values = roots[~np.isnan(roots)].astype(kdtype)
     per = np.bincount(cand // plan.nspans, weights=count, minlength=nDep).astype(np.int64)

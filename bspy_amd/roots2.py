@@ -46,16 +46,15 @@ A zero is rounded once to the knots' dtype at the end.  No atomics, no waiting: 
 
 ``_path="device" | "host"`` (or ``roots2.FORCE_PATH``) pins the path; ``roots2.LAST_PATHS`` lists what the last call ran.
 """
-import ctypes
-
 import numpy as np
 
-from . import _native as nv
+from . import _cells
 from . import refinement
 from . import roots
+from ._cells import zero_cells
 
-# Systems x cells from which the device path is taken.  AN ESTIMATE, not a measurement: nobody has run
-# tools/roots2_time.py on an MI355X yet; its host / device crossover table is to replace this number (DESIGN.md section 17).
+# Systems x cells from which the device path is taken.  AN ESTIMATE from before the first run of tools/roots2_time.py on an
+# MI355X; DESIGN.md section 17 has that run's host / device table (dense random systems cross near 64 x 64 cells).
 DEVICE_MIN_CELLS = 4096
 DEVICE_MIN_K, DEVICE_MAX_K = 2, 4
 HOST_MAX_K = 6
@@ -307,139 +306,20 @@ def statement(rows, plan, mask, scale, walk=None):
     return dict(flags=flags, cand=cand, roots=out, near=near, count=count, status=status, nodes=nodes, keep=keep)
 
 
-# ------------------------------------------------------------------------------------------ plans and tables
-class Plan2:
-    """Bezier extraction of both variables: one ``roots.BezierPlan`` per axis and the band steps on the axes 1 and 2 of a
-    tensor (systems x components, n0, n1)."""
-
-    def __init__(self, order, knots):
-        self.axes = [roots.BezierPlan(order[d], knots[d]) for d in range(2)]
-        self.order = tuple(int(k) for k in order)
-        self.steps = [(d + 1, first, w) for d in range(2) for _, first, w in self.axes[d].steps]
-        self.breaks = [p.breaks for p in self.axes]
-        self.first = [p.first for p in self.axes]
-        self.rowlen = [p.rowlen for p in self.axes]
-        self.ncells = [p.nspans for p in self.axes]
+# ------------------------------------------------------------------------------------------ plans and launches
+Plan2 = _cells.TensorPlan          # one ``roots.BezierPlan`` per axis; the band steps on the axes 1 and 2 of (M, n0, n1)
 
 
-def zero_cells(small, plan):
-    """small: bool (B, 2, n0, n1), |coefficient| < S_d eps.  -> bool (B, nc0, nc1): all K0 x K1 coefficients of the cell
-    are small, for either component."""
-    K0, K1 = plan.order
-    run = np.zeros((small.shape[0], 2, small.shape[2] + 1, small.shape[3] + 1), np.int64)
-    run[:, :, 1:, 1:] = np.cumsum(np.cumsum(small, axis=2, dtype=np.int64), axis=3)
-    hi0, hi1 = plan.axes[0].cell + 1, plan.axes[1].cell + 1
-    lo0, lo1 = hi0 - K0, hi1 - K1
-    total = (run[:, :, hi0[:, None], hi1[None, :]] - run[:, :, lo0[:, None], hi1[None, :]] - run[:, :, hi0[:, None], lo1[None, :]]
-             + run[:, :, lo0[:, None], lo1[None, :]])
-    return (total == K0 * K1).any(axis=1)
-
-
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
-
-
-def _last():
-    return nv.lib().bsk_roots2_last_kernel().decode()
-
-
-# ------------------------------------------------------------------------------------------ the launches
 def extract_host(data, plan):
-    """NumPy (M, n0, n1) float64 -> (M, R0, R1) in Bezier form: the plan's band steps in the order the device path takes
-    them, each summed as the band kernels sum it (``bsk_roots_extract_host`` on the lines of that axis)."""
-    for axis, first, w in refinement._ordered(plan.steps, data.shape):
-        first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
-        lines = np.ascontiguousarray(np.moveaxis(data, axis, -1))
-        out = np.empty(lines.shape[:-1] + (len(first),), np.float64)
-        nv.check(nv.lib().bsk_roots_extract_host(w.shape[1], lines.shape[-1], len(first), first.ctypes.data, w.ctypes.data,
-                                                 lines.ctypes.data, lines.size // lines.shape[-1], out.ctypes.data))
-        LAST_PATHS.append(roots._last())
-        data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
-    return data
-
-
-def _grid(plan, rows, B, ptr):
-    K0, K1 = plan.order
-    return (K0, K1, ptr(rows), B, plan.rowlen[0], plan.rowlen[1], plan.ncells[0], plan.ncells[1])
+    """NumPy (M, n0, n1) float64 -> (M, R0, R1) in Bezier form (``_cells.band_host``)."""
+    return _cells.band_host(data, plan.steps, LAST_PATHS)
 
 
 def _run_host(rows, plan, mask, scale):
     """rows: NumPy float64 (B, 2, R0, R1) in Bezier form; mask: uint8 (B, nc0, nc1); scale: float64 (B, 2).  -> dict of
-    flags, cand, roots (ncand, R, 2), near, count, status, nodes, keep."""
-    L = nv.lib()
-    K0, K1 = plan.order
-    R = slots(K0, K1)
-    B = rows.shape[0]
-    rows, mask, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(scale, np.float64)
-    first0, first1 = plan.first
-    grid = _grid(plan, rows, B, lambda a: a.ctypes.data) + (first0.ctypes.data, first1.ctypes.data)
-    flags = np.empty(mask.shape, np.uint8)
-    nv.check(L.bsk_roots2_flag_host(*grid, mask.ctypes.data, flags.ctypes.data))
-    LAST_PATHS.append(_last())
-    cand = np.flatnonzero(flags).astype(np.int64)
-    n = len(cand)
-    out = dict(flags=flags, cand=cand, roots=np.empty((n, R, 2), np.float64), near=np.empty((n, R), np.uint8),
-               count=np.empty(n, np.int32), status=np.empty(n, np.uint8), nodes=np.empty(n, np.int32))
-    if n:
-        breaks0, breaks1 = (np.ascontiguousarray(b, np.float64) for b in plan.breaks)
-        nv.check(L.bsk_roots2_isolate_host(*grid, breaks0.ctypes.data, breaks1.ctypes.data, scale.ctypes.data, cand.ctypes.data, n,
-                                           out["roots"].ctypes.data, out["near"].ctypes.data, out["count"].ctypes.data,
-                                           out["status"].ctypes.data, out["nodes"].ctypes.data))
-        LAST_PATHS.append(_last())
-    keep = (~np.isnan(out["roots"][:, :, 0])).astype(np.uint8)
-    which = np.flatnonzero(out["near"]).astype(np.int64)
-    if len(which):
-        table = np.cumsum(flags.reshape(-1), dtype=np.int64) - 1
-        nv.check(L.bsk_roots2_merge_host(R, out["roots"].ctypes.data, B, plan.ncells[0], plan.ncells[1], breaks0.ctypes.data,
-                                         breaks1.ctypes.data, cand.ctypes.data, n, flags.ctypes.data, table.ctypes.data,
-                                         which.ctypes.data, len(which), keep.ctypes.data))
-        LAST_PATHS.append(_last())
-    out["keep"] = keep
-    return out
-
-
-def _run_device(rows, plan, mask, scale):
-    """The same with contiguous torch CUDA tensors (mask: NumPy); every entry of the result is a CUDA tensor."""
-    import torch
-    L = nv.lib()
-    K0, K1 = plan.order
-    R = slots(K0, K1)
-    B = mask.shape[0]                                  # systems: the rows come as (2 B, ...), components unfolded
-    if rows.shape[0] != 2 * B:
-        raise ValueError("the rows must hold 2 components per system of the mask")
-    dev = rows.device
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        first0, first1 = (torch.from_numpy(f).to(dev) for f in plan.first)
-        grid = _grid(plan, rows, B, lambda a: a.data_ptr()) + (first0.data_ptr(), first1.data_ptr())
-        d_mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
-        flags = torch.empty(mask.shape, dtype=torch.uint8, device=dev)
-        nv.check(L.bsk_roots2_flag(*grid, d_mask.data_ptr(), flags.data_ptr(), stream))
-        LAST_PATHS.append(_last())
-        cand = torch.nonzero(flags.reshape(-1)).reshape(-1)            # int64, in index order
-        n = int(cand.numel())
-        out = dict(flags=flags, cand=cand, roots=torch.empty((n, R, 2), dtype=torch.float64, device=dev),
-                   near=torch.empty((n, R), dtype=torch.uint8, device=dev), count=torch.empty(n, dtype=torch.int32, device=dev),
-                   status=torch.empty(n, dtype=torch.uint8, device=dev), nodes=torch.empty(n, dtype=torch.int32, device=dev))
-        if n:
-            breaks0, breaks1 = (torch.from_numpy(np.ascontiguousarray(b, np.float64)).to(dev) for b in plan.breaks)
-            nv.check(L.bsk_roots2_isolate(*grid, breaks0.data_ptr(), breaks1.data_ptr(), scale.data_ptr(), cand.data_ptr(), n,
-                                          out["roots"].data_ptr(), out["near"].data_ptr(), out["count"].data_ptr(),
-                                          out["status"].data_ptr(), out["nodes"].data_ptr(), stream))
-            LAST_PATHS.append(_last())
-        keep = (~torch.isnan(out["roots"][:, :, 0])).to(torch.uint8).contiguous()
-        which = torch.nonzero(out["near"].reshape(-1)).reshape(-1)
-        if int(which.numel()):
-            table = torch.cumsum(flags.reshape(-1), 0, dtype=torch.int64) - 1
-            nv.check(L.bsk_roots2_merge(R, out["roots"].data_ptr(), B, plan.ncells[0], plan.ncells[1], breaks0.data_ptr(),
-                                        breaks1.data_ptr(), cand.data_ptr(), n, flags.data_ptr(), table.data_ptr(), which.data_ptr(),
-                                        int(which.numel()), keep.data_ptr(), stream))
-            LAST_PATHS.append(_last())
-        out["keep"] = keep
-    return out
+    flags, cand, roots (ncand, R, 2), near, count, status, nodes, keep (``_cells.isolate_cells``)."""
+    rows, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(scale, np.float64)
+    return _cells.isolate_cells(_cells.Host(), "bsk_roots2", rows, plan, mask, scale, slots(*plan.order), LAST_PATHS)
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -475,11 +355,11 @@ def zeros2_batch(spline, coefs=None, _path=None):
     spline gives the orders and the knots); values, offsets and status are then CUDA tensors.  The table of zero cells (one
     byte per system and cell) is formed on the device and read back; nothing else leaves the device."""
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = _cells.pick_path(_path, FORCE_PATH)
     _check_spline(spline)
     K0, K1 = (int(k) for k in spline.order)
     n0, n1 = (len(spline.knots[d]) - spline.order[d] for d in range(2))
-    on_device = coefs is not None and roots._is_torch(coefs)
+    on_device = coefs is not None and _cells.is_torch(coefs)
     if coefs is None:
         if spline.nDep != 2:
             raise ValueError("zeros2_batch takes two dependent variables, or coefs (B, 2, n0, n1)")
@@ -505,58 +385,27 @@ def zeros2_batch(spline, coefs=None, _path=None):
     if path == "device" and not covered:
         raise ValueError(f"the device path covers orders from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
 
-    def zero_rows(mask):
-        at = np.argwhere(mask)
-        b0, b1 = (np.asarray(b, np.float64) for b in plan.breaks)
-        return np.stack([at[:, 0].astype(np.float64), b0[at[:, 1]], b0[at[:, 1] + 1], b1[at[:, 2]], b1[at[:, 2] + 1]], axis=1).reshape(-1, 5)
-
     if B == 0:
-        if on_device:
-            return (torch.empty((0, 2), dtype=getattr(torch, kdtype.name), device=coefs.device),
-                    torch.zeros(1, dtype=torch.int64, device=coefs.device), np.empty((0, 5)),
-                    torch.zeros((0, nc0, nc1), dtype=torch.uint8, device=coefs.device))
-        return np.empty((0, 2), kdtype), np.zeros(1, np.int64), np.empty((0, 5)), np.zeros((0, nc0, nc1), np.uint8)
+        return _cells.collect(_cells.Device(coefs.device) if on_device else _cells.Host(), plan, kdtype, 0)
 
     if path == "device":
         import torch
         data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        dev = data.device
+        be = _cells.Device(data.device)
         wide = data.abs()
-        d_scale = wide.amax(dim=(2, 3)).contiguous()
-        small = ((wide < (d_scale * EPS)[:, :, None, None]) | (d_scale == 0.0)[:, :, None, None]).cpu().numpy()
+        scale = wide.amax(dim=(2, 3)).contiguous()
+        small = ((wide < (scale * EPS)[:, :, None, None]) | (scale == 0.0)[:, :, None, None]).cpu().numpy()
         mask = zero_cells(small, plan).astype(np.uint8)
         rows = data.reshape((2 * B, n0, n1))
         if plan.steps:
             rows, ran = refinement.run_device(rows, plan.steps)
             LAST_PATHS.extend(ran)
-        res = _run_device(rows.contiguous(), plan, mask, d_scale)
-        kept = res["keep"].reshape(-1).bool()
-        system = torch.div(res["cand"], nc0 * nc1, rounding_mode="floor")
-        system = system[:, None].expand(-1, slots(K0, K1)).reshape(-1)[kept]
-        values = res["roots"].reshape(-1, 2)[kept]
-        order = torch.argsort(values[:, 1], stable=True)
-        order = order[torch.argsort(values[order, 0], stable=True)]
-        order = order[torch.argsort(system[order], stable=True)]
-        values = values[order].to(getattr(torch, kdtype.name))
-        offsets = torch.searchsorted(system[order].contiguous(), torch.arange(B + 1, device=dev))
-        status = torch.zeros(B * nc0 * nc1, dtype=torch.uint8, device=dev)
-        status[res["cand"]] = res["status"]
-        status = status.reshape(B, nc0, nc1)
-        if not on_device:
-            values, offsets, status = values.cpu().numpy(), offsets.cpu().numpy(), status.cpu().numpy()
-        return values, offsets, zero_rows(mask), status
-
-    _, rows, mask, scale = tables(spline, coefs)
-    res = _run_host(rows, plan, mask, scale)
-    kept = res["keep"].reshape(-1).astype(bool)
-    system = np.repeat(res["cand"] // (nc0 * nc1), slots(K0, K1))[kept]
-    values = res["roots"].reshape(-1, 2)[kept]
-    order = np.lexsort((values[:, 1], values[:, 0], system))
-    values = values[order].astype(kdtype)
-    offsets = np.searchsorted(system[order], np.arange(B + 1)).astype(np.int64)
-    status = np.zeros(B * nc0 * nc1, np.uint8)
-    status[res["cand"]] = res["status"]
-    return values, offsets, zero_rows(mask), status.reshape(B, nc0, nc1)
+        res = _cells.isolate_cells(be, "bsk_roots2", rows.contiguous(), plan, mask, scale, slots(K0, K1), LAST_PATHS)
+    else:
+        be = _cells.Host()
+        _, rows, mask, scale = tables(spline, coefs)
+        res = _run_host(rows, plan, mask, scale)             # makes rows and scale contiguous
+    return _cells.collect(be, plan, kdtype, B, slots(K0, K1), res, mask, numpy_out=not on_device)
 
 
 def zeros2(self, _path=None):

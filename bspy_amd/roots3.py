@@ -57,13 +57,12 @@ the two paths.
 
 ``_path="device" | "host"`` (or ``roots3.FORCE_PATH``) pins the path; ``roots3.LAST_PATHS`` lists what the last call ran.
 """
-import ctypes
-
 import numpy as np
 
-from . import _native as nv
+from . import _cells
 from . import refinement
 from . import roots
+from ._cells import zero_cells
 
 # Systems x cells from which the device path is taken.  Measured with tools/roots3_time.py on an MI355X (DESIGN.md section 19):
 # on candidate-dense systems the device wins from 8 cells on and by a factor 2 at 64; on sparse ones the host wins up to
@@ -341,135 +340,20 @@ def statement(rows, plan, mask, scale, walk=None):
     return dict(flags=flags, cand=cand, roots=out, near=near, count=count, status=status, nodes=nodes, keep=keep)
 
 
-# ------------------------------------------------------------------------------------------ plans and tables
-class Plan3:
-    """Bezier extraction of the three variables: one ``roots.BezierPlan`` per axis and the band steps on the axes 1, 2 and 3
-    of a tensor (systems x components, n0, n1, n2)."""
-
-    def __init__(self, order, knots):
-        self.axes = [roots.BezierPlan(order[d], knots[d]) for d in range(3)]
-        self.order = tuple(int(k) for k in order)
-        self.steps = [(d + 1, first, w) for d in range(3) for _, first, w in self.axes[d].steps]
-        self.breaks = [p.breaks for p in self.axes]
-        self.first = [p.first for p in self.axes]
-        self.rowlen = [p.rowlen for p in self.axes]
-        self.ncells = [p.nspans for p in self.axes]
+# ------------------------------------------------------------------------------------------ plans and launches
+Plan3 = _cells.TensorPlan          # one ``roots.BezierPlan`` per axis; the band steps on the axes 1, 2 and 3 of (M, n0, n1, n2)
 
 
-def zero_cells(small, plan):
-    """small: bool (B, 3, n0, n1, n2), |coefficient| < S_d eps.  -> bool (B, nc0, nc1, nc2): all K0 x K1 x K2 coefficients
-    of the cell are small, for any component."""
-    total = small.astype(np.int64)
-    for a in range(3):                                                   # windowed sums, one axis at a time
-        K = plan.order[a]
-        run = np.concatenate((np.zeros_like(np.take(total, [0], axis=a + 2)), np.cumsum(total, axis=a + 2)), axis=a + 2)
-        hi = plan.axes[a].cell + 1
-        total = np.take(run, hi, axis=a + 2) - np.take(run, hi - K, axis=a + 2)
-    return (total == plan.order[0] * plan.order[1] * plan.order[2]).any(axis=1)
-
-
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
-
-
-def _last():
-    return nv.lib().bsk_roots3_last_kernel().decode()
-
-
-# ------------------------------------------------------------------------------------------ the launches
 def extract_host(data, plan):
-    """NumPy (M, n0, n1, n2) float64 -> (M, R0, R1, R2) in Bezier form: the plan's band steps in the order the device path
-    takes them, each summed as the band kernels sum it (``bsk_roots_extract_host`` on the lines of that axis)."""
-    for axis, first, w in refinement._ordered(plan.steps, data.shape):
-        first, w = np.ascontiguousarray(first, np.int32), np.ascontiguousarray(w, np.float64)
-        lines = np.ascontiguousarray(np.moveaxis(data, axis, -1))
-        out = np.empty(lines.shape[:-1] + (len(first),), np.float64)
-        nv.check(nv.lib().bsk_roots_extract_host(w.shape[1], lines.shape[-1], len(first), first.ctypes.data, w.ctypes.data,
-                                                 lines.ctypes.data, lines.size // lines.shape[-1], out.ctypes.data))
-        LAST_PATHS.append(roots._last())
-        data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
-    return data
-
-
-def _grid(plan, rows, B, ptr):
-    return plan.order + (ptr(rows), B) + tuple(plan.rowlen) + tuple(plan.ncells)
+    """NumPy (M, n0, n1, n2) float64 -> (M, R0, R1, R2) in Bezier form (``_cells.band_host``)."""
+    return _cells.band_host(data, plan.steps, LAST_PATHS)
 
 
 def _run_host(rows, plan, mask, scale):
     """rows: NumPy float64 (B, 3, R0, R1, R2) in Bezier form; mask: uint8 (B, nc0, nc1, nc2); scale: float64 (B, 3).
-    -> dict of flags, cand, roots (ncand, R, 3), near, count, status, nodes, keep."""
-    L = nv.lib()
-    R = slots(*plan.order)
-    B = rows.shape[0]
-    rows, mask, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(mask, np.uint8), np.ascontiguousarray(scale, np.float64)
-    first = [np.ascontiguousarray(f, np.int32) for f in plan.first]
-    grid = _grid(plan, rows, B, lambda a: a.ctypes.data) + tuple(f.ctypes.data for f in first)
-    flags = np.empty(mask.shape, np.uint8)
-    nv.check(L.bsk_roots3_flag_host(*grid, mask.ctypes.data, flags.ctypes.data))
-    LAST_PATHS.append(_last())
-    cand = np.flatnonzero(flags).astype(np.int64)
-    n = len(cand)
-    out = dict(flags=flags, cand=cand, roots=np.empty((n, R, 3), np.float64), near=np.empty((n, R), np.uint8),
-               count=np.empty(n, np.int32), status=np.empty(n, np.uint8), nodes=np.empty(n, np.int32))
-    breaks = [np.ascontiguousarray(b, np.float64) for b in plan.breaks]
-    if n:
-        nv.check(L.bsk_roots3_isolate_host(*grid, *(b.ctypes.data for b in breaks), scale.ctypes.data, cand.ctypes.data, n,
-                                           out["roots"].ctypes.data, out["near"].ctypes.data, out["count"].ctypes.data,
-                                           out["status"].ctypes.data, out["nodes"].ctypes.data))
-        LAST_PATHS.append(_last())
-    keep = (~np.isnan(out["roots"][:, :, 0])).astype(np.uint8)
-    which = np.flatnonzero(out["near"]).astype(np.int64)
-    if len(which):
-        table = np.cumsum(flags.reshape(-1), dtype=np.int64) - 1
-        nv.check(L.bsk_roots3_merge_host(R, out["roots"].ctypes.data, B, *plan.ncells, *(b.ctypes.data for b in breaks),
-                                         cand.ctypes.data, n, flags.ctypes.data, table.ctypes.data, which.ctypes.data, len(which),
-                                         keep.ctypes.data))
-        LAST_PATHS.append(_last())
-    out["keep"] = keep
-    return out
-
-
-def _run_device(rows, plan, mask, scale):
-    """The same with contiguous torch CUDA tensors (mask: NumPy); every entry of the result is a CUDA tensor."""
-    import torch
-    L = nv.lib()
-    R = slots(*plan.order)
-    B = mask.shape[0]                                  # systems: the rows come as (3 B, ...), components unfolded
-    if rows.shape[0] != 3 * B:
-        raise ValueError("the rows must hold 3 components per system of the mask")
-    dev = rows.device
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        first = [torch.from_numpy(np.ascontiguousarray(f, np.int32)).to(dev) for f in plan.first]
-        grid = _grid(plan, rows, B, lambda a: a.data_ptr()) + tuple(f.data_ptr() for f in first)
-        d_mask = torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(dev)
-        flags = torch.empty(mask.shape, dtype=torch.uint8, device=dev)
-        nv.check(L.bsk_roots3_flag(*grid, d_mask.data_ptr(), flags.data_ptr(), stream))
-        LAST_PATHS.append(_last())
-        cand = torch.nonzero(flags.reshape(-1)).reshape(-1)            # int64, in index order
-        n = int(cand.numel())
-        out = dict(flags=flags, cand=cand, roots=torch.empty((n, R, 3), dtype=torch.float64, device=dev),
-                   near=torch.empty((n, R), dtype=torch.uint8, device=dev), count=torch.empty(n, dtype=torch.int32, device=dev),
-                   status=torch.empty(n, dtype=torch.uint8, device=dev), nodes=torch.empty(n, dtype=torch.int32, device=dev))
-        if n:
-            breaks = [torch.from_numpy(np.ascontiguousarray(b, np.float64)).to(dev) for b in plan.breaks]
-            nv.check(L.bsk_roots3_isolate(*grid, *(b.data_ptr() for b in breaks), scale.data_ptr(), cand.data_ptr(), n,
-                                          out["roots"].data_ptr(), out["near"].data_ptr(), out["count"].data_ptr(),
-                                          out["status"].data_ptr(), out["nodes"].data_ptr(), stream))
-            LAST_PATHS.append(_last())
-        keep = (~torch.isnan(out["roots"][:, :, 0])).to(torch.uint8).contiguous()
-        which = torch.nonzero(out["near"].reshape(-1)).reshape(-1)
-        if int(which.numel()):
-            table = torch.cumsum(flags.reshape(-1), 0, dtype=torch.int64) - 1
-            nv.check(L.bsk_roots3_merge(R, out["roots"].data_ptr(), B, *plan.ncells, *(b.data_ptr() for b in breaks), cand.data_ptr(), n,
-                                        flags.data_ptr(), table.data_ptr(), which.data_ptr(), int(which.numel()), keep.data_ptr(),
-                                        stream))
-            LAST_PATHS.append(_last())
-        out["keep"] = keep
-    return out
+    -> dict of flags, cand, roots (ncand, R, 3), near, count, status, nodes, keep (``_cells.isolate_cells``)."""
+    rows, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(scale, np.float64)
+    return _cells.isolate_cells(_cells.Host(), "bsk_roots3", rows, plan, mask, scale, slots(*plan.order), LAST_PATHS)
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -507,11 +391,11 @@ def zeros3_batch(spline, coefs=None, _path=None):
     byte per coefficient, 3 B n0 n1 n2 bytes) is read back and the windowed sums over the cells are NumPy's
     (``zero_cells``), as in roots2.  The coefficients themselves, the extracted rows and the zeros stay on the device."""
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = _cells.pick_path(_path, FORCE_PATH)
     _check_spline(spline)
     K = tuple(int(k) for k in spline.order)
     n0, n1, n2 = (len(spline.knots[d]) - spline.order[d] for d in range(3))
-    on_device = coefs is not None and roots._is_torch(coefs)
+    on_device = coefs is not None and _cells.is_torch(coefs)
     if coefs is None:
         if spline.nDep != 3:
             raise ValueError("zeros3_batch takes three dependent variables, or coefs (B, 3, n0, n1, n2)")
@@ -529,68 +413,32 @@ def zeros3_batch(spline, coefs=None, _path=None):
         raise ValueError(f"coefs must have the shape (B, 3, {n0}, {n1}, {n2})")
     B = int(coefs.shape[0])
     plan = Plan3(spline.order, spline.knots)
-    nc = tuple(plan.ncells)
-    ncell = nc[0] * nc[1] * nc[2]
+    ncell = int(np.prod(plan.ncells))
     kdtype = np.result_type(*(spline.knots[d].dtype for d in range(3)))
     if path is None:
         path = "device" if B * ncell >= DEVICE_MIN_CELLS else "host"
 
-    def zero_rows(mask):
-        at = np.argwhere(mask)
-        b = [np.asarray(x, np.float64) for x in plan.breaks]
-        cols = [at[:, 0].astype(np.float64)]
-        for a in range(3):
-            cols += [b[a][at[:, a + 1]], b[a][at[:, a + 1] + 1]]
-        return np.stack(cols, axis=1).reshape(-1, 7)
-
     if B == 0:
-        if on_device:
-            return (torch.empty((0, 3), dtype=getattr(torch, kdtype.name), device=coefs.device),
-                    torch.zeros(1, dtype=torch.int64, device=coefs.device), np.empty((0, 7)),
-                    torch.zeros((0,) + nc, dtype=torch.uint8, device=coefs.device))
-        return np.empty((0, 3), kdtype), np.zeros(1, np.int64), np.empty((0, 7)), np.zeros((0,) + nc, np.uint8)
+        return _cells.collect(_cells.Device(coefs.device) if on_device else _cells.Host(), plan, kdtype, 0)
 
     if path == "device":
         import torch
         data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        dev = data.device
+        be = _cells.Device(data.device)
         wide = data.abs()
-        d_scale = wide.amax(dim=(2, 3, 4)).contiguous()
-        small = ((wide < (d_scale * EPS)[:, :, None, None, None]) | (d_scale == 0.0)[:, :, None, None, None]).cpu().numpy()
+        scale = wide.amax(dim=(2, 3, 4)).contiguous()
+        small = ((wide < (scale * EPS)[:, :, None, None, None]) | (scale == 0.0)[:, :, None, None, None]).cpu().numpy()
         mask = zero_cells(small, plan).astype(np.uint8)
         rows = data.reshape((3 * B, n0, n1, n2))
         if plan.steps:
             rows, ran = refinement.run_device(rows, plan.steps)
             LAST_PATHS.extend(ran)
-        res = _run_device(rows.contiguous(), plan, mask, d_scale)
-        kept = res["keep"].reshape(-1).bool()
-        system = torch.div(res["cand"], ncell, rounding_mode="floor")
-        system = system[:, None].expand(-1, slots(*K)).reshape(-1)[kept]
-        values = res["roots"].reshape(-1, 3)[kept]
-        order = torch.argsort(values[:, 2], stable=True)
-        order = order[torch.argsort(values[order, 1], stable=True)]
-        order = order[torch.argsort(values[order, 0], stable=True)]
-        order = order[torch.argsort(system[order], stable=True)]
-        values = values[order].to(getattr(torch, kdtype.name))
-        offsets = torch.searchsorted(system[order].contiguous(), torch.arange(B + 1, device=dev))
-        status = torch.zeros(B * ncell, dtype=torch.uint8, device=dev)
-        status[res["cand"]] = res["status"]
-        status = status.reshape((B,) + nc)
-        if not on_device:
-            values, offsets, status = values.cpu().numpy(), offsets.cpu().numpy(), status.cpu().numpy()
-        return values, offsets, zero_rows(mask), status
-
-    _, rows, mask, scale = tables(spline, coefs)
-    res = _run_host(rows, plan, mask, scale)
-    kept = res["keep"].reshape(-1).astype(bool)
-    system = np.repeat(res["cand"] // ncell, slots(*K))[kept]
-    values = res["roots"].reshape(-1, 3)[kept]
-    order = np.lexsort((values[:, 2], values[:, 1], values[:, 0], system))
-    values = values[order].astype(kdtype)
-    offsets = np.searchsorted(system[order], np.arange(B + 1)).astype(np.int64)
-    status = np.zeros(B * ncell, np.uint8)
-    status[res["cand"]] = res["status"]
-    return values, offsets, zero_rows(mask), status.reshape((B,) + nc)
+        res = _cells.isolate_cells(be, "bsk_roots3", rows.contiguous(), plan, mask, scale, slots(*K), LAST_PATHS)
+    else:
+        be = _cells.Host()
+        _, rows, mask, scale = tables(spline, coefs)
+        res = _run_host(rows, plan, mask, scale)             # makes rows and scale contiguous
+    return _cells.collect(be, plan, kdtype, B, slots(*K), res, mask, numpy_out=not on_device)
 
 
 def zeros3(self, _path=None):

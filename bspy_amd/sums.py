@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _native as nv
 from . import refinement
+from ._cells import is_torch as _is_torch, pick_path
 
 # Elements of the result from which the device path is taken.  AN ESTIMATE, not a measurement: refinement's threshold
 #  carried over; tools/sum_time.py prints the host / device crossover table that is to replace it.
@@ -37,17 +38,6 @@ FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 SCAN_CHUNK = 32            # rows per chunk of the running sum's association (bsk_sum.hpp)
 SUM_MAX_RANK = 8
-
-
-def _is_torch(a):
-    return type(a).__module__.startswith("torch")
-
-
-def _pick(path):
-    path = path if path is not None else FORCE_PATH
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
 
 
 # ------------------------------------------------------------------------------------------ the running sum
@@ -145,7 +135,7 @@ def _scan(scan_map, tensor, axis, segments):
 
 def integrate(self, with_respect_to=0, _path=None, _segments=None):
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = pick_path(_path, FORCE_PATH)
     if not (0 <= with_respect_to < self.nInd):
         raise ValueError("Invalid with_respect_to")
     iv = with_respect_to
@@ -336,7 +326,7 @@ def _rebuilt(s, order, knots, coefs):
 
 def common_basis(splines, indMap=None, _path=None):
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = pick_path(_path, FORCE_PATH)
     splines = tuple(splines)
     out = []
     for s, (order, knots, stages) in zip(splines, _basis_plans(splines, indMap)):
@@ -352,7 +342,7 @@ def common_basis(splines, indMap=None, _path=None):
 # ------------------------------------------------------------------------------------------ add, subtract, translate
 def add(self, other, indMap=None, _path=None, _sign=1):
     del LAST_PATHS[:]
-    path = _pick(_path)
+    path = pick_path(_path, FORCE_PATH)
     if not (self.nDep == other.nDep):
         raise ValueError("self and other must have same nDep")
     if indMap is None:
@@ -448,7 +438,7 @@ def basis_row(knots, order, u):
 
 def contract(self, uvw, _path=None):
     del LAST_PATHS[:]
-    _pick(_path)
+    pick_path(_path, FORCE_PATH)
     domain = self.domain()
     steps, fixed, dtype = [], [], self.coefs.dtype
     for iv in range(self.nInd):

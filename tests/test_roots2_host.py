@@ -302,6 +302,54 @@ def test_the_halving_never_flips_a_hull():
 
 
 # ------------------------------------------------------------------------------------------ the library's own uses
+def test_zero_cells_is_the_window_check():
+    """``zero_cells`` (windowed sums, one axis at a time, for any number of variables) against the statement read cell by
+    cell: a cell is zero when all K0 x ... x K(n-1) coefficients of its window are small, for any component.  Mixed orders
+    and an interior knot of multiplicity 2 on every axis, so that the knot cells of consecutive spans are not consecutive."""
+    import itertools
+    axis = {2: [0.0, 0, 1, 1, 2, 3, 3], 3: [0.0, 0, 0, 1, 1, 2, 3, 3, 3], 4: [0.0, 0, 0, 0, 1, 2, 2, 3, 4, 4, 4, 4]}
+    rng = np.random.default_rng(20)
+    for order in ((2, 4), (3, 2, 4)):
+        plan = roots2.Plan2(order, [np.array(axis[k]) for k in order])
+        cells = [p.cell for p in plan.axes]
+        assert all((np.diff(c) > 1).any() for c in cells)
+        ncoef = tuple(len(axis[k]) - k for k in order)
+        for B in (1, 3):
+            small = rng.random((B, len(order)) + ncoef) < 0.5
+            forced = tuple(nc - 1 for nc in plan.ncells)
+            window = tuple(slice(c[i] - k + 1, c[i] + 1) for c, i, k in zip(cells, forced, order))
+            small[(B - 1, 1) + window] = True
+            got = roots2.zero_cells(small, plan)
+            assert got.dtype == bool and got.shape == (B,) + tuple(plan.ncells) and got[(B - 1,) + forced]
+            for b in range(B):
+                for at in itertools.product(*(range(nc) for nc in plan.ncells)):
+                    window = tuple(slice(c[i] - k + 1, c[i] + 1) for c, i, k in zip(cells, at, order))
+                    assert small[(b, 0) + window].shape == tuple(order)
+                    want = any(small[(b, d) + window].all() for d in range(len(order)))
+                    assert got[(b,) + at] == want, (order, b, at)
+            assert not got.all()
+
+
+def test_layout_of_the_coefficients_does_not_matter():
+    """Knots in Bezier form already: no extraction step copies the coefficients, so the drivers see the caller's array.
+    Fortran-ordered and strided coefficients give the bytes of the C-ordered ones, through the spline and through coefs=."""
+    knots = [np.array([0.0] * 4 + [1.0] * 4)] * 2
+    rng = np.random.default_rng(2)
+    coefs = rng.standard_normal((2,) + (4,) * 2)
+    c = dict(order=[4] * 2, knots=knots)
+    assert not roots2.Plan2(c["order"], knots).steps
+    want = roots2.zeros2_batch(make_spline(c, coefs), _path="host")
+    assert len(want[0]) >= 1 and not want[3].any()
+    wide = rng.standard_normal((2,) + (4,) * 1 + (8,))
+    wide[..., ::2] = coefs
+    for other in (np.asfortranarray(coefs), wide[..., ::2]):
+        assert not other.flags.c_contiguous and np.array_equal(other, coefs)
+        for got in (roots2.zeros2_batch(make_spline(c, other), _path="host"),
+                    roots2.zeros2_batch(make_spline(c, coefs), coefs=other[None], _path="host")):
+            assert got[0].tobytes() == want[0].tobytes() and got[1].tolist() == want[1].tolist()
+            assert got[2].tobytes() == want[2].tobytes() and got[3].tobytes() == want[3].tobytes()
+
+
 def test_batch_equals_single_calls():
     c = load_case("rand_44")
     rng = np.random.default_rng(11)

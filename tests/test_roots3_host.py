@@ -336,6 +336,26 @@ def test_the_halving_never_flips_a_hull():
 
 
 # ------------------------------------------------------------------------------------------ the library's own uses
+def test_layout_of_the_coefficients_does_not_matter():
+    """Knots in Bezier form already: no extraction step copies the coefficients, so the drivers see the caller's array.
+    Fortran-ordered and strided coefficients give the bytes of the C-ordered ones, through the spline and through coefs=."""
+    knots = [np.array([0.0] * 4 + [1.0] * 4)] * 3
+    rng = np.random.default_rng(5)
+    coefs = rng.standard_normal((3,) + (4,) * 3)
+    c = dict(order=[4] * 3, knots=knots)
+    assert not roots3.Plan3(c["order"], knots).steps
+    want = roots3.zeros3_batch(make_spline(c, coefs), _path="host")
+    assert len(want[0]) >= 1 and not want[3].any()
+    wide = rng.standard_normal((3,) + (4,) * 2 + (8,))
+    wide[..., ::2] = coefs
+    for other in (np.asfortranarray(coefs), wide[..., ::2]):
+        assert not other.flags.c_contiguous and np.array_equal(other, coefs)
+        for got in (roots3.zeros3_batch(make_spline(c, other), _path="host"),
+                    roots3.zeros3_batch(make_spline(c, coefs), coefs=other[None], _path="host")):
+            assert got[0].tobytes() == want[0].tobytes() and got[1].tolist() == want[1].tolist()
+            assert got[2].tobytes() == want[2].tobytes() and got[3].tobytes() == want[3].tobytes()
+
+
 def test_batch_equals_single_calls():
     c = load_case("rand_333")
     rng = np.random.default_rng(11)
