@@ -1,34 +1,22 @@
 """
-What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``) share, written once: the path switch, the
-host band loop, the per-axis Bezier plan, the zero-cell table, and two backends, ``Host`` (NumPy, the ``*_host`` entry
-points) and ``Device`` (torch CUDA tensors, the kernels on the current stream), on which a driver is written once.
+What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``) share, written once: the host band
+loop, the per-axis Bezier plan, the zero-cell table, and the drivers of ``zeros2_batch`` and ``zeros3_batch`` on the two
+backends of bspy_amd/_backend.py (``Host``, ``Device``, the path switch: passed on under their names here).
 
 A driver is a function of a backend: it allocates with ``be.empty``, hands ``be.ptr(a)`` to ``be.call(name, ...)`` and uses
-the few array operations below.  The families differ in their kernels and in the plain-Python statement that says what a
+the backend's few array operations.  The families differ in their kernels and in the plain-Python statement that says what a
 kernel computes; those stay in their modules.  ``isolate_cells`` (flag, isolate, merge) and ``collect`` are the drivers of
 ``zeros2_batch`` and ``zeros3_batch``.
 """
-import ctypes
 import math
 
 import numpy as np
 
 from . import _native as nv
 from . import refinement
+from ._backend import Device, Host, is_torch, pick_path          # the cell families and the tools take them from here
 
 EPS = float(np.finfo(np.float64).eps)
-
-
-def is_torch(a):
-    return type(a).__module__.startswith("torch")
-
-
-def pick_path(path, forced):
-    """``_path`` of a call, else the module's ``FORCE_PATH``."""
-    path = path if path is not None else forced
-    if path not in (None, "device", "host"):
-        raise ValueError("_path must be None, 'device' or 'host'")
-    return path
 
 
 def band_host(data, steps, log):
@@ -105,136 +93,6 @@ def zero_cells(small, plan):
         hi = plan.axes[a].cell + 1
         total = np.take(run, hi, axis=a + 2) - np.take(run, hi - K, axis=a + 2)
     return (total == int(np.prod(plan.order))).any(axis=1)
-
-
-# ------------------------------------------------------------------------------------------ the backends
-class Host:
-    """NumPy arrays and the ``*_host`` entry points."""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-    def empty(self, shape, dtype):
-        return np.empty(shape, dtype)
-
-    def zeros(self, shape, dtype):
-        return np.zeros(shape, dtype)
-
-    def put(self, a, dtype):
-        return np.ascontiguousarray(a, dtype)
-
-    def get(self, a):
-        return a
-
-    def ptr(self, a):
-        return None if a is None else a.ctypes.data
-
-    def code(self, a):
-        return nv.dtype_code(a.dtype)
-
-    def cast(self, a, dtype):
-        return a.astype(dtype)
-
-    def nonzero(self, a):
-        return np.flatnonzero(a).astype(np.int64)
-
-    def cumsum(self, a):
-        return np.cumsum(a, dtype=np.int64)
-
-    def isnan(self, a):
-        return np.isnan(a)
-
-    def amax(self, a, axes):
-        return a.max(axis=axes)
-
-    def sum(self, a, axis):
-        return a.sum(axis=axis)
-
-    def repeat(self, a, n):
-        return np.repeat(a, n)
-
-    def lexsort(self, columns):
-        return np.lexsort(columns)
-
-    def searchsorted(self, a, n):
-        return np.searchsorted(a, np.arange(n)).astype(np.int64)
-
-    def call(self, name, *args):
-        nv.check(getattr(nv.lib(), name + "_host")(*args))
-
-
-class Device:
-    """The same on contiguous torch CUDA tensors of ``dev``, the kernels on the stream that is current on entry."""
-
-    def __init__(self, dev):
-        import torch
-        self.torch, self.dev = torch, dev
-
-    def __enter__(self):
-        self._guard = self.torch.cuda.device(self.dev)
-        self._guard.__enter__()
-        self.stream = ctypes.c_void_p(self.torch.cuda.current_stream().cuda_stream)
-        return self
-
-    def __exit__(self, *exc):
-        return self._guard.__exit__(*exc)
-
-    def _dtype(self, dtype):
-        return getattr(self.torch, np.dtype(dtype).name)
-
-    def empty(self, shape, dtype):
-        return self.torch.empty(shape, dtype=self._dtype(dtype), device=self.dev)
-
-    def zeros(self, shape, dtype):
-        return self.torch.zeros(shape, dtype=self._dtype(dtype), device=self.dev)
-
-    def put(self, a, dtype):
-        return self.torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.dev)
-
-    def get(self, a):
-        return a.cpu().numpy()
-
-    def ptr(self, a):
-        return None if a is None else a.data_ptr()
-
-    def code(self, a):
-        return nv.BSK_F32 if a.dtype == self.torch.float32 else nv.BSK_F64
-
-    def cast(self, a, dtype):
-        return a.to(self._dtype(dtype)).contiguous()
-
-    def nonzero(self, a):
-        return self.torch.nonzero(a.reshape(-1)).reshape(-1)             # int64, in index order
-
-    def cumsum(self, a):
-        return self.torch.cumsum(a, 0, dtype=self.torch.int64)
-
-    def isnan(self, a):
-        return self.torch.isnan(a)
-
-    def amax(self, a, axes):
-        return a.amax(dim=axes)
-
-    def sum(self, a, axis):
-        return a.sum(dim=axis)
-
-    def repeat(self, a, n):
-        return self.torch.repeat_interleave(a, n) if is_torch(n) else a[:, None].expand(-1, n).reshape(-1)
-
-    def lexsort(self, columns):
-        order = self.torch.argsort(columns[0], stable=True)
-        for column in columns[1:]:
-            order = order[self.torch.argsort(column[order], stable=True)]
-        return order
-
-    def searchsorted(self, a, n):
-        return self.torch.searchsorted(a.contiguous(), self.torch.arange(n, device=self.dev))
-
-    def call(self, name, *args):
-        nv.check(getattr(nv.lib(), name)(*args, self.stream))
 
 
 # ------------------------------------------------------------------------------------------ the drivers of zeros2 and zeros3

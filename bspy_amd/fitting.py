@@ -23,7 +23,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nv
-from ._cells import pick_path
+from ._backend import Device, Handle, Host, choose, lines, pick_path
 from .collocation import collocation_matrix
 from .device_spline import _is_torch
 
@@ -35,8 +35,9 @@ FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 
 
-class Plan:
+class Plan(Handle):
     """Banded QR of one collocation matrix (``bsk_fit`` handle)."""
+    prefix = "bsk_fit"
 
     def __init__(self, first, values, ncols):
         first = np.ascontiguousarray(first, np.int32)
@@ -44,21 +45,7 @@ class Plan:
         self.nrows, self.order = values.shape
         self.ncols = int(ncols)
         self.first, self.values = first, values
-        handle = ctypes.c_void_p()
-        nv.check(nv.lib().bsk_fit_create(self.nrows, self.ncols, self.order, first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                         values.ctypes.data, ctypes.byref(handle)))
-        self._handle = handle
-
-    def close(self):
-        if self._handle is not None:
-            nv.lib().bsk_fit_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(self.nrows, self.ncols, self.order, first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), values.ctypes.data)
 
     def rank_indicator(self):
         """min |R_jj| / max |R_jj|."""
@@ -75,41 +62,27 @@ class Plan:
         nv.check(nv.lib().bsk_fit_info(self._handle, None, None, band.ctypes.data))
         return band
 
-    def last_kernel(self):
-        return nv.lib().bsk_fit_last_kernel(self._handle).decode()
-
     def solve_host(self, b, outer, inner):
         """b: NumPy (outer, nrows, inner) float32 / float64 -> (outer, ncols, inner) float64."""
-        b = np.ascontiguousarray(b)
-        if b.dtype != np.float32:
-            b = np.ascontiguousarray(b, np.float64)
-        x = np.empty((outer, self.ncols, inner), np.float64)
-        nv.check(nv.lib().bsk_fit_solve_host(self._handle, nv.dtype_code(b.dtype), b.ctypes.data, outer, inner, x.ctypes.data))
+        be = Host()
+        b = be.put(b, np.float32 if np.asarray(b).dtype == np.float32 else np.float64)
+        x = be.empty((outer, self.ncols, inner), np.float64)
+        be.call("bsk_fit_solve", self._handle, be.code(b), be.ptr(b), outer, inner, be.ptr(x))
         return x
 
     def sweep(self, b, outer, inner):
         """b: contiguous torch CUDA tensor of outer * nrows * inner float32 / float64 -> (outer, ncols, inner) float64."""
-        import torch
-        with torch.cuda.device(b.device):
-            x = torch.empty((outer, self.ncols, inner), dtype=torch.float64, device=b.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            nv.check(nv.lib().bsk_fit_sweep(self._handle, _torch_code(b), b.data_ptr(), outer, inner, x.data_ptr(), stream))
+        with Device(b.device) as be:
+            x = be.empty((outer, self.ncols, inner), np.float64)
+            be.call("bsk_fit_sweep", self._handle, be.code(b), be.ptr(b), outer, inner, be.ptr(x))
         return x
 
     def residual_rows(self, b, x, outer, inner):
         """Sum over all lines of (b - A x)^2 for every row (NumPy, nrows), from device b and x."""
-        import torch
         sumsq = np.empty(self.nrows, np.float64)
-        with torch.cuda.device(b.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            nv.check(nv.lib().bsk_fit_residual(self._handle, _torch_code(b), b.data_ptr(), x.data_ptr(), outer, inner,
-                                               sumsq.ctypes.data, stream))
+        with Device(b.device) as be:
+            be.call("bsk_fit_residual", self._handle, be.code(b), be.ptr(b), be.ptr(x), outer, inner, sumsq.ctypes.data)
         return sumsq
-
-
-def _torch_code(t):
-    import torch
-    return nv.BSK_F32 if t.dtype == torch.float32 else nv.BSK_F64
 
 
 def residual_rows_host(first, values, b, x):
@@ -170,38 +143,25 @@ def _is_spline_input(data):
     return flat.dtype == object and flat.size > 0 and all(hasattr(flat[0], a) for a in ("nInd", "nDep", "knots", "coefs"))
 
 
-def _to_device(a):
-    import torch
-    if _is_torch(a):
-        return a
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _to_host(a):
-    if _is_torch(a):
-        return a.detach().cpu().numpy()
-    return a
+    return a.detach().cpu().numpy() if _is_torch(a) else a
 
 
 def _solve_variable(first, values, ncols, data, outer, nrows, inner, want_norms, fix_rows, path):
     """One solve of one variable: data viewed as (outer, nrows, inner) -> ((outer, ncols, inner), row sums of squares or None)."""
-    lines = outer * inner
+    count = outer * inner
     order = values.shape[1]
-    plan = Plan(first, values, ncols)
-    try:
+    with Plan(first, values, ncols) as plan:
         if fix_rows or plan.deficient():
             b = np.asarray(_to_host(data), np.float64).reshape(outer, nrows, inner)
-            flat = np.moveaxis(b, 1, 0).reshape(nrows, lines)
+            flat = np.moveaxis(b, 1, 0).reshape(nrows, count)
             x, resid = fallback_solve(dense_matrix(first, values, ncols), flat, fix_rows)
             LAST_PATHS.append("fallback")
             x = np.ascontiguousarray(np.moveaxis(x.reshape(ncols, outer, inner), 0, 1))
             return x, (np.einsum("rl,rl->r", resid, resid) if want_norms else None)
-        if path is None:
-            path = "device" if order <= DEVICE_MAX_ORDER and lines >= DEVICE_MIN_LINES else "host"
+        path = choose(path, order <= DEVICE_MAX_ORDER, count >= DEVICE_MIN_LINES, f"the device path covers orders up to {DEVICE_MAX_ORDER}")
         if path == "device":
-            if order > DEVICE_MAX_ORDER:
-                raise ValueError(f"the device path covers orders up to {DEVICE_MAX_ORDER}")
-            b = _to_device(data).contiguous()
+            b = (data if _is_torch(data) else Device.current().put(data, data.dtype)).contiguous()
             x = plan.sweep(b, outer, inner)
             LAST_PATHS.append(plan.last_kernel())
             return x, (plan.residual_rows(b, x, outer, inner) if want_norms else None)
@@ -209,8 +169,6 @@ def _solve_variable(first, values, ncols, data, outer, nrows, inner, want_norms,
         x = plan.solve_host(b, outer, inner)
         LAST_PATHS.append(plan.last_kernel())
         return x, (residual_rows_host(first, values, b, x) if want_norms else None)
-    finally:
-        plan.close()
 
 
 def least_squares(uValues, dataPoints, order=None, knots=None, compression=0.0, tolerance=None, fixEnds=False,
@@ -280,8 +238,7 @@ def least_squares(uValues, dataPoints, order=None, knots=None, compression=0.0, 
     for iInd in range(nInd):
         u, o = uValues[iInd], order[iInd]
         nrows = shape[iInd + 1]
-        outer = int(np.prod(shape[:iInd + 1], dtype=np.int64))
-        inner = int(np.prod(shape[iInd + 2:], dtype=np.int64))
+        outer, inner = lines(shape, iInd + 1, nrows)
         fix_rows = [r for r in range(nrows) if u[r] == u[0] or u[r] == u[-1]] if fixEnds else []
         while True:
             ncols = len(knots[iInd]) - o

@@ -32,7 +32,7 @@ import math
 import numpy as np
 
 from . import _native as nv
-from ._cells import is_torch as _is_torch, pick_path
+from ._backend import FLOATS, Device, Handle, Host, choose, is_torch as _is_torch, pick_path
 from .refinement import knot_cell, support_cell
 
 # Elements of the result from which the device path is taken.  AN ESTIMATE, not a measurement: refinement's threshold
@@ -41,6 +41,7 @@ from .refinement import knot_cell, support_cell
 DEVICE_MIN_ELEMENTS = 1 << 16
 DEVICE_MIN_K, DEVICE_MAX_K = 2, 6
 DEVICE_MAX_M, HOST_MAX_M = 2, 3
+UNCOVERED = f"the device path covers one or two mapped variables of orders {DEVICE_MIN_K} to {DEVICE_MAX_K}"
 FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 
@@ -115,8 +116,9 @@ def _descend(knots, order, first, done, u, state):
     return out
 
 
-class ProductMap:
+class ProductMap(Handle):
     """The operators of M >= 1 mapped variables (``bsk_product`` handle).  variables: [(f, g, W, nIn1, nIn2)]."""
+    prefix = "bsk_product"
 
     def __init__(self, variables):
         self.M = len(variables)
@@ -130,12 +132,9 @@ class ProductMap:
         self.k2 = [w.shape[2] for w in self.W]
         i32 = lambda values: (ctypes.c_int32 * self.M)(*values)
         i32p = ctypes.POINTER(ctypes.c_int32)
-        handle = ctypes.c_void_p()
-        nv.check(nv.lib().bsk_product_create(
-            self.M, i32(self.nIn1), i32(self.nIn2), i32(self.nOut), i32(self.k1), i32(self.k2),
-            (i32p * self.M)(*[a.ctypes.data_as(i32p) for a in self.f]), (i32p * self.M)(*[a.ctypes.data_as(i32p) for a in self.g]),
-            nv.ptr_array([w.ctypes.data for w in self.W]), ctypes.byref(handle)))
-        self._handle = handle
+        self._open(self.M, i32(self.nIn1), i32(self.nIn2), i32(self.nOut), i32(self.k1), i32(self.k2),
+                   (i32p * self.M)(*[a.ctypes.data_as(i32p) for a in self.f]), (i32p * self.M)(*[a.ctypes.data_as(i32p) for a in self.g]),
+                   nv.ptr_array([w.ctypes.data for w in self.W]))
 
     @classmethod
     def from_knots(cls, pairs):
@@ -146,20 +145,6 @@ class ProductMap:
             knots.append(tbar)
             variables.append((*product_map(knots1, k1, knots2, k2, tbar), len(knots1) - k1, len(knots2) - k2))
         return cls(variables), knots
-
-    def close(self):
-        if self._handle is not None:
-            nv.lib().bsk_product_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def last_kernel(self):
-        return nv.lib().bsk_product_last_kernel(self._handle).decode()
 
     def covered(self):
         """Whether the device path has kernels for this map."""
@@ -178,36 +163,28 @@ class ProductMap:
             acc += V[:, l] * b[self.g[0] + l].astype(np.float64)
         return acc.astype(a.dtype)
 
-    def _check(self, a_shape, b_shape, terms):
-        if tuple(a_shape[1:]) != tuple(self.nIn1) or tuple(b_shape[1:]) != tuple(self.nIn2):
+    def apply(self, be, a, b, terms):
+        """The launch: a (PA, *nIn1) and b (PB, *nIn2), the entered backend's contiguous arrays of one float32 / float64
+        type; terms (P, T, 3): NumPy plane table -> (P, *nOut) of that type."""
+        if tuple(a.shape[1:]) != tuple(self.nIn1) or tuple(b.shape[1:]) != tuple(self.nIn2):
             raise ValueError(f"the map takes a of shape (PA, {self.nIn1}) and b of shape (PB, {self.nIn2})")
         terms = np.ascontiguousarray(terms, np.int32)
         if terms.ndim != 3 or terms.shape[2] != 3 or terms.size == 0:
             raise ValueError("terms must have shape (P, T, 3) with P, T >= 1")
-        return terms
+        code = be.code(a)
+        out = be.empty((terms.shape[0], *self.nOut), FLOATS[code])
+        be.call("bsk_product_apply", self._handle, code, be.ptr(a), a.shape[0], be.ptr(b), b.shape[0],
+                terms.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), terms.shape[0], terms.shape[1], be.ptr(out))
+        return out
 
     def apply_host(self, a, b, terms):
         """a: NumPy (PA, *nIn1), b: (PB, *nIn2), the same float32 / float64 type; terms (P, T, 3) -> (P, *nOut)."""
-        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-        terms = self._check(a.shape, b.shape, terms)
-        out = np.empty((terms.shape[0], *self.nOut), a.dtype)
-        nv.check(nv.lib().bsk_product_apply_host(self._handle, nv.dtype_code(a.dtype), a.ctypes.data, a.shape[0], b.ctypes.data,
-                                                 b.shape[0], terms.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                 terms.shape[0], terms.shape[1], out.ctypes.data))
-        return out
+        return self.apply(Host(), np.ascontiguousarray(a), np.ascontiguousarray(b), terms)
 
     def apply_device(self, a, b, terms):
         """a, b: contiguous torch CUDA tensors of one float type -> CUDA tensor (P, *nOut) of that type."""
-        import torch
-        terms = self._check(a.shape, b.shape, terms)
-        with torch.cuda.device(a.device):
-            out = torch.empty((terms.shape[0], *self.nOut), dtype=a.dtype, device=a.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
-            nv.check(nv.lib().bsk_product_apply(self._handle, code, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0],
-                                                terms.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), terms.shape[0],
-                                                terms.shape[1], out.data_ptr(), stream))
-        return out
+        with Device(a.device) as be:
+            return self.apply(be, a, b, terms)
 
 
 # ------------------------------------------------------------------------------------------ the plane table
@@ -250,7 +227,7 @@ def apply(maps, a, b, terms):
     if a.dtype != b.dtype or a.dtype not in (torch.float32, torch.float64):
         raise TypeError("product.apply takes two float32 or two float64 tensors")
     if not maps.covered():
-        raise ValueError(f"the device path covers one or two mapped variables of orders {DEVICE_MIN_K} to {DEVICE_MAX_K}")
+        raise ValueError(UNCOVERED)
     out = maps.apply_device(a.contiguous(), b.contiguous(), terms)
     LAST_PATHS[:] = [maps.last_kernel()]
     return out
@@ -258,17 +235,10 @@ def apply(maps, a, b, terms):
 
 def _run(maps, a, b, terms, path):
     """a, b: NumPy in the canonical layout, one dtype.  Returns NumPy (P, *nOut)."""
-    path = path if path is not None else FORCE_PATH
-    if path is None:
-        size = terms.shape[0] * int(np.prod(maps.nOut, dtype=np.int64))
-        path = "device" if maps.covered() and size >= DEVICE_MIN_ELEMENTS else "host"
-    if path == "device":
-        if not maps.covered():
-            raise ValueError(f"the device path covers one or two mapped variables of orders {DEVICE_MIN_K} to {DEVICE_MAX_K}")
-        import torch
-        out = maps.apply_device(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), terms).cpu().numpy()
-    else:
-        out = maps.apply_host(a, b, terms)
+    size = terms.shape[0] * int(np.prod(maps.nOut, dtype=np.int64))
+    path = choose(path if path is not None else FORCE_PATH, maps.covered(), size >= DEVICE_MIN_ELEMENTS, UNCOVERED)
+    with (Device.current() if path == "device" else Host()) as be:
+        out = be.get(maps.apply(be, be.put(a, a.dtype), be.put(b, b.dtype), terms))
     LAST_PATHS.append(maps.last_kernel())
     return out
 
@@ -329,14 +299,11 @@ def multiply(self, other, indMap=None, productType="S", _path=None):
         f, g, W = product_map(self.knots[ind1], self.order[ind1], other.knots[ind2], other.order[ind2], tbar[at])
         variables.append((f, g, W, self.nCoef[ind1], other.nCoef[ind2]))
     UA, UB = int(np.prod(rest1, dtype=np.int64)), int(np.prod(rest2, dtype=np.int64))
-    maps = ProductMap(variables)
-    try:
+    with ProductMap(variables) as maps:
         if a.size == 0 or b.size == 0:
             out = np.empty((len(dep) * UA * UB, *maps.nOut), dtype)
         else:
             out = _run(maps, a, b, plane_table(dep, UA, UB), _path)
-    finally:
-        maps.close()
 
     # (component, unmapped of self, unmapped of other, mapped) -> self's variables with the mapped ones in place, then other's
     out = out.reshape((len(dep), *rest1, *rest2, *maps.nOut))

@@ -38,22 +38,21 @@ kernels compute (DESIGN.md sections 17 and 18); the host path uses ``bsk_band_ap
 
     device path   the coefficient tensor goes to the device once; per round ``bsk_band_absmax`` (band_absmax /
                   band_absmax_line + band_absmax_fold) for the residuals, one ``bsk_band_apply`` for the removal,
-                  ``refinement.run_device`` for all but the last refinement step of the certificate and
-                  ``absmax(..., minus=original)`` for the last one: the refined tensor of the original's size is not
+                  ``refinement.run_steps`` for all but the last refinement step of the certificate and the maxima
+                  against ``minus=original`` for the last one: the refined tensor of the original's size is not
                   written for that step.  Only the (groups, nOut) maxima cross to the host.
     host path     the same operators on the CPU: small tensors, and K = order + 1 above 8
+
+Both paths are one loop on a backend of bspy_amd/_backend.py (``Host`` or ``Device``).
 
 ``_path="device" | "host"`` (or ``reduction.FORCE_PATH``) pins the path; a spline with a variable of order above 7 takes
 the host path whatever is asked.  ``LAST_PATHS`` lists the kernels of the last call, ``LAST_ROUNDS`` per variable the
 list of knot indices removed in each round.
 """
-import ctypes
-
 import numpy as np
 
-from . import _cells
-from . import _native as nv
 from . import refinement
+from ._backend import Device, Host, is_torch, lines, pick_path
 from .refinement import BandMap
 
 # Elements of the coefficient tensor from which remove_knots takes the device path: the whole call on both paths
@@ -191,12 +190,13 @@ def select(rho, order, tolerance):
 
 
 # ------------------------------------------------------------------------------------------ maxima
-def _geometry(band, shape, axis):
-    if shape[axis] != band.nIn:
-        raise ValueError(f"axis {axis} has {shape[axis]} entries, the map takes {band.nIn}")
-    outer = int(np.prod(shape[:axis], dtype=np.int64))
-    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
-    return outer, inner
+def _absmax(be, band, data, axis, groups, minus=None):
+    """The launch of ``absmax`` and ``absmax_host``: data (and minus, or None), the entered backend's contiguous arrays;
+    axis not negative.  Returns the backend's (groups, band.nOut) float64."""
+    outer, inner = lines(data.shape, axis, band.nIn)
+    out = be.empty((groups, band.nOut), np.float64)
+    be.call("bsk_band_absmax", band._handle, be.code(data), be.ptr(data), outer, inner, groups, be.ptr(minus), be.ptr(out))
+    return out
 
 
 def absmax(band, tensor, axis, groups=1, minus=None):
@@ -204,27 +204,21 @@ def absmax(band, tensor, axis, groups=1, minus=None):
     (float32 / float64); groups divides the product of the extents in front of ``axis``; minus: None or a CUDA tensor of
     the result's shape.  Returns a (groups, band.nOut) float64 CUDA tensor.  ``LAST_PATHS`` holds this call's kernel."""
     import torch
-    if not (_cells.is_torch(tensor) and tensor.is_cuda):
+    if not (is_torch(tensor) and tensor.is_cuda):
         raise TypeError("reduction.absmax takes a torch CUDA tensor")
     if tensor.dtype not in (torch.float32, torch.float64):
         raise TypeError("reduction.absmax takes float32 or float64")
     axis = axis % tensor.dim()
-    outer, inner = _geometry(band, tensor.shape, axis)
-    if outer * inner == 0:
+    if 0 in lines(tensor.shape, axis, band.nIn):
         raise ValueError("reduction.absmax: empty tensor")
-    a = tensor.contiguous()
     shape = list(tensor.shape)
     shape[axis] = band.nOut
     if minus is not None:
         if list(minus.shape) != shape or minus.dtype != tensor.dtype or minus.device != tensor.device:
             raise ValueError("reduction.absmax: minus must have the result's shape, type and device")
         minus = minus.contiguous()
-    with torch.cuda.device(a.device):
-        out = torch.empty((groups, band.nOut), dtype=torch.float64, device=a.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
-        nv.check(nv.lib().bsk_band_absmax(band._handle, code, a.data_ptr(), outer, inner, groups,
-                                          minus.data_ptr() if minus is not None else None, out.data_ptr(), stream))
+    with Device(tensor.device) as be:
+        out = _absmax(be, band, tensor.contiguous(), axis, groups, minus)
     LAST_PATHS[:] = [band.last_kernel()]
     return out
 
@@ -232,85 +226,24 @@ def absmax(band, tensor, axis, groups=1, minus=None):
 def absmax_host(band, a, axis, groups=1, minus=None):
     """The same values for NumPy arrays (``bsk_band_absmax_host``): (groups, band.nOut) float64."""
     a = np.ascontiguousarray(a)
-    axis = axis % a.ndim
-    outer, inner = _geometry(band, a.shape, axis)
-    out = np.empty((groups, band.nOut), np.float64)
     if minus is not None:
         minus = np.ascontiguousarray(minus, a.dtype)
-    nv.check(nv.lib().bsk_band_absmax_host(band._handle, nv.dtype_code(a.dtype), a.ctypes.data, outer, inner, groups,
-                                           minus.ctypes.data if minus is not None else None, out.ctypes.data))
-    return out
+    return _absmax(Host(), band, a, axis % a.ndim, groups, minus)
 
 
 def apply_fma_host(band, a, axis):
     """``band`` along ``axis`` of a NumPy array with the kernels' fused sums (``bsk_band_apply_fma_host``)."""
     a = np.ascontiguousarray(a)
-    axis = axis % a.ndim
-    outer, inner = _geometry(band, a.shape, axis)
-    shape = list(a.shape)
-    shape[axis] = band.nOut
-    out = np.empty(shape, a.dtype)
-    if out.size:
-        nv.check(nv.lib().bsk_band_apply_fma_host(band._handle, nv.dtype_code(a.dtype), a.ctypes.data, outer, inner, out.ctypes.data))
-    return out
+    return band.along(Host(), a, axis % a.ndim, fused=True)
 
 
-class _Host:
-    """The operators of the statement on NumPy arrays."""
-    name = "host"
-
-    def __init__(self, coefs):
-        self.original = np.ascontiguousarray(coefs)
-
-    def start(self):
-        return self.original
-
-    def apply(self, band, data, axis):
-        out = apply_fma_host(band, data, axis)
-        LAST_PATHS.append("host band")
-        return out
-
-    def absmax(self, band, data, axis, groups, minus=None):
-        out = absmax_host(band, data, axis, groups, minus)
-        LAST_PATHS.append("host band_absmax")
-        return out
-
-    def finish(self, data):
-        return data
-
-
-class _Device:
-    """The same on torch CUDA tensors: the data stays on the device, the maxima come back."""
-    name = "device"
-
-    def __init__(self, coefs):
-        import torch
-        self.original = torch.from_numpy(np.ascontiguousarray(coefs)).cuda()
-
-    def start(self):
-        return self.original
-
-    def apply(self, band, data, axis):
-        out = refinement._apply(band, data, axis)
+def _maxima(be, first, w, data, axis, groups, minus=None):
+    """``_absmax`` of the band (first, w) on the entered backend's array, brought to NumPy: of a round only these maxima
+    cross to the host.  ``LAST_PATHS`` receives what ran."""
+    with BandMap(first, w, data.shape[axis]) as band:
+        out = be.get(_absmax(be, band, data, axis, groups, minus))
         LAST_PATHS.append(band.last_kernel())
-        return out
-
-    def absmax(self, band, data, axis, groups, minus=None):
-        kernels = list(LAST_PATHS)
-        out = absmax(band, data, axis, groups, minus).cpu().numpy()
-        LAST_PATHS[:] = kernels + [band.last_kernel()]
-        return out
-
-    def finish(self, data):
-        return data.cpu().numpy()
-
-
-def _with_band(first, w, nIn, call):
-    band = BandMap(first, w, nIn)
-    try:
-        return call(band)
-    finally:
-        band.close()
+    return out
 
 
 def _origin(knots, original):
@@ -325,20 +258,17 @@ def _origin(knots, original):
     return origin
 
 
-def _certificate(engine, candidate, order, knots, original_knots, reduced, nDep):
-    """E_d of the statement's step 3 for the tensor ``candidate`` on ``knots``."""
+def _certificate(be, candidate, original, order, knots, original_knots, reduced, nDep):
+    """E_d of the statement's step 3 for the backend's tensor ``candidate`` on ``knots`` against ``original``."""
     steps = []
     for iv in reduced:
         if len(knots[iv]) != len(original_knots[iv]):
             origin = _origin(knots[iv], original_knots[iv])
             steps.append((iv + 1, *refinement.refine_map(knots[iv], order[iv], original_knots[iv], 0, origin=origin)))
     steps = refinement._ordered(steps, candidate.shape)
-    data = candidate
-    for axis, first, w in steps[:-1]:
-        data = _with_band(first, w, data.shape[axis], lambda band: engine.apply(band, data, axis))
+    data = refinement.run_steps(be, candidate, steps[:-1], LAST_PATHS, fused=True)
     axis, first, w = steps[-1]
-    E = _with_band(first, w, data.shape[axis], lambda band: engine.absmax(band, data, axis, nDep, engine.original))
-    return E.max(axis=1)
+    return _maxima(be, first, w, data, axis, nDep, original).max(axis=1)
 
 
 def _finite_or_inf(a):
@@ -346,7 +276,7 @@ def _finite_or_inf(a):
 
 
 def remove_knots(self, tolerance=1e-14, nLeft=0, nRight=0, _path=None):
-    path = _cells.pick_path(_path, FORCE_PATH)
+    path = pick_path(_path, FORCE_PATH)
     del LAST_PATHS[:]
     LAST_ROUNDS[:] = [[] for _ in range(self.nInd)]
     coefs = np.ascontiguousarray(self.coefs)
@@ -358,44 +288,45 @@ def remove_knots(self, tolerance=1e-14, nLeft=0, nRight=0, _path=None):
         path = "device" if coefs.size >= DEVICE_MIN_ELEMENTS else "host"
     if not covered:
         path = "host"                       # bsk_band_absmax: BSK_ERR_UNSUPPORTED for K outside [2, 8]
-    engine = (_Device if path == "device" else _Host)(coefs)
+    be = Device.current() if path == "device" else Host()
 
     nDep = self.nDep
     scale = np.abs(coefs.reshape(nDep, -1)).max(axis=1).astype(np.float64)
     scale[scale == 0.0] = 1.0
     original_knots = [np.asarray(t, np.float64) for t in self.knots]
-    data = engine.start()
-    for iv in range(self.nInd):
-        k, axis = order[iv], iv + 1
-        reduced = range(iv + 1)
-        while len(knots[iv]) - k > k:
-            t = knots[iv]
-            _, first, v = residual_map(t, k, nLeft, nRight)
-            bad = ~np.all(np.isfinite(v), axis=1)
-            v[bad] = 0.0
-            res = _with_band(first, v, data.shape[axis], lambda band: engine.absmax(band, data, axis, nDep))
-            rho = _finite_or_inf((res / scale[:, None]).max(axis=0))
-            rho[bad] = np.inf
-            kept = select(rho, k, tolerance)
-            accepted = False
-            while kept:
-                try:
-                    newKnots, first, w = removal_map(t, k, kept, nLeft, nRight)
-                except ValueError:
-                    break                   # a weight that is not finite: this set has no removal
-                candidate = _with_band(first, w, data.shape[axis], lambda band: engine.apply(band, data, axis))
-                trial = list(knots)
-                trial[iv] = newKnots
-                E = _certificate(engine, candidate, order, [np.asarray(x, np.float64) for x in trial], original_knots, reduced, nDep)
-                if np.max(_finite_or_inf(E / scale)) <= tolerance:
-                    accepted = True
+    original = data = be.put(coefs, coefs.dtype)
+    with be:
+        for iv in range(self.nInd):
+            k, axis = order[iv], iv + 1
+            reduced = range(iv + 1)
+            while len(knots[iv]) - k > k:
+                t = knots[iv]
+                _, first, v = residual_map(t, k, nLeft, nRight)
+                bad = ~np.all(np.isfinite(v), axis=1)
+                v[bad] = 0.0
+                res = _maxima(be, first, v, data, axis, nDep)
+                rho = _finite_or_inf((res / scale[:, None]).max(axis=0))
+                rho[bad] = np.inf
+                kept = select(rho, k, tolerance)
+                accepted = False
+                while kept:
+                    try:
+                        newKnots, first, w = removal_map(t, k, kept, nLeft, nRight)
+                    except ValueError:
+                        break                   # a weight that is not finite: this set has no removal
+                    candidate = refinement.run_steps(be, data, [(axis, first, w)], LAST_PATHS, fused=True)
+                    trial = [np.asarray(x, np.float64) for x in knots]
+                    trial[iv] = np.asarray(newKnots, np.float64)
+                    E = _certificate(be, candidate, original, order, trial, original_knots, reduced, nDep)
+                    if np.max(_finite_or_inf(E / scale)) <= tolerance:
+                        accepted = True
+                        break
+                    kept = kept[:len(kept) // 2]
+                if not accepted:
                     break
-                kept = kept[:len(kept) // 2]
-            if not accepted:
-                break
-            data, knots[iv] = candidate, newKnots
-            LAST_ROUNDS[iv].append([int(i) for i in kept])
-    result = engine.finish(data)
+                data, knots[iv] = candidate, newKnots
+                LAST_ROUNDS[iv].append([int(i) for i in kept])
+    result = be.get(data)
     if result is coefs:
         result = coefs.copy()
     return refinement._rebuild(self, order, knots, result)
@@ -415,10 +346,9 @@ def remove_knot(self, iKnot, nLeft=0, nRight=0):
         raise ValueError("remove_knot: an operator weight is not finite (a fixed unknown whose pivot is zero); "
                          "the reference returns inf / nan coefficients")
     coefs = np.ascontiguousarray(self.coefs)
-    engine = _Host(coefs)
-    out = _with_band(first, w, coefs.shape[1], lambda band: engine.apply(band, coefs, 1))
-    window = np.ascontiguousarray(coefs[:, iKnot - k:iKnot + 1])
-    residual = _with_band(np.zeros(1, np.int32), v, k + 1, lambda band: apply_fma_host(band, window, 1))
+    out = refinement.run_steps(Host(), coefs, [(1, first, w)], LAST_PATHS, fused=True)
+    with BandMap(np.zeros(1, np.int32), v, k + 1) as band:
+        residual = apply_fma_host(band, coefs[:, iKnot - k:iKnot + 1], 1)
     return type(self)(1, self.nDep, self.order, out.shape[1:], [newKnots], out), np.abs(residual[:, 0])
 
 

@@ -30,43 +30,27 @@ import itertools
 
 import numpy as np
 
-from . import _native as nv
-from . import _cells          # (it imports this module too: use its names at call time only)
+from ._backend import FLOATS, Device, Handle, Host, choose, is_torch, lines, pick_path
 
 # Elements of the coefficient tensor (the larger of input and result) from which the device path is taken.  The key is
 # the total element count: see DESIGN.md section 13 for its standing.
 DEVICE_MIN_ELEMENTS = 1 << 16
 DEVICE_MIN_K, DEVICE_MAX_K = 2, 8
+UNCOVERED = f"the device path covers K from {DEVICE_MIN_K} to {DEVICE_MAX_K}"
 FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 
 
-class BandMap:
+class BandMap(Handle):
     """out[j] = sum_t w[j, t] * in[first[j] + t] (``bsk_band`` handle).  first: (nOut,) non-decreasing; w: (nOut, K)."""
+    prefix = "bsk_band"
 
     def __init__(self, first, w, nIn):
         self.first = np.ascontiguousarray(first, np.int32)
         self.w = np.ascontiguousarray(w, np.float64)
         self.nOut, self.K = self.w.shape
         self.nIn = int(nIn)
-        handle = ctypes.c_void_p()
-        nv.check(nv.lib().bsk_band_create(self.nIn, self.nOut, self.K, self.first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                          self.w.ctypes.data, ctypes.byref(handle)))
-        self._handle = handle
-
-    def close(self):
-        if self._handle is not None:
-            nv.lib().bsk_band_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def last_kernel(self):
-        return nv.lib().bsk_band_last_kernel(self._handle).decode()
+        self._open(self.nIn, self.nOut, self.K, self.first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.w.ctypes.data)
 
     def apply_line(self, x):
         """One line in NumPy, the statement of what the library computes: fp64 products added in the order of t."""
@@ -76,22 +60,36 @@ class BandMap:
             acc += self.w[:, t] * x[self.first + t].astype(np.float64)
         return acc.astype(x.dtype)
 
+    def apply(self, be, a, outer, inner, fused=False):
+        """The launch: a, the entered backend's contiguous float32 / float64 array of outer * nIn * inner values ->
+        (outer, nOut, inner), same type.  fused: sums as the kernels form them; on the host that is an entry point of
+        its own, which has no device twin."""
+        code = be.code(a)
+        out = be.empty((outer, self.nOut, inner), FLOATS[code])
+        name = "bsk_band_apply_fma" if fused and isinstance(be, Host) else "bsk_band_apply"
+        be.call(name, self._handle, code, be.ptr(a), outer, inner, be.ptr(out))
+        return out
+
     def apply_host(self, a, outer, inner):
         """a: NumPy float32 / float64 of outer * nIn * inner values -> (outer, nOut, inner), same dtype."""
-        a = np.ascontiguousarray(a)
-        out = np.empty((outer, self.nOut, inner), a.dtype)
-        nv.check(nv.lib().bsk_band_apply_host(self._handle, nv.dtype_code(a.dtype), a.ctypes.data, outer, inner, out.ctypes.data))
-        return out
+        return self.apply(Host(), np.ascontiguousarray(a), outer, inner)
 
     def apply_device(self, a, outer, inner):
         """a: contiguous torch CUDA tensor of outer * nIn * inner float32 / float64 -> (outer, nOut, inner), same dtype."""
-        import torch
-        with torch.cuda.device(a.device):
-            out = torch.empty((outer, self.nOut, inner), dtype=a.dtype, device=a.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
-            nv.check(nv.lib().bsk_band_apply(self._handle, code, a.data_ptr(), outer, inner, out.data_ptr(), stream))
-        return out
+        with Device(a.device) as be:
+            return self.apply(be, a, outer, inner)
+
+    def along(self, be, data, axis, fused=False):
+        """``apply`` along ``axis`` (not negative) of the backend's contiguous array: the result has nOut entries there.
+        A tensor without lines launches nothing."""
+        shape = list(data.shape)
+        outer, inner = lines(shape, axis, self.nIn)
+        shape[axis] = self.nOut
+        if outer * inner == 0:
+            return be.empty(shape, FLOATS[be.code(data)])
+        if type(be) is Host and not fused:                  # under its public name, which callers may wrap
+            return self.apply_host(data, outer, inner).reshape(shape)
+        return self.apply(be, data, outer, inner, fused).reshape(shape)
 
 
 # ------------------------------------------------------------------------------------------ operators
@@ -245,24 +243,23 @@ def apply(band, tensor, axis):
     return out
 
 
-def _apply(band, tensor, axis):
+def _device_floats(tensor):
+    """What every device-resident entry point takes: a torch CUDA tensor of float32 or float64."""
     import torch
-    if not (_cells.is_torch(tensor) and tensor.is_cuda):
+    if not (is_torch(tensor) and tensor.is_cuda):
         raise TypeError("refinement.apply takes a torch CUDA tensor")
     if tensor.dtype not in (torch.float32, torch.float64):
         raise TypeError("refinement.apply takes float32 or float64")
+
+
+def _apply(band, tensor, axis):
+    _device_floats(tensor)
     axis = axis % tensor.dim()
-    shape = list(tensor.shape)
-    if shape[axis] != band.nIn:
-        raise ValueError(f"axis {axis} has {shape[axis]} entries, the map takes {band.nIn}")
+    lines(tensor.shape, axis, band.nIn)                      # (this message comes before the next one)
     if not (DEVICE_MIN_K <= band.K <= DEVICE_MAX_K):
-        raise ValueError(f"the device path covers K from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
-    outer = int(np.prod(shape[:axis], dtype=np.int64))
-    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
-    shape[axis] = band.nOut
-    if outer * inner == 0:
-        return torch.empty(shape, dtype=tensor.dtype, device=tensor.device)
-    return band.apply_device(tensor.contiguous(), outer, inner).reshape(shape)
+        raise ValueError(UNCOVERED)
+    with Device(tensor.device) as be:
+        return band.along(be, tensor.contiguous(), axis)
 
 
 def _ordered(steps, shape):
@@ -276,63 +273,48 @@ def steps_covered(steps):
     return all(DEVICE_MIN_K <= np.shape(w)[1] <= DEVICE_MAX_K for _, _, w in steps)
 
 
+def run_steps(be, data, steps, log, fused=False):
+    """The band pipeline: data, the entered backend's contiguous array (nDep, *nCoef), through steps [(axis, first, w)]
+    in ``_ordered``'s order, one ``BandMap`` per step; the intermediates stay where the backend keeps them.  ``log``
+    receives what every step ran (nothing for an empty result); fused: ``BandMap.apply``'s.  Returns the backend's array."""
+    for axis, first, w in _ordered(steps, data.shape):
+        with BandMap(first, w, data.shape[axis]) as band:
+            data = band.along(be, data, axis, fused)
+            if 0 not in data.shape:
+                log.append(band.last_kernel())
+    return data
+
+
 def run_device(data, steps):
     """data: torch CUDA tensor (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step with the band kernels and
     returns the CUDA tensor: the intermediates of a pipeline stay on the device.  Returns (tensor, kernels that ran)."""
+    _device_floats(data)
+    if not steps_covered(steps):
+        raise ValueError(UNCOVERED)
     ran = []
-    for axis, first, w in _ordered(steps, data.shape):
-        band = BandMap(first, w, data.shape[axis])
-        try:
-            data = _apply(band, data, axis)
-            if data.numel():
-                ran.append(band.last_kernel())
-        finally:
-            band.close()
-    return data, ran
+    with Device(data.device) as be:
+        return run_steps(be, data.contiguous(), steps, ran), ran
 
 
 def _run(coefs, steps, path):
-    """coefs: NumPy (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step, the one that shrinks the tensor most
-    first and the one that grows it most last (the operators of different variables commute), and returns NumPy."""
-    path = _cells.pick_path(path, FORCE_PATH)
+    """coefs: NumPy (nDep, *nCoef); steps: [(axis, first, w)].  Applies every step (``run_steps``) and returns NumPy."""
+    path = pick_path(path, FORCE_PATH)
     del LAST_PATHS[:]
     if not steps:
         return coefs
     steps = _ordered(steps, coefs.shape)
-    bands = [(axis, BandMap(first, w, coefs.shape[axis])) for axis, first, w in steps]
-    try:
-        if coefs.size == 0:
-            shape = list(coefs.shape)
-            for axis, band in bands:
+    if coefs.size == 0:
+        shape = list(coefs.shape)
+        for axis, first, w in steps:
+            with BandMap(first, w, shape[axis]) as band:            # the library still checks the step
                 shape[axis] = band.nOut
-            return np.empty(shape, coefs.dtype)
-        covered = all(DEVICE_MIN_K <= band.K <= DEVICE_MAX_K for _, band in bands)
-        if path is None:
-            size = coefs.size
-            for axis, band in bands:
-                size = max(size, size // band.nIn * band.nOut)
-            path = "device" if covered and size >= DEVICE_MIN_ELEMENTS else "host"
-        if path == "device":
-            if not covered:
-                raise ValueError(f"the device path covers K from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
-            import torch
-            data = torch.from_numpy(np.ascontiguousarray(coefs)).cuda()
-            for axis, band in bands:
-                data = _apply(band, data, axis)
-                LAST_PATHS.append(band.last_kernel())
-            return data.cpu().numpy()
-        data = coefs
-        for axis, band in bands:
-            shape = list(data.shape)
-            outer = int(np.prod(shape[:axis], dtype=np.int64))
-            inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
-            shape[axis] = band.nOut
-            data = band.apply_host(data, outer, inner).reshape(shape)
-            LAST_PATHS.append(band.last_kernel())
-        return data
-    finally:
-        for _, band in bands:
-            band.close()
+        return np.empty(shape, coefs.dtype)
+    size = coefs.size
+    for axis, first, _ in steps:
+        size = max(size, size // coefs.shape[axis] * len(first))
+    path = choose(path, steps_covered(steps), size >= DEVICE_MIN_ELEMENTS, UNCOVERED)
+    with (Device.current() if path == "device" else Host()) as be:
+        return be.get(run_steps(be, be.put(coefs, coefs.dtype), steps, LAST_PATHS))
 
 
 # ------------------------------------------------------------------------------------------ knot vectors

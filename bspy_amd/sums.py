@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _native as nv
 from . import refinement
-from ._cells import is_torch as _is_torch, pick_path
+from ._backend import FLOATS, Device, Handle, Host, choose, is_torch as _is_torch, lines, pick_path
 
 # Elements of the result from which the device path is taken.  AN ESTIMATE, not a measurement: refinement's threshold
 #  carried over; tools/sum_time.py prints the host / device crossover table that is to replace it.
@@ -38,32 +38,18 @@ FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 SCAN_CHUNK = 32            # rows per chunk of the running sum's association (bsk_sum.hpp)
 SUM_MAX_RANK = 8
+RANK_UNCOVERED = f"the device path covers a rank of at most {SUM_MAX_RANK} after merging"
 
 
 # ------------------------------------------------------------------------------------------ the running sum
-class ScanMap:
+class ScanMap(Handle):
     """out[0] = 0, out[j + 1] = sum_{i <= j} g[i] * in[i] (``bsk_scan`` handle).  g: (n,) float64."""
+    prefix = "bsk_scan"
 
     def __init__(self, g):
         self.g = np.ascontiguousarray(g, np.float64)
         self.n = len(self.g)
-        handle = ctypes.c_void_p()
-        nv.check(nv.lib().bsk_scan_create(self.n, self.g.ctypes.data, ctypes.byref(handle)))
-        self._handle = handle
-
-    def close(self):
-        if self._handle is not None:
-            nv.lib().bsk_scan_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def last_kernel(self):
-        return nv.lib().bsk_scan_last_kernel(self._handle).decode()
+        self._open(self.n, self.g.ctypes.data)
 
     def apply_line(self, x):
         """One line in NumPy, the statement of what the library computes on every path: fp64 products, each rounded;
@@ -81,23 +67,23 @@ class ScanMap:
             carry = carry + local
         return out.astype(x.dtype)
 
-    def apply_host(self, a, outer, inner):
-        """a: NumPy float32 / float64 of outer * n * inner values -> (outer, n + 1, inner), same dtype."""
-        a = np.ascontiguousarray(a)
-        out = np.empty((outer, self.n + 1, inner), a.dtype)
-        nv.check(nv.lib().bsk_scan_apply_host(self._handle, nv.dtype_code(a.dtype), a.ctypes.data, outer, inner, out.ctypes.data))
+    def apply(self, be, a, outer, inner, segments=0):
+        """The launch: a, the entered backend's contiguous float32 / float64 array of outer * n * inner values ->
+        (outer, n + 1, inner), same type.  segments: pieces the kernels cut a line into (0: the library chooses)."""
+        code = be.code(a)
+        out = be.empty((outer, self.n + 1, inner), FLOATS[code])
+        cut = (int(segments),) if isinstance(be, Device) else ()            # the host entry point has no such argument
+        be.call("bsk_scan_apply", self._handle, code, be.ptr(a), outer, inner, be.ptr(out), *cut)
         return out
 
+    def apply_host(self, a, outer, inner):
+        """a: NumPy float32 / float64 of outer * n * inner values -> (outer, n + 1, inner), same dtype."""
+        return self.apply(Host(), np.ascontiguousarray(a), outer, inner)
+
     def apply_device(self, a, outer, inner, segments=0):
-        """a: contiguous torch CUDA tensor of outer * n * inner float32 / float64 -> (outer, n + 1, inner), same dtype.
-        segments: pieces a line is cut into (0: the library chooses)."""
-        import torch
-        with torch.cuda.device(a.device):
-            out = torch.empty((outer, self.n + 1, inner), dtype=a.dtype, device=a.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
-            nv.check(nv.lib().bsk_scan_apply(self._handle, code, a.data_ptr(), outer, inner, out.data_ptr(), int(segments), stream))
-        return out
+        """a: contiguous torch CUDA tensor of outer * n * inner float32 / float64 -> (outer, n + 1, inner), same dtype."""
+        with Device(a.device) as be:
+            return self.apply(be, a, outer, inner, segments)
 
 
 def integral_weights(knots, order):
@@ -110,12 +96,6 @@ def scan(scan_map, tensor, axis, _segments=None):
     """The running sum ``scan_map`` along ``axis`` of a torch CUDA tensor (float32 / float64); returns a new CUDA tensor
     whose extent along ``axis`` is n + 1.  For pipelines that stay on the device.  ``LAST_PATHS`` holds this call's
     kernel."""
-    out = _scan(scan_map, tensor, axis, _segments)
-    LAST_PATHS[:] = [scan_map.last_kernel()] if out.numel() else []
-    return out
-
-
-def _scan(scan_map, tensor, axis, segments):
     import torch
     if not (_is_torch(tensor) and tensor.is_cuda):
         raise TypeError("sums.scan takes a torch CUDA tensor")
@@ -123,14 +103,14 @@ def _scan(scan_map, tensor, axis, segments):
         raise TypeError("sums.scan takes float32 or float64")
     axis = axis % tensor.dim()
     shape = list(tensor.shape)
-    if shape[axis] != scan_map.n:
-        raise ValueError(f"axis {axis} has {shape[axis]} entries, the map takes {scan_map.n}")
-    outer = int(np.prod(shape[:axis], dtype=np.int64))
-    inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
+    outer, inner = lines(shape, axis, scan_map.n)
     shape[axis] += 1
     if outer * inner == 0:
+        LAST_PATHS[:] = []
         return torch.empty(shape, dtype=tensor.dtype, device=tensor.device)
-    return scan_map.apply_device(tensor.contiguous(), outer, inner, segments or 0).reshape(shape)
+    out = scan_map.apply_device(tensor.contiguous(), outer, inner, _segments or 0).reshape(shape)
+    LAST_PATHS[:] = [scan_map.last_kernel()]
+    return out
 
 
 def integrate(self, with_respect_to=0, _path=None, _segments=None):
@@ -144,24 +124,15 @@ def integrate(self, with_respect_to=0, _path=None, _segments=None):
     order[iv] = k + 1
     knots[iv] = np.concatenate((t[:1], t, t[-1:]))
     shape = list(self.coefs.shape)
-    outer = int(np.prod(shape[:iv + 1], dtype=np.int64))
-    inner = int(np.prod(shape[iv + 2:], dtype=np.int64))
+    outer, inner = lines(shape, iv + 1, shape[iv + 1])
     shape[iv + 1] += 1
     if outer * inner == 0:
         return type(self)(self.nInd, self.nDep, order, shape[1:], knots, np.empty(shape, self.coefs.dtype), self.metadata)
-    scan_map = ScanMap(integral_weights(t, k))
-    try:
-        if path is None:
-            path = "device" if outer * inner * shape[iv + 1] >= DEVICE_MIN_ELEMENTS else "host"
-        if path == "device":
-            import torch
-            data = torch.from_numpy(np.ascontiguousarray(self.coefs)).cuda()
-            coefs = scan_map.apply_device(data, outer, inner, _segments or 0).cpu().numpy().reshape(shape)
-        else:
-            coefs = scan_map.apply_host(self.coefs, outer, inner).reshape(shape)
+    path = choose(path, True, outer * inner * shape[iv + 1] >= DEVICE_MIN_ELEMENTS, None)
+    be = Device.current() if path == "device" else Host()
+    with ScanMap(integral_weights(t, k)) as scan_map, be:
+        coefs = be.get(scan_map.apply(be, be.put(self.coefs, self.coefs.dtype), outer, inner, _segments or 0)).reshape(shape)
         LAST_PATHS.append(scan_map.last_kernel())
-    finally:
-        scan_map.close()
     return type(self)(self.nInd, self.nDep, order, shape[1:], knots, coefs, self.metadata)
 
 
@@ -200,16 +171,30 @@ def _i64(values):
     return (ctypes.c_int64 * len(values))(*values)
 
 
+def _add(be, a, b, sign):
+    """a + sign * b, the entered backend's arrays of one float type and one rank, any non-negative strides -> the
+    backend's contiguous array.  One launch; above ``SUM_MAX_RANK`` the host peels the leading axis in Python."""
+    shape, dim, sa, sb = sum_layout(a, b)
+    if len(dim) > SUM_MAX_RANK and isinstance(be, Device):
+        raise ValueError(RANK_UNCOVERED)
+    out = be.empty(shape, FLOATS[be.code(a)])
+    if 0 in shape:
+        return out
+    if len(dim) > SUM_MAX_RANK:                       # more axes than one call takes: the leading axis in Python
+        at = next(i for i, d in enumerate(shape) if d != 1)
+        for i in range(shape[at]):
+            take = lambda x: x if x.shape[at] == 1 else np.take(x, [i], axis=at)
+            index = (slice(None),) * at + (slice(i, i + 1),)
+            out[index] = _add(be, take(a), take(b), sign)
+        return out
+    be.call("bsk_sum_apply", be.code(a), len(dim), _i64(dim), be.ptr(a), _i64(sa), be.ptr(b), _i64(sb), int(sign), be.ptr(out))
+    return out
+
+
 def add_tensors(a, b, sign=1):
     """a + sign * b for torch CUDA tensors of one type (float32 / float64) and one rank whose extents agree or are 1
     (broadcast); any non-negative strides (views made by permute and expand need no copy).  One ``sum_bcast`` launch;
     returns a new contiguous CUDA tensor.  For pipelines that stay on the device.  ``LAST_PATHS`` holds the kernel."""
-    out = _add_device(a, b, sign)
-    LAST_PATHS[:] = [nv.lib().bsk_sum_last_kernel().decode()] if out.numel() else []
-    return out
-
-
-def _add_device(a, b, sign):
     import torch
     if not (_is_torch(a) and _is_torch(b) and a.is_cuda and b.is_cuda):
         raise TypeError("sums.add_tensors takes torch CUDA tensors")
@@ -217,36 +202,15 @@ def _add_device(a, b, sign):
         raise TypeError("sums.add_tensors takes two float32 or two float64 tensors")
     if sign not in (1, -1):
         raise ValueError("sign must be 1 or -1")
-    shape, dim, sa, sb = sum_layout(a, b)
-    if len(dim) > SUM_MAX_RANK:
-        raise ValueError(f"the device path covers a rank of at most {SUM_MAX_RANK} after merging")
-    with torch.cuda.device(a.device):
-        out = torch.empty(shape, dtype=a.dtype, device=a.device)
-        if out.numel() == 0:
-            return out
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        code = nv.BSK_F32 if a.dtype == torch.float32 else nv.BSK_F64
-        nv.check(nv.lib().bsk_sum_apply(code, len(dim), _i64(dim), a.data_ptr(), _i64(sa), b.data_ptr(), _i64(sb), int(sign),
-                                        out.data_ptr(), stream))
+    with Device(a.device) as be:
+        out = _add(be, a, b, sign)
+    LAST_PATHS[:] = [nv.lib().bsk_sum_last_kernel().decode()] if out.numel() else []
     return out
 
 
 def _add_host(a, b, sign):
     """NumPy arrays of one float type, any non-negative strides."""
-    shape, dim, sa, sb = sum_layout(a, b)
-    out = np.empty(shape, a.dtype)
-    if out.size == 0:
-        return out
-    if len(dim) > SUM_MAX_RANK:                       # more axes than one call takes: the leading axis in Python
-        at = next(i for i, d in enumerate(shape) if d != 1)
-        for i in range(shape[at]):
-            take = lambda x: x if x.shape[at] == 1 else np.take(x, [i], axis=at)
-            index = (slice(None),) * at + (slice(i, i + 1),)
-            out[index] = _add_host(take(a), take(b), sign)
-        return out
-    nv.check(nv.lib().bsk_sum_apply_host(nv.dtype_code(a.dtype), len(dim), _i64(dim), a.ctypes.data, _i64(sa), b.ctypes.data,
-                                         _i64(sb), int(sign), out.ctypes.data))
-    return out
+    return _add(Host(), a, b, sign)
 
 
 def _placed(x, sources):
@@ -320,6 +284,17 @@ def _run_stages(coefs, stages, path):
     return coefs, ran
 
 
+def _staged(be, coefs, stages):
+    """NumPy coefs through the stages on the entered backend (``refinement.run_steps``); returns the backend's array.  The host
+    keeps an array that no stage touches as it is, strides and all: the sum takes any strides."""
+    if not stages and isinstance(be, Host):
+        return coefs
+    data = be.put(coefs, coefs.dtype)
+    for steps in stages:
+        data = refinement.run_steps(be, data, steps, LAST_PATHS)
+    return data
+
+
 def _rebuilt(s, order, knots, coefs):
     return type(s)(s.nInd, s.nDep, order, coefs.shape[1:], knots, coefs, s.metadata)
 
@@ -373,37 +348,18 @@ def add(self, other, indMap=None, _path=None, _sign=1):
     size = self.nDep * int(np.prod(nCoef, dtype=np.int64))
     if size == 0:
         return type(self)(len(order), self.nDep, order, nCoef, knots, np.empty((self.nDep, *nCoef), dtype), self.metadata)
-    if path is None:
-        rank = len(sum_layout(_placed(np.empty((self.nDep, *nCoef[:self.nInd]), np.int8), own),
-                              _placed(np.empty((other.nDep, *shape2), np.int8), source))[1])
-        covered = one_type and refinement.steps_covered(steps) and rank <= SUM_MAX_RANK
-        path = "device" if covered and size >= DEVICE_MIN_ELEMENTS else "host"
-    if path == "device":
-        if not one_type:
-            raise ValueError("the device path takes two splines of one coefficient dtype")
-        if not refinement.steps_covered(steps):
-            raise ValueError(f"the device path covers K from {refinement.DEVICE_MIN_K} to {refinement.DEVICE_MAX_K}")
-        import torch
-        a = torch.from_numpy(np.ascontiguousarray(self.coefs)).cuda()
-        b = torch.from_numpy(np.ascontiguousarray(other.coefs)).cuda()
-        for stage in stages1:
-            a, ran = refinement.run_device(a, stage)
-            LAST_PATHS.extend(ran)
-        for stage in stages2:
-            b, ran = refinement.run_device(b, stage)
-            LAST_PATHS.extend(ran)
-        out = _add_device(_placed(a, own), _placed(b, source), _sign)
-        LAST_PATHS.append(nv.lib().bsk_sum_last_kernel().decode())
-        coefs = out.cpu().numpy()
-    else:
-        a, ran = _run_stages(self.coefs, stages1, "host")
-        LAST_PATHS.extend(ran)
-        b, ran = _run_stages(other.coefs, stages2, "host")
-        LAST_PATHS.extend(ran)
-        common = np.result_type(a.dtype, b.dtype)           # two dtypes: summed in float64, rounded to self's
-        coefs = _add_host(_placed(a.astype(common, copy=False), own), _placed(b.astype(common, copy=False), source), _sign)
-        coefs = coefs.astype(dtype, copy=False)
-        LAST_PATHS.append(nv.lib().bsk_sum_last_kernel().decode())
+    rank = len(sum_layout(_placed(np.empty((self.nDep, *nCoef[:self.nInd]), np.int8), own),
+                          _placed(np.empty((other.nDep, *shape2), np.int8), source))[1])
+    why = ("the device path takes two splines of one coefficient dtype" if not one_type else
+           refinement.UNCOVERED if not refinement.steps_covered(steps) else RANK_UNCOVERED)
+    path = choose(path, one_type and refinement.steps_covered(steps) and rank <= SUM_MAX_RANK, size >= DEVICE_MIN_ELEMENTS, why)
+    with (Device.current() if path == "device" else Host()) as be:
+        a, b = _staged(be, self.coefs, stages1), _staged(be, other.coefs, stages2)
+        if not one_type:                                    # host only: summed in float64, rounded to self's
+            common = np.result_type(a.dtype, b.dtype)
+            a, b = a.astype(common, copy=False), b.astype(common, copy=False)
+        coefs = be.get(_add(be, _placed(a, own), _placed(b, source), _sign)).astype(dtype, copy=False)
+    LAST_PATHS.append(nv.lib().bsk_sum_last_kernel().decode())
     return type(self)(len(order), self.nDep, order, nCoef, knots, coefs, self.metadata)
 
 

@@ -561,3 +561,16 @@ def operator_scale_cases():
         return (4,), [t], rng.standard_normal((3, len(t) - 4)).astype(dt)
     return {"A": A, "B": B, "C": C, "roots_b": roots_b, "roots_curves": {dt: many_spans(dt) for dt in (f64, f32)},
             "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "domains": SCALE_DOMAINS, "domains_f32": SCALE_DOMAINS_F32}
+
+
+def band_pipeline(dtype):
+    """(data, steps): a (2, 12, 9, 8) tensor and one band step on each of its three variables, K = 2, 4 and 8; the step on
+    axis 2 shrinks, the one on axis 3 keeps the extent, the one on axis 1 grows (tests/test_host_logic.py runs them on the
+    host, tests/test_gpu_refine.py on the device)."""
+    rng = np.random.default_rng(11)
+    data = rng.standard_normal((2, 12, 9, 8)).astype(dtype)
+    steps = []
+    for axis, K, n_out in ((1, 2, 15), (2, 4, 5), (3, 8, 8)):
+        first = np.sort(rng.integers(0, data.shape[axis] - K + 1, n_out)).astype(np.int32)
+        steps.append((axis, first, rng.random((n_out, K))))
+    return data, steps

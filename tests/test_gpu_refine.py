@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import cases
 from bspy_amd import Spline, refinement
 from conftest import GOLDEN, observe
 from test_refine_host import NAMES, check_golden, load_case, make_spline, random_knots, run_case
@@ -121,6 +122,47 @@ def test_layouts(dtype, order, m, inserted):
         inner = int(np.prod(shape[axis + 1:], dtype=np.int64))
         compare(band, a, axis, "band_apply_line" if inner == 1 else "band_apply", f"order {order}")
     band.close()
+
+
+def test_run_steps_on_the_device_is_the_step_by_step_apply():
+    """The band pipeline on the Device backend (refinement.run_steps) against refinement.apply step by step, bit for bit
+    and kernel for kernel: the tensor of tests/test_host_logic.py and a curve, on the default stream and on a second one."""
+    from bspy_amd._backend import Device
+    second = torch.cuda.Stream()
+    for dtype in (np.float64, np.float32):
+        data, steps = cases.band_pipeline(dtype)
+        for array, todo, kernels in ((data, steps, ["band_apply", "band_apply_line", "band_apply"]),
+                                     (np.ascontiguousarray(data[:, :, 0, 0]), steps[:1], ["band_apply_line"])):
+            t = torch.from_numpy(array).cuda()
+            want, ran = t, []
+            for axis, first, w in refinement._ordered(todo, t.shape):
+                with refinement.BandMap(first, w, want.shape[axis]) as band:
+                    want = refinement.apply(band, want, axis)
+                    ran.append(band.last_kernel())
+            assert ran == kernels
+            torch.cuda.synchronize()
+            for stream in (torch.cuda.current_stream(), second):
+                log = []
+                with torch.cuda.stream(stream), Device(t.device) as be:
+                    got = refinement.run_steps(be, t, todo, log)
+                stream.synchronize()
+                assert log == ran
+                assert got.dtype == want.dtype and got.shape == want.shape and got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
+
+
+def test_run_device_refuses_what_the_kernels_do_not_take():
+    """The device-resident pipeline keeps refinement.apply's checks: a tensor that is not float32 / float64 or not on the
+    GPU is a TypeError before anything is launched, not data handed to the kernels as doubles."""
+    _, steps = cases.band_pipeline(np.float64)
+    good = torch.zeros((2, 12, 9, 8), dtype=torch.float64, device="cuda")
+    for bad in (good.half(), good.to(torch.bfloat16), good.to(torch.int32)):
+        with pytest.raises(TypeError, match="refinement.apply takes float32 or float64"):
+            refinement.run_device(bad, steps)
+    for bad in (good.cpu(), good.cpu().numpy()):
+        with pytest.raises(TypeError, match="refinement.apply takes a torch CUDA tensor"):
+            refinement.run_device(bad, steps)
+    out, ran = refinement.run_device(good, steps)
+    assert tuple(out.shape) == (2, 15, 5, 8) and ran == ["band_apply", "band_apply_line", "band_apply"]
 
 
 def test_row_block_multiples_and_long_lines():

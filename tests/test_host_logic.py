@@ -299,6 +299,113 @@ def test_collocation_derivative_orders():
 
 
 # ---------------------------------------------------------------------------------------------
+# what the operator families share (bspy_amd/_backend.py): the handle, the line geometry, the path switch, and the band
+# pipeline written on a backend (refinement.run_steps)
+# ---------------------------------------------------------------------------------------------
+def _handles():
+    """One open handle of each family: (handle, a host apply on it, what last_kernel() says after that)."""
+    from bspy_amd import fitting, product, refinement, sums
+    rng = np.random.default_rng(5)
+    t = np.array([0, 0, 0, .5, 1, 1, 1.0])                                # order 3, four coefficients
+    line = rng.standard_normal((1, 4, 1))
+    band = refinement.BandMap(*refinement.differentiate_map(t, 3), 4)
+    scan = sums.ScanMap(sums.integral_weights(t, 3))
+    maps, _ = product.ProductMap.from_knots([(t, 3, t, 3)])
+    u = np.linspace(0, 1, 9)                                              # the hat functions on 0, .5, 1 at nine points
+    first = (u >= 0.5).astype(np.int32)
+    plan = fitting.Plan(first, np.stack([1 + first - 2 * u, 2 * u - first], axis=1), 3)
+    rhs = rng.standard_normal((1, 9, 1))
+    return [(band, lambda: band.apply_host(line, 1, 1), "host band"),
+            (scan, lambda: scan.apply_host(line, 1, 1), "host scan"),
+            (maps, lambda: maps.apply_host(line[:, :, 0], line[:, :, 0], np.array([[[0, 0, 1]]], np.int32)), "host product"),
+            (plan, lambda: plan.solve_host(rhs, 1, 1), "host plan")]
+
+
+def test_handles_close_once_and_refuse_calls_when_closed():
+    from bspy_amd._backend import Handle
+    for handle, run, name in _handles():
+        assert isinstance(handle, Handle)
+        with handle as same:
+            assert same is handle and handle._handle is not None
+            assert np.all(np.isfinite(run()))
+            assert handle.last_kernel() == name
+        assert handle._handle is None                                      # with closes
+        handle.close()                                                     # a second close is harmless
+        with pytest.raises(bspy_amd.BskError):                             # the library refuses the NULL handle
+            run()
+
+
+def test_lines_counts_the_lines_along_an_axis():
+    from bspy_amd import reduction, refinement
+    from bspy_amd._backend import lines
+    for shape in [(3, 4, 5), (1, 7), (7, 1), (2, 0, 3), (0, 4), (4, 0), (2, 3, 0), (1, 1, 1), (5,)]:
+        for axis, n in enumerate(shape):
+            outer, inner = lines(shape, axis, n)
+            assert type(outer) is int and type(inner) is int
+            assert outer == sum(1 for _ in np.ndindex(*shape[:axis])) and inner == sum(1 for _ in np.ndindex(*shape[axis + 1:]))
+            with pytest.raises(ValueError, match=f"axis {axis} has {n} entries, the map takes {n + 1}"):
+                lines(shape, axis, n + 1)
+    # a negative axis is its callers' business, as before
+    a = np.random.default_rng(2).standard_normal((2, 4, 3))
+    with refinement.BandMap(*refinement.differentiate_map(np.array([0, 0, 0, .5, 1, 1, 1.0]), 3), 4) as band:
+        assert reduction.apply_fma_host(band, a, -2).tobytes() == reduction.apply_fma_host(band, a, 1).tobytes()
+        assert reduction.absmax_host(band, a, -2, 2).tobytes() == reduction.absmax_host(band, a, 1, 2).tobytes()
+        with pytest.raises(ValueError, match="axis 2 has 3 entries, the map takes 4"):
+            reduction.apply_fma_host(band, a, -1)
+
+
+def test_choose_truth_table():
+    from bspy_amd._backend import choose
+    for covered in (False, True):
+        for large in (False, True):
+            assert choose(None, covered, large, "why") == ("device" if covered and large else "host")
+            assert choose("host", covered, large, "why") == "host"
+            if covered:
+                assert choose("device", covered, large, "why") == "device"
+            else:
+                with pytest.raises(ValueError, match="^why$"):
+                    choose("device", covered, large, "why")
+
+
+def test_backend_imports_the_binding_only_and_either_import_order_works():
+    source = open(os.path.join(ROOT, "bspy_amd", "_backend.py")).read()
+    relative = re.findall(r"^\s*from\s+(\.\S*)\s+import\s+(.+?)\s*$", source, re.M)
+    assert relative == [(".", "_native as nv")], relative
+    assert not re.search(r"^\s*import\s+bspy_amd|^\s*from\s+bspy_amd", source, re.M)
+    for module in ("refinement", "reduction"):
+        assert "_cells" not in open(os.path.join(ROOT, "bspy_amd", module + ".py")).read(), module
+    for order in (("refinement", "_cells"), ("_cells", "refinement")):
+        code = f"import sys; sys.path.insert(0, {ROOT!r})\n" + "".join(f"import bspy_amd.{m}\n" for m in order) + \
+               "assert bspy_amd._cells.Host is bspy_amd._backend.Host and bspy_amd._cells.pick_path is bspy_amd.refinement.pick_path"
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_run_steps_on_the_host_is_the_step_by_step_apply(dtype, fused):
+    from bspy_amd import reduction, refinement
+    from bspy_amd._backend import Host
+    data, steps = cases.band_pipeline(dtype)
+    ordered = refinement._ordered(steps, data.shape)
+    assert [step[0] for step in ordered] == [2, 3, 1]
+    want = data
+    for axis, first, w in ordered:
+        with refinement.BandMap(first, w, want.shape[axis]) as band:
+            if fused:
+                want = reduction.apply_fma_host(band, want, axis)
+            else:
+                shape = list(want.shape)
+                outer, inner = int(np.prod(shape[:axis])), int(np.prod(shape[axis + 1:]))
+                shape[axis] = band.nOut
+                want = band.apply_host(want, outer, inner).reshape(shape)
+    log = []
+    got = refinement.run_steps(Host(), data, steps, log, fused=fused)
+    assert got.dtype == dtype and got.shape == (2, 15, 5, 8) and got.tobytes() == want.tobytes()
+    assert log == 3 * ["host band"]
+
+
+# ---------------------------------------------------------------------------------------------
 # build-time guard of the inline-asm LDS kernels (bspy_amd/csrc/check_lds_hazards.py)
 # ---------------------------------------------------------------------------------------------
 def _hazards(body):

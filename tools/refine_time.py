@@ -76,17 +76,17 @@ def device_time(f, launches, repeats):
 
 def captured(call):
     """Run `call` on the device path and return the launches it made: (first, w, nIn, shape, axis, dtype)."""
-    steps, keep = [], refinement._apply
+    steps, keep = [], refinement.BandMap.along
 
-    def spy(band, tensor, axis):
+    def spy(band, be, tensor, axis, fused=False):
         steps.append((band.first.copy(), band.w.copy(), band.nIn, tuple(tensor.shape), axis, tensor.dtype))
-        return keep(band, tensor, axis)
+        return keep(band, be, tensor, axis, fused)
 
-    refinement._apply = spy
+    refinement.BandMap.along = spy
     try:
         call()
     finally:
-        refinement._apply = keep
+        refinement.BandMap.along = keep
     return steps
 
 
