@@ -39,7 +39,10 @@ float64 whatever the dtypes, float32 is widened first, every product and sum rou
     else status bit 4 and stop.  The local step times the cell's width is the step; the new trial is clamped to the
     domain.  The iterate moves freely across cells;
   * status: 1 the evaluation bound was reached, 2 the foot point is on a domain bound (informational), 4 singular step,
-    8 not iterated.  ``distance`` = sqrt(d2) at the returned parameter, which is rounded once to the knots' dtype.
+    8 not iterated.  ``distance`` = sqrt(d2) at the returned parameter, which is rounded once to the knots' dtype;
+  * scale: the drivers of both paths hand the statement the (widened) coefficients and points x 2^-e, e the binary exponent
+    of max |coefficient| (``norm_exponent``), and return the distances x 2^e: coefficients and points x 2^k give the same
+    parameters, status and steps and the distances x 2^k, bit for bit, wherever inputs and outputs are finite.
 No atomics, no waiting: two runs give the same bytes.
 
 ``_path="device" | "host"`` (or ``project.FORCE_PATH``) pins the path; ``project.LAST_PATHS`` lists what the last call ran.
@@ -424,6 +427,23 @@ def host_tables(spline, samples=None):
     return plan, rows, band_host(rows, plan.sample_steps)
 
 
+def norm_exponent(coefs):
+    """e with max |coefficient| = m 2^e, 1/2 <= m < 1; 0 when that maximum is 0 or not finite.  The statement squares
+    coordinates and multiplies the squares (A + B of ``solve_step``: the fourth power), so both paths work on the
+    coefficients and the points x 2^-e and give the distances back x 2^e.  A power of two commutes with every rounding:
+    in range (|e| <= 250) no bit of a result changes, and out of it the result is the in-range one."""
+    top = float(np.abs(np.asarray(coefs, np.float64)).max(initial=0.0))
+    return int(math.frexp(top)[1]) if 0.0 < top < INF else 0
+
+
+def _ldexp(a, e):
+    """a x 2^e for float64 NumPy arrays and torch tensors alike: in two factors, each a power of two in range (2^e
+    itself need not be); exact unless the result is subnormal, and then the same on both paths."""
+    half = e // 2
+    with np.errstate(over="ignore", under="ignore"):                   # a distance beyond float64 is inf, as in the kernels
+        return a * 2.0 ** half * 2.0 ** (e - half)
+
+
 def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=None):
     """The closest point of the spline to each query point.  ``points``: (nDep, *shape), NumPy float32 / float64 or a torch
     CUDA tensor of those types; ``guess``: (nInd, *shape) of the same kind, takes the place of the seed search.
@@ -469,6 +489,7 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
     N = int(np.prod(shape, dtype=np.int64))
     plan = Plan(spline.order, spline.knots, G)
     kdtype = np.result_type(*(k.dtype for k in spline.knots))
+    e = norm_exponent(spline.coefs)
     if path is None:
         path = "device" if N * max(plan.nsamples, NEWTON_WORK) >= DEVICE_MIN_WORK and refinement.steps_covered(plan.steps) else "host"
 
@@ -482,12 +503,14 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
 
     if path == "device":
         import torch
-        pts = (points if on_device else torch.from_numpy(np.ascontiguousarray(points)).cuda()).double().reshape(nDep, N).contiguous()
+        pts = (points if on_device else torch.from_numpy(np.ascontiguousarray(points)).cuda()).double().reshape(nDep, N)
+        pts = (_ldexp(pts, -e) if e else pts).contiguous()
         dev = pts.device
         start = None
         if guess is not None:
             start = (guess if on_device else torch.from_numpy(np.ascontiguousarray(guess)).to(dev)).double().reshape(nInd, N).contiguous()
         rows = torch.from_numpy(np.ascontiguousarray(spline.coefs)).to(dev).double()   # widened BEFORE the extraction
+        rows = _ldexp(rows, -e) if e else rows
         if plan.steps:
             rows, ran = refinement.run_device(rows, plan.steps)
             LAST_PATHS.extend(ran)
@@ -499,17 +522,21 @@ def project_batch(spline, points, guess=None, samples=None, _path=None, _chunk=N
             grid = grid.contiguous()
         uvw, distance, status, steps = run(_cells.Device(dev), plan, rows, grid, pts, start, chunk)
         uvw = uvw.to(getattr(torch, kdtype.name))
+        distance = _ldexp(distance, e) if e else distance
         if not on_device:
             uvw, distance, status, steps = (a.cpu().numpy() for a in (uvw, distance, status, steps))
     else:
         pts = points.astype(np.float64).reshape(nDep, N)
         start = None if guess is None else guess.astype(np.float64).reshape(nInd, N)
         rows = np.asarray(spline.coefs).astype(np.float64)             # widened BEFORE the extraction
+        if e:
+            pts, rows = _ldexp(pts, -e), _ldexp(rows, -e)
         if plan.steps:
             rows = band_host(rows, plan.steps)
         grid = band_host(rows, plan.sample_steps) if start is None else None
         uvw, distance, status, steps = run_host(plan, rows, grid, pts, start, chunk)
         uvw = uvw.astype(kdtype)
+        distance = _ldexp(distance, e) if e else distance
     return uvw.reshape((nInd,) + shape), distance.reshape(shape), status.reshape(shape), steps.reshape(shape)
 
 

@@ -574,3 +574,141 @@ def band_pipeline(dtype):
         first = np.sort(rng.integers(0, data.shape[axis] - K + 1, n_out)).astype(np.int32)
         steps.append((axis, first, rng.random((n_out, K))))
     return data, steps
+
+
+# ---------------------------------------------------------------------------------------------
+# Scale tests of the cell families (tests/test_scale_cells_host.py, tests/test_gpu_scale_cells.py): zeros2, zeros3,
+# project, contours and remove_knots (DESIGN.md sections 17-21).
+# ---------------------------------------------------------------------------------------------
+CELL_KERNELS = {"zeros2": {"roots2_flag", "roots2_isolate", "roots2_merge"}, "zeros3": {"roots3_flag", "roots3_isolate", "roots3_merge"},
+                "project": {"project_seed", "project_newton"}, "contours": {"contour_flag", "contour_march"},
+                "remove_knots": {"band_absmax", "band_absmax_line"}}
+
+
+class CellCase:
+    """One public batch call of a cell family on [0, 1]: the spline's orders and knots, the coefficients (with their batch
+    axis where the call has one), the family's kernels ``LAST_PATHS`` must name on the device path, and the call's
+    arguments (points, guess, levels, depth, tolerances, ...)."""
+
+    def __init__(self, name, family, order, knots, coefs, kernels, **args):
+        self.name, self.family, self.order, self.knots, self.coefs = name, family, tuple(order), list(knots), coefs
+        self.kernels, self.args = set(kernels), args                # args["optional"]: kernels that may run as well
+
+    @property
+    def kind(self):
+        return "fp32" if self.coefs.dtype == np.float32 else "fp64"
+
+    def replaced(self, knots=None, coefs=None, **args):
+        return CellCase(self.name, self.family, self.order, self.knots if knots is None else knots,
+                        self.coefs if coefs is None else coefs, self.kernels, **{**self.args, **args})
+
+    def with_kernels(self, kernels):
+        return CellCase(self.name, self.family, self.order, self.knots, self.coefs, kernels, **self.args)
+
+
+def cell_knots(rng, order, ncells, dt=np.float64):
+    """Clamped knots on [0, 1] with ncells - 1 simple random interior knots per variable."""
+    return [np.concatenate((k * [0.0], np.sort(rng.random(nc - 1)), k * [1.0])).astype(dt) for k, nc in zip(order, ncells)]
+
+
+def _kind_name(dt):
+    return np.dtype(dt).name
+
+
+def zeros_scale_cases(dt):
+    """zeros2 on 9 x 7 cells and zeros3 on 3 x 2 x 3 cells, B = 3 random systems per order class the kernels instantiate (the
+    candidates straddle a block of 64), one of them with a zero cell in system 0; and the planted systems of
+    tests/test_gpu_roots2.py (test_merge_on_a_3_by_2_grid) and tests/test_gpu_roots3.py (planted), whose zeros on shared
+    edges make the merge kernels run, three times over with factors that keep the zero coefficients zero."""
+    n, out = _kind_name(dt), []
+    for family, ncells, orders in (("zeros2", (9, 7), [(2, 2), (3, 4), (4, 4)]), ("zeros3", (3, 2, 3), [(2, 2, 2), (3, 3, 2), (4, 4, 4)])):
+        nind = len(ncells)
+        flag, isolate, merge = (f"roots{nind}_{s}" for s in ("flag", "isolate", "merge"))
+        for order in orders:
+            rng = np.random.default_rng(1000 * nind + 100 * order[0] + 10 * order[1] + order[-1])
+            knots = cell_knots(rng, order, ncells, dt)
+            ncoef = [len(t) - k for t, k in zip(knots, order)]
+            coefs = rng.standard_normal((3, nind, *ncoef)).astype(dt)
+            out.append(CellCase(f"{family} {order} {n}", family, order, knots, coefs, {flag, isolate}))
+            if order == orders[-1]:
+                holed = coefs.copy()
+                holed[(0, 0) + tuple(slice(0, k) for k in order)] = 0.0
+                out.append(CellCase(f"{family} {order} zero cell {n}", family, order, knots, holed, {flag, isolate}, zero_cells=1))
+        factors = np.array([1.0, -3.0, 0.375], dt).reshape((3,) + (1,) * (nind + 1))
+        if nind == 2:
+            third = 1.0 / 3.0
+            p, q = np.array([1.0, 0.0, -1.0, 1.0]), np.array([1.0, -1.0, 1.0, 2.0])
+            planted = np.stack([np.repeat(p[:, None], 4, axis=1), np.repeat(q[None, :], 4, axis=0)])
+            knots, order = [np.array([0, 0, third, 2 * third, 1, 1.0], dt), np.array([0, 0, 0, 0.5, 1, 1, 1.0], dt)], (2, 3)
+        else:
+            p = np.array([1.0, -1.0, 0.0, 1.0, 2.0])
+            planted = np.stack([np.broadcast_to(p[:, None, None], (5, 5, 5)), np.broadcast_to(p[None, :, None], (5, 5, 5)),
+                                np.broadcast_to(p[None, None, :], (5, 5, 5))])
+            knots, order = [np.array([0, 0, 0, 0.5, 0.5, 1, 1, 1.0], dt)] * 3, (3, 3, 3)
+        out.append(CellCase(f"{family} planted, zeros on shared edges {n}", family, order, knots, (planted[None] * factors).astype(dt),
+                            {flag, isolate, merge}))
+    return out
+
+
+def project_scale_cases(dt):
+    """A curve of order 6 and surfaces of orders (2, 3) and (4, 4), nDep 2 and 3: graphs over the parameters plus noise (the
+    splines of tests/test_gpu_project.py), 300 points of which some lie past the domain's ends, a guess per point inside
+    and slightly outside the domain, and a chunk that cuts the samples into three."""
+    out = []
+    shapes = [((6,), (5,), 2), ((2, 3), (4, 3), 3), ((4, 4), (4, 3), 3)] if dt == np.float64 else [((6,), (5,), 3), ((4, 4), (4, 3), 2)]
+    for order, ncells, ndep in shapes:
+        rng = np.random.default_rng(2000 + 100 * order[0] + 10 * len(order) + ndep)
+        knots = cell_knots(rng, order, ncells, dt)
+        ncoef = [len(t) - k for t, k in zip(knots, order)]
+        coefs = 0.3 * rng.standard_normal((ndep, *ncoef))
+        for a, m in enumerate(ncoef):
+            coefs[a] += np.linspace(0.0, 2.0, m).reshape([-1 if b == a else 1 for b in range(len(ncoef))])
+        points = (1.0 + 1.2 * rng.standard_normal((ndep, 300))).astype(dt)
+        guess = rng.uniform(-0.1, 1.1, (len(order), 300)).astype(dt)
+        nsamples = int(np.prod([nc * k for nc, k in zip(ncells, order)]))
+        out.append(CellCase(f"project {order} nDep {ndep} {_kind_name(dt)}", "project", order, knots, coefs.astype(dt),
+                            {"project_seed", "project_newton"}, points=points, guess=guess, chunk=-(-nsamples // 3)))
+    return out
+
+
+def contour_scale_cases(dt):
+    """Three levels of one bicubic field at depth 4 and three fields (B, n0, n1) of orders (2, 3) on 9 x 7 cells at depth 2
+    (65 or more candidates: the lanes of split level 0 cross a wave)."""
+    n, kernels = _kind_name(dt), {"contour_flag", "contour_march"}
+    rng = np.random.default_rng(3000)
+    k44 = cell_knots(rng, (4, 4), (3, 2), dt)
+    c44 = rng.uniform(-1.0, 1.0, (1, 6, 5)).astype(dt)
+    k23 = cell_knots(rng, (2, 3), (9, 7), dt)
+    c23 = rng.uniform(-1.0, 1.0, (3, 10, 9)).astype(dt)
+    return [CellCase(f"contours (4, 4) three levels depth 4 {n}", "contours", (4, 4), k44, c44, kernels, levels=np.array([-0.2, 0.0, 0.3]), depth=4),
+            CellCase(f"contours (2, 3) three fields depth 2 {n}", "contours", (2, 3), k23, c23, kernels, levels=None, depth=2)]
+
+
+REMOVE_TOLERANCES = (1e-12, 1e-5, 1e-2)
+
+
+def remove_scale_cases(dt):
+    """A coarse, smooth curve and a coarse, smooth (4, 3) surface with the knots to insert into them and the relative size of the noise
+    put on the refined coefficients (between the first two tolerances): the test module refines and perturbs."""
+    n, out = _kind_name(dt), []
+    for tag, order, ncoef, ndep, count, kernels in (("curve", (4,), (12,), 3, (10,), {"band_absmax_line"}),
+                                                     ("surface", (4, 3), (9, 8), 2, (7, 6), {"band_absmax", "band_absmax_line"})):
+        rng = np.random.default_rng(4000 + len(order))
+        knots = cell_knots(rng, order, [m - k + 1 for m, k in zip(ncoef, order)])
+        greville = [np.array([t[i + 1:i + k].mean() for i in range(len(t) - k)]) for t, k in zip(knots, order)]
+        grid = np.meshgrid(*greville, indexing="ij")
+        smooth = np.stack([np.sin((2.0 + d) * sum(grid) + d) for d in range(ndep)])     # the loosest tolerance removes knots of its own
+        coefs = (smooth + 2e-3 * rng.standard_normal((ndep, *ncoef))).astype(dt)
+        new = [list(0.02 + 0.96 * rng.random(c)) for c in count]
+        out.append(CellCase(f"remove_knots {tag} {order} {n}", "remove_knots", order, knots, coefs, kernels, new=new, noise=1e-7, seed=4100))
+    return out
+
+
+def cell_scale_cases():
+    """Everything the cell families' scale tests share: part A's cases per family and type, the exponents and the domains."""
+    A = {family: [] for family in CELL_KERNELS}
+    for dt in (np.float64, np.float32):
+        for c in zeros_scale_cases(dt) + project_scale_cases(dt) + contour_scale_cases(dt) + remove_scale_cases(dt):
+            A[c.family].append(c)
+    return {"A": A, "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "domains": SCALE_DOMAINS, "domains_f32": SCALE_DOMAINS_F32,
+            "tolerances": REMOVE_TOLERANCES}

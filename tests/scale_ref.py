@@ -486,3 +486,55 @@ def multiplied(coefs, index, k):
     c = np.array(coefs)
     c[index] = np.ldexp(c[index], k)
     return c
+
+
+# ------------------------------------------------------------------------------------------------- cell-family specs
+# A cases.CellCase is a public batch call of zeros2, zeros3, project, contours or remove_knots.  With the coefficients
+# x 2^ks (one exponent per leading index: system and component, field, or dependent row; project and a field with levels take
+# one for all, since they subtract points or levels, which go along x 2^ks) and every knot, guess and inserted knot x 2^kp:
+# zeros, vertices, foot parameters and result knots are x 2^kp, distances and result coefficients x 2^ks, and offsets, status
+# bytes, step counts, polyline structure, zero cells and the choice of removed knots are unchanged, bit for bit.  Every
+# threshold of the five families is relative: S_d eps, tau_of(K0, K1, S), 2^-20 h, TRUST of the domain width, a tolerance
+# relative to max |coefficient|; every x = (t - left) / width is a ratio; every rounding commutes with a power of two.
+def cell_scaled(case, ks, kp):
+    ks = np.asarray(ks)
+    coefs = _p2(case.coefs, ks.reshape(ks.shape + (1,) * (case.coefs.ndim - ks.ndim)))
+    args = {}
+    for key, k in (("points", ks), ("levels", ks), ("guess", kp)):
+        if case.args.get(key) is not None:
+            assert np.ndim(k) == 0, f"{key} go along with one exponent"
+            args[key] = _p2(case.args[key], int(k))
+    if "new" in case.args:
+        args["new"] = _scale_arg(case.args["new"], lambda v: float(np.ldexp(np.float64(v), kp)))
+    return case.replaced([_p2(t, kp) for t in case.knots], coefs, **args)
+
+
+def cell_transforms(case, exponents, rows):
+    """[(label, ks, kp)]: the type's (kc, kp) pairs, then the rows pattern cycled over every leading index that takes an
+    exponent of its own: per component and per system (zeros2, zeros3), per field (contours with coefs), per dependent row
+    (remove_knots); one for all (project, contours with levels): the pattern's exponents one after the other."""
+    lead = {"zeros2": 2, "zeros3": 2, "project": 0, "contours": 0 if case.args.get("levels") is not None else 1, "remove_knots": 1}[case.family]
+    shape = case.coefs.shape[:lead]
+    out = [(f"coefficients x 2^{kc}, knots x 2^{kp}", np.full(shape, kc), kp) for kc, kp in exponents[case.kind]]
+    r = rows[case.kind]
+    if lead == 0:
+        return out + [(f"coefficients x 2^{k}", np.array(k), 0) for k in r if k]
+    cyc = np.array(r)[np.arange(shape[-1]) % len(r)]
+    out.append((f"the last leading index x 2^{cyc.tolist()}", np.broadcast_to(cyc, shape).copy(), 0))
+    if lead == 2:
+        per = np.array(r)[(np.arange(shape[0]) + 1) % len(r)]
+        out.append((f"systems x 2^{per.tolist()}", np.broadcast_to(per[:, None], shape).copy(), 0))
+    return out
+
+
+def cell_shifted(case, lo, width):
+    """The case with every variable's domain moved to [lo, lo + width] (map_axis, in the knots' dtype); a guess and knots
+    to insert are mapped along."""
+    knots = [map_axis(t, k, lo, width, t.dtype.type) for t, k in zip(case.knots, case.order)]
+    args = {}
+    if case.args.get("guess") is not None:
+        g = case.args["guess"]
+        args["guess"] = (lo + width * g.astype(np.float64)).astype(g.dtype)
+    if "new" in case.args:
+        args["new"] = [map_axis(t, k, lo, width, np.float64, values=v) for t, k, v in zip(case.knots, case.order, case.args["new"])]
+    return case.replaced(knots, **args)
