@@ -247,7 +247,12 @@ def curvature(self, uv):
             import torch
             dev = next(a for a in uv if _is_torch(a) and a.is_cuda).device
             ts = torch.broadcast_tensors(*[(a if _is_torch(a) else torch.as_tensor(np.asarray(a))).to(dev) for a in uv])
-            return device_tables(self, dev.index).curvature_device(ts).view(tuple(ts[0].shape))
+            try:
+                out = device_tables(self, dev.index).curvature_device(ts)
+            except nv.DomainError as e:
+                cpu = [t.reshape(-1)[e.index].item() for t in ts]
+                raise ValueError(f"Spline evaluation outside domain: {np.atleast_1d(cpu)}") from None
+            return out.view(tuple(ts[0].shape))
         arrays = [np.asarray(a) for a in uv]
         shape = np.broadcast_shapes(*[a.shape for a in arrays])
         flat = [np.ascontiguousarray(np.broadcast_to(a, shape), compute_dtype(self)).reshape(-1) for a in arrays]

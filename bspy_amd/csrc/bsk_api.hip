@@ -265,9 +265,9 @@ extern "C" bsk_status bsk_spline_create(bsk_dtype dtype, int device, int nInd, i
         }
     }
     HIPCHK_C(hipMalloc((void **)&s->lut, std::max<size_t>(16, sizeof(unsigned) * (size_t)(dtype == BSK_F32 ? s->t32.lut_len : s->t64.lut_len))));
-    HIPCHK_C(hipMalloc((void **)&s->bad, sizeof(unsigned long long)));
+    HIPCHK_C(hipMalloc((void **)&s->bad, 2 * sizeof(unsigned long long)));      // [0] the record, [1] fold_bad's minimum
     if (const char *v = getenv("BSK_VARIANT")) s->variant = atoi(v);
-    HIPCHK_C(hipMemset(s->bad, 0xff, sizeof(unsigned long long)));
+    HIPCHK_C(hipMemset(s->bad, 0xff, 2 * sizeof(unsigned long long)));
 #undef HIPCHK_C
     st = dtype == BSK_F32 ? upload_tables<float>(s, knots, coefs) : upload_tables<double>(s, knots, coefs);
     if (st == BSK_OK) st = dtype == BSK_F32 ? upload_uniform<float>(s, knots, coefs) : upload_uniform<double>(s, knots, coefs);
@@ -1097,6 +1097,18 @@ __global__ void publish_bad(unsigned long long *bad, unsigned long long *slot)
     if (v != NO_BAD) *bad = NO_BAD;
 }
 
+// BSK_DEVICE calls in several chunks: the kernels record chunk-local indices.  After each chunk one thread folds
+// start + record into the minimum kept in bad[1] and clears the record; `last` puts the minimum back into the record,
+// where bsk_domain_status finds the call's flat index.  Stream-ordered, no synchronisation.
+__global__ void fold_bad(unsigned long long *bad, unsigned long long start, int last)
+{
+    const unsigned long long v = bad[0];
+    unsigned long long m = start ? bad[1] : NO_BAD;      // the first chunk starts the minimum
+    if (v != NO_BAD && start + v < m) m = start + v;
+    bad[0] = last ? m : NO_BAD;
+    bad[1] = last ? NO_BAD : m;
+}
+
 static bsk_status reserve_pin(bsk_spline s, size_t bytes)
 {
     if (bytes <= s->pin_cap) return BSK_OK;
@@ -1587,8 +1599,12 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
     if (mem == BSK_HOST) return run_staged<T>(s, uvw, n, chunk, 1, out, st, first_bad, curv_chunk);
     for (long long start = 0; start < n; start += chunk) {
         const long long m = std::min(chunk, n - start);
-        const bsk_status r = curv_chunk(device_params<T>(s, uvw, start), m, static_cast<T *>(out) + start, st);
+        bsk_status r = curv_chunk(device_params<T>(s, uvw, start), m, static_cast<T *>(out) + start, st);
         if (r != BSK_OK) return r;
+        if (n > chunk) {                 // several chunks: the record is chunk-local, the caller reads the call's index
+            r = launch(s, nullptr, fold_bad, dim3(1), dim3(1), 0, st, s->bad, (unsigned long long)start, start + m >= n ? 1 : 0);
+            if (r != BSK_OK) return r;
+        }
     }
     return BSK_OK;
 }

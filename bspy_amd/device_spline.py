@@ -205,6 +205,8 @@ class DeviceSpline:
         torch, tdt, ps, n = self._torch_params(points)
         if out is None:
             out = torch.empty((n,), dtype=tdt, device=ps[0].device)
+        elif out.dtype != tdt or out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (N,) tensor of the spline's dtype")
         st = nv.lib().bsk_curvature(self._handle, nv.ptr_array([p.data_ptr() for p in ps]), n, nv.BSK_DEVICE,
                                     out.data_ptr(), self._stream_ptr(torch, self.device), None)
         nv.check(st)

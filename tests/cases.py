@@ -7,6 +7,7 @@ definitions and parameter points) from fixed seeds, following the generator
 spec of SURVEY.md section 8(c)-2, so the GPU box can regenerate exactly the
 inputs whose reference outputs are stored in ``tests/golden/*.npz``.
 """
+import functools
 import itertools
 import numpy as np
 
@@ -712,3 +713,163 @@ def cell_scale_cases():
             A[c.family].append(c)
     return {"A": A, "exponents": SCALE_EXPONENTS, "rows": SCALE_ROWS, "domains": SCALE_DOMAINS, "domains_f32": SCALE_DOMAINS_F32,
             "tolerances": REMOVE_TOLERANCES}
+
+
+# ---------------------------------------------------------------------------------------------
+# Normal and curvature on every kernel family, batch path and chunk (tests/test_shape_host.py, tests/test_gpu_shape.py;
+# yardstick and bars: tests/shape_ref.py).
+# ---------------------------------------------------------------------------------------------
+class ShapeCase:
+    """One spline, one batch size and the quantity to pin (kind: normal / curvature).  ``kernel``: what last_kernel() must
+    name after the call (a trailing * matches a part of it); ``variant``: the BSK_VARIANT that forces the family;
+    ``uniform``: a table-free uniform-knot family (its bar takes the form of test_gpu_scale.py part B); ``zero``: the result
+    is exactly 0.0 wherever it is finite (a polyline's curvature)."""
+
+    def __init__(self, name, kind, order, ncoef, knots, coefs, dt, n, kernel, variant=None, uniform=False, zero=False, seed=1):
+        self.name, self.kind, self.order, self.nCoef, self.knots, self.coefs, self.dt = name, kind, tuple(order), tuple(ncoef), knots, coefs, dt
+        self.n, self.kernel, self.variant, self.uniform, self.zero, self.seed = n, kernel, variant, uniform, zero, seed
+        self.nInd, self.nDep = len(self.order), coefs.shape[0]
+
+    @property
+    def type(self):
+        return "fp32" if self.dt == np.float32 else "fp64"
+
+    def points(self):
+        return shape_points(self.order, self.nCoef, self.knots, self.n, self.dt, self.seed)
+
+    def sized(self, n, kernel=None):
+        """The same spline and quantity on a batch of n points."""
+        return ShapeCase(f"{self.name}, n {n}", self.kind, self.order, self.nCoef, self.knots, self.coefs, self.dt, n,
+                         kernel or self.kernel, self.variant, self.uniform, self.zero, self.seed)
+
+
+def shape_points(order, ncoef, knots, n, dt, seed):
+    """n random points of the domain; point 0 lies on the low end of every variable, point 1 on the high end, point 2 on an
+    interior knot of every variable that has one, point 3 has a NaN first parameter and point 4 a NaN last one."""
+    rng = np.random.default_rng(seed)
+    pts = []
+    for iv, (k, o, c) in enumerate(zip(knots, order, ncoef)):
+        k = np.asarray(k, dt)
+        lo, hi = k[o - 1], k[c]
+        p = np.clip((lo + (hi - lo) * rng.random(n)).astype(dt), lo, hi)
+        if n > 4:
+            p[0], p[1] = lo, hi
+            inner = np.unique(k[o:c])
+            inner = inner[(inner > lo) & (inner < hi)]
+            if len(inner):
+                p[2] = inner[len(inner) // 2]
+            if iv == 0:
+                p[3] = np.nan
+            if iv == len(order) - 1:
+                p[4] = np.nan
+        pts.append(p)
+    return pts
+
+
+def graph_spec(order, ncoef, ndep, dt, seed, uniform=False, lo=0.0, hi=1.0):
+    """A well-conditioned "graph plus noise" spline (as project_scale_cases): coefficient row a runs from 0 to 2 along
+    variable a, plus 0.3 x standard normal noise; clamped uniform knots or the non-uniform ones of nonuniform_knots."""
+    rng = np.random.default_rng(seed)
+    if uniform:
+        knots = [clamped_uniform_knots(o, c, dt, lo, hi) for o, c in zip(order, ncoef)]
+    else:
+        knots = [nonuniform_knots(rng, o, c, dt, lo, hi) for o, c in zip(order, ncoef)]
+    coefs = 0.3 * rng.standard_normal((ndep, *ncoef))
+    for a, m in enumerate(ncoef[:ndep]):
+        coefs[a] += np.linspace(0.0, 2.0, m).reshape([-1 if b == a else 1 for b in range(len(ncoef))])
+    return tuple(order), tuple(ncoef), knots, coefs.astype(dt)
+
+
+SHAPE_N = 20_011
+# above the cell-order cut of dispatch_jac (2^18 points): derivative passes through the cell-order pipeline, and from 2^19 on eval_slab2
+SHAPE_CELL_ORDER = {270_001: "cell-order pipeline*", 530_003: "eval_slab2"}
+SHAPE_PIPED = (1 << 21) + 5                     # three chunks of 2^20 through the pipelined host path
+SHAPE_STAGED = 70_001                           # one chunk of the staged host path
+SHAPE_DEVICE_CHUNKS = (1 << 22) + 4_099         # two chunks of the curvature device loop
+
+
+@functools.lru_cache(maxsize=None)
+def shape_cases():
+    """{name: ShapeCase}: the normal and curvature cases per kernel family, and the batch-path cases built on three of them."""
+    f32, f64 = np.float32, np.float64
+    P = {c.name: c for c in parity_cases()}
+    out = {}
+
+    def add(kind, label, spec, dt, kernel, n=SHAPE_N, **kw):
+        c = ShapeCase(f"{kind}: {label}", kind, *spec, dt, n, kernel, **kw)
+        assert c.name not in out
+        out[c.name] = c
+        return c
+
+    def parity(name):
+        c = P[name]
+        return c.order, c.nCoef, c.knots, c.coefs
+
+    _, _, o2, nc2, k2, cf2, _ = bench_spline(2)
+    _, _, o5, nc5, k5, cf5, _ = bench_spline(5)
+    cfg2n = parity("cfg2_bicubic_nonuniform")
+    o33 = graph_spec((3, 3), (9, 10), 3, f64, 801)
+    o33_32 = graph_spec((3, 3), (9, 10), 3, f32, 801)
+    o33u = graph_spec((3, 3), (9, 10), 3, f64, 802, uniform=True)
+    l2 = graph_spec((4, 4), (200, 150), 3, f64, 803)
+
+    # ---- normal
+    N = "normal"
+    add(N, "fused, table-free, cfg2", (o2, nc2, k2, cf2), f64, "jac_uni", uniform=True)
+    add(N, "fused, cfg2 non-uniform", cfg2n, f64, "jac_rowrot")
+    add(N, "fused, order (2, 2) fp32", graph_spec((2, 2), (40, 33), 3, f32, 804), f32, "jac_rowrot")
+    add(N, "general LDS, order (3, 3)", o33, f64, "jac_stream")
+    add(N, "general LDS, order (3, 3) fp32", o33_32, f32, "jac_stream")
+    add(N, "general LDS, order (3, 3, 3) nDep 2", graph_spec((3, 3, 3), (6, 7, 5), 2, f64, 805), f64, "jac_stream")
+    add(N, "general LDS, order (3, 3, 3) nDep 4", graph_spec((3, 3, 3), (6, 7, 5), 4, f64, 806), f64, "jac_stream")
+    add(N, "table-free, order (3, 3) uniform", o33u, f64, "jac_stream_uni", uniform=True)
+    add(N, "table-free, cubic curve uniform", graph_spec((4,), (40,), 2, f64, 807, uniform=True), f64, "jac_stream_uni", uniform=True)
+    add(N, "fixed, cfg2 non-uniform under BSK_VARIANT=1", cfg2n, f64, "jac_fixed", variant="1")
+    add(N, "fixed, order (6, 6)", graph_spec((6, 6), (10, 9), 3, f64, 808), f64, "jac_fixed")
+    add(N, "fixed, order (5, 5, 5) nDep 4", graph_spec((5, 5, 5), (7, 6, 7), 4, f64, 809), f64, "jac_fixed")
+    add(N, "mixed, surface_o3x4", parity("surface_o3x4"), f64, "jac_mixed")
+    add(N, "mixed, order (3, 4, 2) nDep 2", graph_spec((3, 4, 2), (6, 7, 5), 2, f64, 810), f64, "jac_mixed")
+    add(N, "derivative passes, four variables", graph_spec((3, 2, 4, 3), (4, 5, 6, 4), 3, f64, 811), f64, "eval_mixed")
+    add(N, "derivative passes, curve order 12", parity("curve_order12"), f64, "eval_mixed")
+    add(N, "derivative passes, curve order 14", graph_spec((14,), (24,), 2, f64, 812), f64, "eval_generic")
+    nl2 = add(N, "L2-resident surface", l2, f64, "jac_fixed")
+    for n, kernel in SHAPE_CELL_ORDER.items():
+        out[nl2.sized(n).name] = nl2.sized(n, kernel)
+    add(N, "fused cell-order jacobian, cfg5 fp32", (o5, nc5, k5, cf5), f32, "fused jacobian*", n=280_003)
+
+    # ---- curvature
+    C = "curvature"
+    rng = np.random.default_rng(31)
+    for order, ncoef in (((2, 2), (9, 7)), ((4, 4), (12, 10))):         # the splines of test_fused_curvature_orders_and_sizes
+        knots = [nonuniform_knots(rng, o, c, f64, 0.0, 1.0) for o, c in zip(order, ncoef)]
+        add(C, f"fused, order {order}", (order, ncoef, knots, rng.standard_normal((3, *ncoef))), f64, "curv_rowrot")
+    add(C, "fused, bicubic fp32", graph_spec((4, 4), (12, 10), 3, f32, 813), f32, "curv_rowrot")
+    cfused = add(C, "fused, cfg2 non-uniform", cfg2n, f64, "curv_rowrot")
+    c33 = add(C, "non-fused surface, order (3, 3)", o33, f64, "jac_stream")
+    add(C, "non-fused surface, order (3, 3) fp32", o33_32, f32, "jac_stream")
+    add(C, "non-fused surface, order (3, 3) uniform", o33u, f64, "jac_stream_uni", uniform=True)
+    add(C, "non-fused surface, surface_o3x4", parity("surface_o3x4"), f64, "jac_mixed")
+    add(C, "non-fused surface, cfg2 non-uniform under BSK_VARIANT=1", cfg2n, f64, "jac_fixed", variant="1")
+    cl2 = add(C, "non-fused surface, L2-resident", l2, f64, "jac_fixed")
+    for n, kernel in SHAPE_CELL_ORDER.items():
+        out[cl2.sized(n).name] = cl2.sized(n, kernel)
+    cubic = graph_spec((4,), (40,), 2, f64, 814, uniform=True)
+    add(C, "curve, cubic uniform nDep 2", cubic, f64, "eval_stream_uni", uniform=True)
+    add(C, "curve, cubic uniform nDep 2, reversed", (*cubic[:3], cubic[3][:, ::-1].copy()), f64, "eval_stream_uni", uniform=True)
+    add(C, "curve, order 6 nDep 3", graph_spec((6,), (20,), 3, f64, 815), f64, "eval_stream")
+    add(C, "curve, order 12 nDep 2", parity("curve_order12"), f64, "eval_mixed")
+    add(C, "curve, order 14 nDep 2", graph_spec((14,), (24,), 2, f64, 812), f64, "eval_generic")
+    # L2-resident gather: the coefficients exceed LDS, the axis table still fits half of it (50 000 coefficients land on eval_generic)
+    add(C, "curve, order 4, 2 500 coefficients nDep 4", graph_spec((4,), (2_500,), 4, f64, 816), f64, "eval_gather*")
+    for ndep in (2, 3):
+        add(C, f"curve, order 2 polyline nDep {ndep}", graph_spec((2,), (30,), ndep, f64, 817 + ndep), f64, "eval_stream", zero=True)
+
+    # ---- batch paths (section 3 of the tests): the jac_stream surface, the fused cfg2 surface, the L2-resident surface
+    n33 = out["normal: general LDS, order (3, 3)"]
+    nfused = out["normal: fused, cfg2 non-uniform"]
+    for base in (n33, nfused, nl2, c33, cfused, cl2):
+        for n in (SHAPE_STAGED, SHAPE_PIPED):
+            out[base.sized(n).name] = base.sized(n)
+    for base in (c33, cfused):
+        out[base.sized(SHAPE_DEVICE_CHUNKS).name] = base.sized(SHAPE_DEVICE_CHUNKS)
+    return out
