@@ -11,6 +11,7 @@
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "bsk_common.hpp"
@@ -187,8 +188,23 @@ inline bsk_status launch(bsk_spline s, const char *name, K kernel, dim3 grid, di
     return BSK_OK;
 }
 
+// The launches of the handle-free families: `lanes` lanes in blocks of BLOCK on stream st (`layers`: gridDim.y).
+template <int BLOCK, typename K, typename... Args>
+inline bsk_status launch_lanes(K kernel, long long lanes, long long layers, hipStream_t st, const Args &...args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + BLOCK - 1) / BLOCK), (unsigned)layers), dim3(BLOCK), 0, st, args...);
+    HIPCHK(hipGetLastError());
+    return BSK_OK;
+}
+template <int BLOCK, typename K, typename... Args>
+inline bsk_status launch_lanes(K kernel, long long lanes, hipStream_t st, const Args &...args)
+{
+    return launch_lanes<BLOCK>(kernel, lanes, 1, st, args...);
+}
+
 // Run-time value -> template constant: f receives a std::integral_constant.  with_int<A, B, ..., Z>(v, f) hands over
-// v's own class, and Z for every value that is not listed (callers check the range, or Z is the "any" class).
+// v's own class, and Z for every value that is not listed (callers check the range, or Z is the "any" class);
+// with_range<LO, HI> is with_int<LO, LO + 1, ..., HI>.  with_dtype hands over a zero of the element type.
 template <typename F>
 inline bsk_status with_bool(bool b, F &&f)
 {
@@ -199,6 +215,21 @@ inline bsk_status with_int(int v, F &&f)
 {
     if constexpr (sizeof...(Ns) == 0) return f(std::integral_constant<int, N0>{});
     else return v == N0 ? f(std::integral_constant<int, N0>{}) : with_int<Ns...>(v, f);
+}
+template <int LO, int... Is, typename F>
+inline bsk_status with_offsets(int v, std::integer_sequence<int, Is...>, F &&f)
+{
+    return with_int<LO + Is...>(v, f);
+}
+template <int LO, int HI, typename F>
+inline bsk_status with_range(int v, F &&f)
+{
+    return with_offsets<LO>(v, std::make_integer_sequence<int, HI - LO + 1>{}, f);
+}
+template <typename F>
+inline bsk_status with_dtype(bsk_dtype dtype, F &&f)
+{
+    return dtype == BSK_F32 ? f(0.0f) : f(0.0);
 }
 
 

@@ -379,6 +379,26 @@ BSK_HD void newton_lane(const Tables &T, const double *points, long long npts, c
     steps[lane] = n;
 }
 
+// The host drivers' loops over seed_lane and newton_lane (bsk_project_tu.hip): out of line and on a 64-byte boundary, so
+// that where their instructions lie does not depend on the dispatcher that calls them.  Host functions: the device pass
+// emits nothing for them.
+template <int NDEP>
+__attribute__((noinline, aligned(64))) void seed_host(const double *samples, long long M, const double *points, long long npts,
+                                                      long long chunk, long long nchunks, double *part_d2, int32_t *part_idx)
+{
+    for (long long c = 0; c < nchunks; ++c)
+        for (long long lane = 0; lane < npts; ++lane) seed_lane<NDEP>(samples, M, points, npts, chunk, c, lane, part_d2, part_idx);
+}
+
+template <int NIND, int K0, int K1, int NDEP>
+__attribute__((noinline, aligned(64))) void newton_host(const Tables &T, const double *points, long long npts, const double *part_d2,
+                                                        const int32_t *part_idx, long long nchunks, const double *guess, double *uvw,
+                                                        double *distance, uint8_t *status, int32_t *steps)
+{
+    for (long long lane = 0; lane < npts; ++lane)
+        newton_lane<NIND, K0, K1, NDEP>(T, points, npts, part_d2, part_idx, nchunks, guess, lane, uvw, distance, status, steps);
+}
+
 #ifdef __HIPCC__
 template <int NDEP>
 __global__ __launch_bounds__(PROJECT_BLOCK) void project_seed(const double *__restrict__ samples, long long M,

@@ -1,5 +1,6 @@
 // Closest points on curves and surfaces (bsk_project.hpp): the bsk_project_* entry points.  Like bsk_roots2_tu.hip the
-// family keeps no handle: a call takes the extracted rows, the sample grid and the query points and enqueues one launch.
+// family keeps no handle, and each x_host / x pair is one function of DEVICE: the checks, the dispatch, then the host
+// loop over the lanes (seed_host and newton_host of bsk_project.hpp) or the launch.
 // Instantiations: project_seed for ndep = 2, 3; project_newton for curves of order 2 .. 6 and surfaces of orders 2 .. 4,
 // ndep = 2, 3, on the device and on the host alike.
 #include <cstdint>
@@ -17,11 +18,25 @@ constexpr long long PROJECT_MAX_CHUNKS = 65535;     // gridDim.y
 struct SeedCall {
     int ndep;
     const double *samples;
-    int64_t nsamples;
+    long long nsamples;
     const double *points;
-    int64_t npts, chunk;
+    long long npts, chunk;
     double *part_d2;
     int32_t *part_idx;
+};
+
+struct NewtonCall {
+    int nind, K0, K1, ndep;
+    Tables T;
+    const double *points;
+    long long npts;
+    const double *part_d2;
+    const int32_t *part_idx;
+    long long nchunks;
+    const double *guess;
+    double *uvw, *distance;
+    uint8_t *status;
+    int32_t *steps;
 };
 
 static bsk_status check_seed(const SeedCall &c, const char *who)
@@ -35,60 +50,6 @@ static bsk_status check_seed(const SeedCall &c, const char *who)
     if ((double)c.npts * (double)((c.nsamples + c.chunk - 1) / c.chunk) > 5.0e11) return fail(BSK_ERR_INVALID, w + ": array too large");
     return BSK_OK;
 }
-
-extern "C" const char *bsk_project_last_kernel(void) { return g_project_kernel; }
-
-extern "C" bsk_status bsk_project_seed_host(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts,
-                                            int64_t chunk, double *part_d2, int32_t *part_idx)
-{
-    const SeedCall c{ndep, samples, nsamples, points, npts, chunk, part_d2, part_idx};
-    const bsk_status s = check_seed(c, "bsk_project_seed_host");
-    if (s != BSK_OK) return s;
-    const long long nchunks = (nsamples + chunk - 1) / chunk;
-    for (long long k = 0; k < nchunks; ++k)
-        for (long long lane = 0; lane < npts; ++lane) {
-            if (ndep == 2) seed_lane<2>(samples, nsamples, points, npts, chunk, k, lane, part_d2, part_idx);
-            else seed_lane<3>(samples, nsamples, points, npts, chunk, k, lane, part_d2, part_idx);
-        }
-    g_project_kernel = "host project_seed";
-    return BSK_OK;
-}
-
-extern "C" bsk_status bsk_project_seed(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts,
-                                       int64_t chunk, double *part_d2, int32_t *part_idx, void *stream)
-{
-    const SeedCall c{ndep, samples, nsamples, points, npts, chunk, part_d2, part_idx};
-    const bsk_status s = check_seed(c, "bsk_project_seed");
-    if (s != BSK_OK) return s;
-    const long long nchunks = (nsamples + chunk - 1) / chunk;
-    const long long blocks = (npts + PROJECT_BLOCK - 1) / PROJECT_BLOCK;
-    if (blocks > 0x7fffffffLL) return fail(BSK_ERR_INVALID, "bsk_project_seed: too many points for one launch");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks, (unsigned)nchunks);
-    if (ndep == 2)
-        hipLaunchKernelGGL((project_seed<2>), grid, dim3(PROJECT_BLOCK), 0, st, samples, (long long)nsamples, points, (long long)npts,
-                           (long long)chunk, part_d2, part_idx);
-    else
-        hipLaunchKernelGGL((project_seed<3>), grid, dim3(PROJECT_BLOCK), 0, st, samples, (long long)nsamples, points, (long long)npts,
-                           (long long)chunk, part_d2, part_idx);
-    HIPCHK(hipGetLastError());
-    g_project_kernel = "project_seed";
-    return BSK_OK;
-}
-
-struct NewtonCall {
-    int nind, K0, K1, ndep;
-    Tables T;
-    const double *points;
-    int64_t npts;
-    const double *part_d2;
-    const int32_t *part_idx;
-    int64_t nchunks;
-    const double *guess;
-    double *uvw, *distance;
-    uint8_t *status;
-    int32_t *steps;
-};
 
 static bsk_status check_newton(const NewtonCall &c, const char *who)
 {
@@ -116,36 +77,72 @@ static bsk_status check_newton(const NewtonCall &c, const char *who)
     return BSK_OK;
 }
 
-// f(<NIND>, <K0>, <K1>, <NDEP>) for the covered combinations
+// f(<NIND>, <K0>, <K1>, <NDEP>) behind check_newton: curves of order 2 .. 6 (K1 = 1), surfaces of orders 2 .. 4
 template <typename F>
-static bsk_status by_shape(int nind, int K0, int K1, int ndep, F &&f)
+static bsk_status by_shape(const NewtonCall &c, F &&f)
 {
     auto dep = [&](auto ni, auto k0, auto k1) {
-        return ndep == 2 ? f(ni, k0, k1, std::integral_constant<int, 2>()) : f(ni, k0, k1, std::integral_constant<int, 3>());
+        return with_int<2, 3>(c.ndep, [&](auto nd) { return f(ni, k0, k1, nd); });
     };
-    auto second = [&](auto k0) {
-        switch (K1) {
-        case 2: return dep(std::integral_constant<int, 2>(), k0, std::integral_constant<int, 2>());
-        case 3: return dep(std::integral_constant<int, 2>(), k0, std::integral_constant<int, 3>());
-        case 4: return dep(std::integral_constant<int, 2>(), k0, std::integral_constant<int, 4>());
-        default: return fail(BSK_ERR_UNSUPPORTED, "bsk_project: order not covered");
+    return with_int<1, 2>(c.nind, [&](auto ni) {
+        if constexpr (decltype(ni)::value == 1)          // a curve has K1 = 1
+            return with_range<2, PROJECT_CURVE_MAX_K>(c.K0, [&](auto k0) {
+                return with_int<1>(c.K1, [&](auto k1) { return dep(ni, k0, k1); });
+            });
+        else
+            return with_range<2, PROJECT_SURFACE_MAX_K>(c.K0, [&](auto k0) {
+                return with_range<2, PROJECT_SURFACE_MAX_K>(c.K1, [&](auto k1) { return dep(ni, k0, k1); });
+            });
+    });
+}
+
+template <bool DEVICE>
+static bsk_status seed(const SeedCall &c, hipStream_t st)
+{
+    const char *who = DEVICE ? "bsk_project_seed" : "bsk_project_seed_host";
+    bsk_status s = check_seed(c, who);
+    if (s != BSK_OK) return s;
+    const long long nchunks = (c.nsamples + c.chunk - 1) / c.chunk;
+    // the bound of the launch's gridDim.x, on the device twin alone
+    if constexpr (DEVICE)
+        if ((c.npts + PROJECT_BLOCK - 1) / PROJECT_BLOCK > 0x7fffffffLL) return fail(BSK_ERR_INVALID, std::string(who) + ": too many points for one launch");
+    s = with_int<2, 3>(c.ndep, [&](auto nd) {
+        constexpr int NDEP = decltype(nd)::value;
+        if constexpr (DEVICE)
+            return launch_lanes<PROJECT_BLOCK>(project_seed<NDEP>, c.npts, nchunks, st, c.samples, c.nsamples, c.points, c.npts, c.chunk,
+                                               c.part_d2, c.part_idx);
+        else {
+            seed_host<NDEP>(c.samples, c.nsamples, c.points, c.npts, c.chunk, nchunks, c.part_d2, c.part_idx);
+            return BSK_OK;
         }
-    };
-    if (nind == 1) switch (K0) {
-        case 2: return dep(std::integral_constant<int, 1>(), std::integral_constant<int, 2>(), std::integral_constant<int, 1>());
-        case 3: return dep(std::integral_constant<int, 1>(), std::integral_constant<int, 3>(), std::integral_constant<int, 1>());
-        case 4: return dep(std::integral_constant<int, 1>(), std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
-        case 5: return dep(std::integral_constant<int, 1>(), std::integral_constant<int, 5>(), std::integral_constant<int, 1>());
-        case 6: return dep(std::integral_constant<int, 1>(), std::integral_constant<int, 6>(), std::integral_constant<int, 1>());
-        default: break;
+    });
+    if (s == BSK_OK) g_project_kernel = DEVICE ? "project_seed" : "host project_seed";
+    return s;
+}
+
+template <bool DEVICE>
+static bsk_status newton(const NewtonCall &c, hipStream_t st)
+{
+    const char *who = DEVICE ? "bsk_project_newton" : "bsk_project_newton_host";
+    bsk_status s = check_newton(c, who);
+    if (s != BSK_OK) return s;
+    // the bound of the launch's gridDim.x, on the device twin alone
+    if constexpr (DEVICE)
+        if ((c.npts + PROJECT_NEWTON_BLOCK - 1) / PROJECT_NEWTON_BLOCK > 0x7fffffffLL)
+            return fail(BSK_ERR_INVALID, std::string(who) + ": too many points for one launch");
+    s = by_shape(c, [&](auto ni, auto k0, auto k1, auto nd) {
+        constexpr int NIND = decltype(ni)::value, K0 = decltype(k0)::value, K1 = decltype(k1)::value, NDEP = decltype(nd)::value;
+        if constexpr (DEVICE)
+            return launch_lanes<PROJECT_NEWTON_BLOCK>(project_newton<NIND, K0, K1, NDEP>, c.npts, st, c.T, c.points, c.npts, c.part_d2,
+                                                      c.part_idx, c.nchunks, c.guess, c.uvw, c.distance, c.status, c.steps);
+        else {
+            newton_host<NIND, K0, K1, NDEP>(c.T, c.points, c.npts, c.part_d2, c.part_idx, c.nchunks, c.guess, c.uvw, c.distance, c.status,
+                                            c.steps);
+            return BSK_OK;
         }
-    else switch (K0) {
-        case 2: return second(std::integral_constant<int, 2>());
-        case 3: return second(std::integral_constant<int, 3>());
-        case 4: return second(std::integral_constant<int, 4>());
-        default: break;
-        }
-    return fail(BSK_ERR_UNSUPPORTED, "bsk_project: order not covered");
+    });
+    if (s == BSK_OK) g_project_kernel = DEVICE ? "project_newton" : "host project_newton";
+    return s;
 }
 
 static NewtonCall newton_call(int nind, int K0, int K1, int ndep, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
@@ -158,24 +155,29 @@ static NewtonCall newton_call(int nind, int K0, int K1, int ndep, const double *
     return NewtonCall{nind, K0, K1, ndep, T, points, npts, part_d2, part_idx, nchunks, guess, uvw, distance, status, steps};
 }
 
+extern "C" const char *bsk_project_last_kernel(void) { return g_project_kernel; }
+
+extern "C" bsk_status bsk_project_seed_host(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts,
+                                            int64_t chunk, double *part_d2, int32_t *part_idx)
+{
+    return seed<false>(SeedCall{ndep, samples, nsamples, points, npts, chunk, part_d2, part_idx}, nullptr);
+}
+
+extern "C" bsk_status bsk_project_seed(int ndep, const double *samples, int64_t nsamples, const double *points, int64_t npts,
+                                       int64_t chunk, double *part_d2, int32_t *part_idx, void *stream)
+{
+    return seed<true>(SeedCall{ndep, samples, nsamples, points, npts, chunk, part_d2, part_idx}, static_cast<hipStream_t>(stream));
+}
+
 extern "C" bsk_status bsk_project_newton_host(int nind, int K0, int K1, int ndep, const double *rows, int64_t R0, int64_t R1,
                                               int64_t nc0, int64_t nc1, const int32_t *first0, const int32_t *first1,
                                               const double *breaks0, const double *breaks1, int g0, int g1, const double *points,
                                               int64_t npts, const double *part_d2, const int32_t *part_idx, int64_t nchunks,
                                               const double *guess, double *uvw, double *distance, uint8_t *status, int32_t *steps)
 {
-    const NewtonCall c = newton_call(nind, K0, K1, ndep, rows, R0, R1, nc0, nc1, first0, first1, breaks0, breaks1, g0, g1, points, npts,
-                                     part_d2, part_idx, nchunks, guess, uvw, distance, status, steps);
-    bsk_status s = check_newton(c, "bsk_project_newton_host");
-    if (s != BSK_OK) return s;
-    s = by_shape(nind, K0, K1, ndep, [&](auto ni, auto k0, auto k1, auto nd) {
-        for (long long lane = 0; lane < npts; ++lane)
-            newton_lane<decltype(ni)::value, decltype(k0)::value, decltype(k1)::value, decltype(nd)::value>(
-                c.T, points, npts, part_d2, part_idx, nchunks, guess, lane, uvw, distance, status, steps);
-        return BSK_OK;
-    });
-    if (s == BSK_OK) g_project_kernel = "host project_newton";
-    return s;
+    return newton<false>(newton_call(nind, K0, K1, ndep, rows, R0, R1, nc0, nc1, first0, first1, breaks0, breaks1, g0, g1, points, npts,
+                                     part_d2, part_idx, nchunks, guess, uvw, distance, status, steps),
+                         nullptr);
 }
 
 extern "C" bsk_status bsk_project_newton(int nind, int K0, int K1, int ndep, const double *rows, int64_t R0, int64_t R1, int64_t nc0,
@@ -184,20 +186,7 @@ extern "C" bsk_status bsk_project_newton(int nind, int K0, int K1, int ndep, con
                                          const double *part_d2, const int32_t *part_idx, int64_t nchunks, const double *guess,
                                          double *uvw, double *distance, uint8_t *status, int32_t *steps, void *stream)
 {
-    const NewtonCall c = newton_call(nind, K0, K1, ndep, rows, R0, R1, nc0, nc1, first0, first1, breaks0, breaks1, g0, g1, points, npts,
-                                     part_d2, part_idx, nchunks, guess, uvw, distance, status, steps);
-    bsk_status s = check_newton(c, "bsk_project_newton");
-    if (s != BSK_OK) return s;
-    const long long blocks = (npts + PROJECT_NEWTON_BLOCK - 1) / PROJECT_NEWTON_BLOCK;
-    if (blocks > 0x7fffffffLL) return fail(BSK_ERR_INVALID, "bsk_project_newton: too many points for one launch");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    s = by_shape(nind, K0, K1, ndep, [&](auto ni, auto k0, auto k1, auto nd) {
-        hipLaunchKernelGGL((project_newton<decltype(ni)::value, decltype(k0)::value, decltype(k1)::value, decltype(nd)::value>),
-                           dim3((unsigned)blocks), dim3(PROJECT_NEWTON_BLOCK), 0, st, c.T, points, (long long)npts, part_d2, part_idx,
-                           (long long)nchunks, guess, uvw, distance, status, steps);
-        HIPCHK(hipGetLastError());
-        return BSK_OK;
-    });
-    if (s == BSK_OK) g_project_kernel = "project_newton";
-    return s;
+    return newton<true>(newton_call(nind, K0, K1, ndep, rows, R0, R1, nc0, nc1, first0, first1, breaks0, breaks1, g0, g1, points, npts,
+                                    part_d2, part_idx, nchunks, guess, uvw, distance, status, steps),
+                        static_cast<hipStream_t>(stream));
 }

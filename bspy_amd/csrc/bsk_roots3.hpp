@@ -603,6 +603,26 @@ BSK_HD void merge_lane(long long lane, int R, const double *roots, long long nsy
     keep[at] = kept;
 }
 
+// The host drivers' loops over flag_lane and isolate_wave (bsk_roots3_tu.hip): out of line and on a 64-byte boundary, so
+// that where their instructions lie does not depend on the dispatcher that calls them.  Host functions: the device pass
+// emits nothing for them.
+template <int K0, int K1, int K2>
+__attribute__((noinline, aligned(64))) void flag_host(const Grid &g, const uint8_t *mask, uint8_t *flags)
+{
+    const long long lanes = g.nsys * g.nc0 * g.nc1 * g.nc2;
+    for (long long at = 0; at < lanes; ++at) flag_lane<K0, K1, K2>(g, at, mask, flags);
+}
+
+template <int K0, int K1, int K2>
+__attribute__((noinline, aligned(64))) void isolate_host(const Grid &g, const Breaks &br, const double *scale, const int64_t *cand,
+                                                         long long ncand, double *roots, uint8_t *near, int32_t *count, uint8_t *status,
+                                                         int32_t *nodes)
+{
+    const HostWave wave;
+    for (long long slot = 0; slot < ncand; ++slot)
+        isolate_wave<HostWave, K0, K1, K2>(wave, g, slot, br, scale, cand, roots, near, count, status, nodes);
+}
+
 #ifdef __HIPCC__
 template <int K0, int K1, int K2>
 __global__ __launch_bounds__(ROOTS3_BLOCK) void roots3_flag(Grid g, const uint8_t *__restrict__ mask, uint8_t *__restrict__ flags)
