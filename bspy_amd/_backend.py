@@ -133,6 +133,12 @@ class Host:
     def searchsorted(self, a, n):
         return np.searchsorted(a, np.arange(n)).astype(np.int64)
 
+    def arange(self, n):
+        return np.arange(n, dtype=np.int64)
+
+    def cat(self, arrays):
+        return np.concatenate(arrays)
+
     def call(self, name, *args):
         nv.check(getattr(nv.lib(), name + "_host")(*args))
 
@@ -209,6 +215,12 @@ class Device:
 
     def searchsorted(self, a, n):
         return self.torch.searchsorted(a.contiguous(), self.torch.arange(n, device=self.dev))
+
+    def arange(self, n):
+        return self.torch.arange(n, dtype=self.torch.int64, device=self.dev)
+
+    def cat(self, arrays):
+        return self.torch.cat(list(arrays))
 
     def call(self, name, *args):
         nv.check(getattr(nv.lib(), name)(*args, self.stream))

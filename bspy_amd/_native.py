@@ -38,6 +38,8 @@ PRODUCT_SYMBOLS = (
     "bsk_roots_extract_host", "bsk_roots_flag_host", "bsk_roots_flag", "bsk_roots_isolate_host", "bsk_roots_isolate", "bsk_roots_last_kernel",
     "bsk_project_seed_host", "bsk_project_seed", "bsk_project_newton_host", "bsk_project_newton", "bsk_project_last_kernel",
     "bsk_contour_flag_host", "bsk_contour_flag", "bsk_contour_march_host", "bsk_contour_march", "bsk_contour_last_kernel",
+    "bsk_rays_boxes_host", "bsk_rays_boxes", "bsk_rays_count_host", "bsk_rays_count", "bsk_rays_emit_host", "bsk_rays_emit",
+    "bsk_rays_isolate_host", "bsk_rays_isolate", "bsk_rays_reduce_host", "bsk_rays_reduce", "bsk_rays_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -207,6 +209,24 @@ def lib():
     L.bsk_contour_march.argtypes = march_c + [_vp]
     L.bsk_contour_last_kernel.argtypes = []
     L.bsk_contour_last_kernel.restype = ctypes.c_char_p
+    surface = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]
+    rays = [_vp, _vp, _vp, _i64]
+    search = surface + rays + [ctypes.c_double, ctypes.c_double, _i64, ctypes.c_int, _vp]
+    isolate_r = surface + [_vp, _vp] + rays + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    reduce_r = surface + [_vp, _vp] + rays + [ctypes.c_double, ctypes.c_double, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                              _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.bsk_rays_boxes_host.argtypes = surface + [_vp]
+    L.bsk_rays_boxes.argtypes = surface + [_vp, _vp]
+    L.bsk_rays_count_host.argtypes = search + [_vp, _vp]
+    L.bsk_rays_count.argtypes = search + [_vp, _vp, _vp]
+    L.bsk_rays_emit_host.argtypes = search + [_vp, _vp, _vp, _i64]
+    L.bsk_rays_emit.argtypes = search + [_vp, _vp, _vp, _i64, _vp]
+    L.bsk_rays_isolate_host.argtypes = isolate_r
+    L.bsk_rays_isolate.argtypes = isolate_r + [_vp]
+    L.bsk_rays_reduce_host.argtypes = reduce_r
+    L.bsk_rays_reduce.argtypes = reduce_r + [_vp]
+    L.bsk_rays_last_kernel.argtypes = []
+    L.bsk_rays_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -216,7 +236,7 @@ def lib():
     for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel"):
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_rays_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

@@ -231,9 +231,10 @@ BSK_HD double outside(double x, double lo, double w)
     return d;
 }
 
-// The leaf box with corner (lo0, lo1): at most one root into out, see the head of this file.
-template <int K0, int K1>
-BSK_HD void leaf(const CellRef &ref, double lo0, double lo1, double t0u, double hu, double t0v, double hv, double S0, double S1,
+// The leaf box with corner (lo0, lo1): at most one root into out, see the head of this file.  Ref: where the cell's own
+// coefficients come from, load_cell<K0, K1>(ref, c): CellRef reads them, bsk_rays.hpp's RayCell forms them.
+template <int K0, int K1, class Ref>
+BSK_HD void leaf(const Ref &ref, double lo0, double lo1, double t0u, double hu, double t0v, double hv, double S0, double S1,
                  double *out, uint8_t *near, int &count, unsigned &status)
 {
     constexpr int R = slots(K0, K1);
@@ -300,8 +301,8 @@ BSK_HD void leaf(const CellRef &ref, double lo0, double lo1, double t0u, double 
 }
 
 // out: R x 2 slots (the roots in front, NaN behind), near: R bytes.  The cell is a candidate (roots2_flag said 1).
-template <int K0, int K1>
-BSK_HD void isolate_cell(const CellRef &ref, double t0u, double t1u, double t0v, double t1v, double S0, double S1, double *out,
+template <int K0, int K1, class Ref>
+BSK_HD void isolate_cell(const Ref &ref, double t0u, double t1u, double t0v, double t1v, double S0, double S1, double *out,
                          uint8_t *near, int32_t *count_out, uint8_t *status_out, int32_t *nodes_out)
 {
     constexpr int R = slots(K0, K1);
@@ -455,7 +456,8 @@ BSK_HD void merge_lane(long long lane, int R, const double *roots, long long nsy
     keep[at] = k;
 }
 
-#ifdef __HIPCC__
+// BSK_ROOTS2_FUNCTIONS_ONLY: a unit that takes the walk for cells of its own (bsk_rays.hpp) leaves the kernels to bsk_roots2_tu.hip
+#if defined(__HIPCC__) && !defined(BSK_ROOTS2_FUNCTIONS_ONLY)
 template <int K0, int K1>
 __global__ __launch_bounds__(ROOTS2_BLOCK) void roots2_flag(Grid g, const uint8_t *__restrict__ mask, uint8_t *__restrict__ flags)
 {

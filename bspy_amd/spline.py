@@ -474,6 +474,22 @@ class Spline:
         from . import project as _project
         return _project.project(self, points, guess=guess, samples=samples, **kwargs)
 
+    def intersect_rays(self, origins, directions, tmin=0.0, tmax=float("inf"), **kwargs):
+        """Where N rays o + t d hit this surface, and which hit comes first (an extension: the reference has no
+        counterpart).  ``origins``, ``directions``: (3, *shape), NumPy float32 / float64 or torch CUDA tensors of those
+        types; directions need not be normalised.  Returns ``(uv, t)``: the parameters (2, *shape) in the knots' dtype and
+        t (*shape) in float64 with S(uv) = o + t d, for the hit of smallest t in [tmin, tmax]; NaN for a ray without a hit;
+        CUDA in gives CUDA out.  Surfaces (nInd 2, nDep 3) of orders 2 .. 4; anything else raises NotImplementedError.  A
+        hit is a common zero of the two planes of the ray on the surface: almost every (ray, knot cell) pair is discarded
+        by a box test and the rest is isolated by the walk of ``zeros2``.  What is computed is stated in
+        bspy_amd/rays.py; results are bitwise reproducible and the same on both paths.  A grazing hit (the ray
+        tangent to the surface) may be missed silently: only transversal hits are promised.  One RuntimeWarning when a ray
+        carries a status bit (a ray in the plane of a flat cell, a ray that is not finite, a walk that hit a bound);
+        ``bspy_amd.rays.cast_batch`` returns the status, the cell and the number of hits of every ray and, with
+        hits="all", every hit.  ``_path="device"`` / ``"host"`` pins the path."""
+        from . import rays as _rays
+        return _rays.intersect_rays(self, origins, directions, tmin=tmin, tmax=tmax, **kwargs)
+
     def contours(self, tolerance=None, depth=None, **kwargs):
         """The level curves {f = 0} of a scalar spline in two variables (nInd == 2, nDep == 1; reference spline.py
         ``contours``, whose other shapes are not built): a list of curves (nInd 1, nDep 2, on [0, 1], order 4, f >= 0 on

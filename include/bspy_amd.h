@@ -448,6 +448,100 @@ bsk_status bsk_roots2_merge(int R, const double *roots, int64_t nsys, int64_t nc
 const char *bsk_roots2_last_kernel(void);
 
 /*
+ * Ray-surface hits (Spline.intersect_rays, bspy_amd.rays.cast_batch; the statement of what a hit is and of the arithmetic is
+ * in bspy_amd/rays.py and DESIGN.md section 22).  The family keeps no handle.  The caller brings the surface (nInd 2,
+ * nDep 3) to Bezier form with the band operator: rows[3][R0][R1] (doubles), and cell (i, j), flat index i * nc1 + j, is
+ * the K0 x K1 window of the three components at first0[i], first1[j]; it covers [breaks0[i], breaks0[i + 1]] x
+ * [breaks1[j], breaks1[j + 1]].  Rays: origins[3][nrays], dirs[3][nrays] (doubles), cmax[3] = max |coefficient| per
+ * component.  A hit of ray r is a common zero of g_k = n_k . (S - o), k = 1, 2, the two planes of the ray's frame; a
+ * cell's coefficients of g_k are formed from the window and the ray, never stored.  A window that leaves the rows, or an
+ * index that is no cell, no ray or no pair, gives no hit instead of an access out of bounds.
+ *   bsk_rays_boxes(_host)  : boxes[nc0 * nc1][6] = min and max of the window per component (lo0, hi0, lo1, hi1, lo2, hi2).
+ *   bsk_rays_count(_host)  : the cells in chunks of `chunk`, nchunks = ceil(cells / chunk) <= 65535; partial[nrays][nchunks]
+ *                            (int32) = the pairs (ray, cell) of the chunk that pass the slab test against the box on
+ *                            [tmin, tmax] (prefilter != 0) and are flat or not of one sign in g_1 or g_2; skipped[nrays]
+ *                            (bytes) = 8 for a ray with a non-finite entry or a zero direction, which has no pairs.
+ *   bsk_rays_emit(_host)   : the same search; offset[nrays][nchunks] (int64) = the exclusive sums of partial in that order;
+ *                            pair_ray, pair_cell[npairs] (int32), npairs >= 1: a ray's pairs are contiguous, cells ascending.
+ *   bsk_rays_isolate(_host): per pair the walk of bsk_roots2_isolate on the formed cell, with the ray's S_1, S_2 as the
+ *                            scale: roots[npairs][R][2] as (u, v), R = 2 (K0 - 1)(K1 - 1), NaN behind the last one;
+ *                            near[npairs][R], count, status, nodes[npairs] as there; status bit 16 = the ray lies in the
+ *                            plane of a flat cell (all K0 K1 values of a g_k below S_k eps): not walked.
+ *   bsk_rays_reduce(_host) : pstart[nrays + 1] (int64) = where a ray's pairs start.  Per ray: a root near an edge of its
+ *                            cell is dropped when a pair of the same ray on a neighbouring cell with a lower flat index
+ *                            holds one within 2^-20 of the cell widths; t = (S_c(u, v) - o_c) / d_c on the dominant axis c;
+ *                            a hit has tmin <= t <= tmax.  all == 0: uv[2][nrays], t, cell (-1: no hit), hits[nrays]
+ *                            (int32), status[nrays] (bytes, the OR of skipped and the pairs' status) of the hit of smallest
+ *                            t; all != 0: every hit of ray r at hit_off[r] + n, n < hits[r], in (cell, slot) order:
+ *                            uv[nhits][2], t, cell[nhits]; hits and status are not written.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1 in 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above) on both sides.  No atomics, no waiting, no declared LDS; the host drivers and the kernels give
+ *   the same bits.
+ *   bsk_rays_last_kernel   : "ray_boxes", "ray_count", "ray_emit", "ray_isolate", "ray_reduce", "ray_reduce all" or the
+ *                            same behind "host ".
+ */
+bsk_status bsk_rays_boxes_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                               const int32_t *first0, const int32_t *first1,
+                               double *boxes);
+bsk_status bsk_rays_boxes(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                          const int32_t *first0, const int32_t *first1,
+                          double *boxes,
+                          void *stream);
+bsk_status bsk_rays_count_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                               const int32_t *first0, const int32_t *first1,
+                               const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                               double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
+                               int32_t *partial, uint8_t *skipped);
+bsk_status bsk_rays_count(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                          const int32_t *first0, const int32_t *first1,
+                          const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                          double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
+                          int32_t *partial, uint8_t *skipped,
+                          void *stream);
+bsk_status bsk_rays_emit_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                              const int32_t *first0, const int32_t *first1,
+                              const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                              double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
+                              const int64_t *offset, int32_t *pair_ray, int32_t *pair_cell, int64_t npairs);
+bsk_status bsk_rays_emit(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                         const int32_t *first0, const int32_t *first1,
+                         const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                         double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
+                         const int64_t *offset, int32_t *pair_ray, int32_t *pair_cell, int64_t npairs,
+                         void *stream);
+bsk_status bsk_rays_isolate_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                                 const int32_t *first0, const int32_t *first1,
+                                 const double *breaks0, const double *breaks1,
+                                 const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                                 const int32_t *pair_ray, const int32_t *pair_cell, int64_t npairs, double *roots, uint8_t *near,
+                                 int32_t *count, uint8_t *status, int32_t *nodes);
+bsk_status bsk_rays_isolate(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                            const int32_t *first0, const int32_t *first1,
+                            const double *breaks0, const double *breaks1,
+                            const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                            const int32_t *pair_ray, const int32_t *pair_cell, int64_t npairs, double *roots, uint8_t *near,
+                            int32_t *count, uint8_t *status, int32_t *nodes,
+                            void *stream);
+bsk_status bsk_rays_reduce_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                                const int32_t *first0, const int32_t *first1,
+                                const double *breaks0, const double *breaks1,
+                                const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                                double tmin, double tmax, const int64_t *pstart, const int32_t *pair_cell, int64_t npairs,
+                                const double *roots, const uint8_t *near, const int32_t *count, const uint8_t *pstatus,
+                                const uint8_t *skipped, int all, const int64_t *hit_off, int64_t nhits, double *uv, double *t,
+                                int32_t *cell, int32_t *hits, uint8_t *status);
+bsk_status bsk_rays_reduce(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
+                           const int32_t *first0, const int32_t *first1,
+                           const double *breaks0, const double *breaks1,
+                           const double *cmax, const double *origins, const double *dirs, int64_t nrays,
+                           double tmin, double tmax, const int64_t *pstart, const int32_t *pair_cell, int64_t npairs,
+                           const double *roots, const uint8_t *near, const int32_t *count, const uint8_t *pstatus,
+                           const uint8_t *skipped, int all, const int64_t *hit_off, int64_t nhits, double *uv, double *t,
+                           int32_t *cell, int32_t *hits, uint8_t *status,
+                           void *stream);
+const char *bsk_rays_last_kernel(void);
+
+/*
  * Isolated common zeros of three scalar splines in three variables (Spline.zeros3; the statement of what a zero is and of
  * the arithmetic is in bspy_amd/roots3.py and DESIGN.md section 19).  The family keeps no handle.  The caller brings the
  * three variables to Bezier form with the band operator: rows[nsys][3][R0][R1][R2] (doubles) holds nsys systems of three
