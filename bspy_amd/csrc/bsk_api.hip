@@ -174,6 +174,18 @@ static bsk_status upload_uniform(bsk_spline s, const void *const *knots, const v
 template <typename T>
 static bsk_status upload_uniform_nd(bsk_spline s, const void *const *knots, const void *coefs);   // ... of the other LDS-resident shapes
 
+// Everything bsk_spline_create and bsk_spline_update put on the device: the tables, then the images of the uniform paths.
+static bsk_status upload_all(bsk_spline s, const void *const *knots, const void *coefs)
+{
+    return with_dtype(s->dtype, [&](auto z) {
+        using T = decltype(z);
+        bsk_status st = upload_tables<T>(s, knots, coefs);
+        if (st == BSK_OK) st = upload_uniform<T>(s, knots, coefs);
+        if (st == BSK_OK) st = upload_uniform_nd<T>(s, knots, coefs);
+        return st;
+    });
+}
+
 extern "C" int bsk_version(void) { return BSK_VERSION; }
 extern "C" const char *bsk_last_error(void) { return g_err.c_str(); }
 
@@ -221,7 +233,7 @@ extern "C" bsk_status bsk_spline_create(bsk_dtype dtype, int device, int nInd, i
         s->ncoef[iv] = nCoef[iv];
         if (order[iv] != order[0]) s->same_order = false;
     }
-    bsk_status st = dtype == BSK_F32 ? init_desc<float>(s) : init_desc<double>(s);
+    bsk_status st = with_dtype(dtype, [&](auto z) { return init_desc<decltype(z)>(s); });
     if (st != BSK_OK) { delete s; return st; }
     const int tab_len = dtype == BSK_F32 ? s->d32.tab_len : s->d64.tab_len;
     const int coef_len = dtype == BSK_F32 ? s->d32.coef_len : s->d64.coef_len;
@@ -253,9 +265,8 @@ extern "C" bsk_status bsk_spline_create(bsk_dtype dtype, int device, int nInd, i
     HIPCHK_C(hipMalloc(&s->coef, std::max<size_t>(16, s->esize * (size_t)coef_len)));
     {
         const size_t tbytes = s->esize * (size_t)tab_len + s->esize * (size_t)coef_len;
-        int omax = 0;
-        for (int iv = 0; iv < nInd; ++iv) omax = std::max(omax, order[iv]);
-        bool fixed = nInd <= 3 && omax <= 6;                  // gather / cell-order kernels: any mix of orders <= 6
+        const int omax = max_order(s);
+        const bool fixed = nInd <= 3 && omax <= 6;                 // gather / cell-order kernels: any mix of orders <= 6
         if (fixed && nDep <= 4 && tbytes + 8192 > s->lds_max)
             HIPCHK_C(hipMalloc(&s->coef_aos, std::max<size_t>(16, s->esize * (size_t)coef_len)));
         else if (fixed && nDep <= 4 && nInd == 2 && !s->same_order && omax >= 2) {
@@ -269,9 +280,7 @@ extern "C" bsk_status bsk_spline_create(bsk_dtype dtype, int device, int nInd, i
     if (const char *v = getenv("BSK_VARIANT")) s->variant = atoi(v);
     HIPCHK_C(hipMemset(s->bad, 0xff, 2 * sizeof(unsigned long long)));
 #undef HIPCHK_C
-    st = dtype == BSK_F32 ? upload_tables<float>(s, knots, coefs) : upload_tables<double>(s, knots, coefs);
-    if (st == BSK_OK) st = dtype == BSK_F32 ? upload_uniform<float>(s, knots, coefs) : upload_uniform<double>(s, knots, coefs);
-    if (st == BSK_OK) st = dtype == BSK_F32 ? upload_uniform_nd<float>(s, knots, coefs) : upload_uniform_nd<double>(s, knots, coefs);
+    st = upload_all(s, knots, coefs);
     if (st != BSK_OK) { s->uni_img.release(); cleanup(); return st; }
     *out = s;
     return BSK_OK;
@@ -282,11 +291,7 @@ extern "C" bsk_status bsk_spline_update(bsk_spline s, const void *const *knots, 
     if (!s || !knots || !coefs) return fail(BSK_ERR_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipDeviceSynchronize());
-    const bsk_status st = s->dtype == BSK_F32 ? upload_tables<float>(s, knots, coefs) : upload_tables<double>(s, knots, coefs);
-    if (st != BSK_OK) return st;
-    const bsk_status su = s->dtype == BSK_F32 ? upload_uniform<float>(s, knots, coefs) : upload_uniform<double>(s, knots, coefs);
-    if (su != BSK_OK) return su;
-    return s->dtype == BSK_F32 ? upload_uniform_nd<float>(s, knots, coefs) : upload_uniform_nd<double>(s, knots, coefs);
+    return upload_all(s, knots, coefs);
 }
 
 extern "C" bsk_status bsk_spline_destroy(bsk_spline s)
@@ -419,7 +424,6 @@ static bool has_fixed_path(bsk_spline s)
     return s->same_order && s->nInd >= 1 && s->nInd <= 3 && s->order[0] >= 1 && s->order[0] <= 6;
 }
 
-// eval_rowrot / jac_rowrot / fused normal: surfaces of order 2 or 4 whose odd-stride image fits LDS
 // Points per launch of the rowrot kernels (32-bit indices).  BSK_RR_CHUNK lowers it so that the
 // chunk loop can be exercised by tests without a 2^28-point batch.
 static long long rr_chunk_points()
@@ -457,11 +461,68 @@ static size_t rowrot_lds_bytes(bsk_spline s)
     return rec_b + rr_lut_bytes<T>(tdr.lut_len) + coef_b + TILE * sizeof(unsigned);
 }
 
+// eval_rowrot / jac_rowrot / fused normal: surfaces of order 2 or 4 whose odd-stride image fits LDS
 template <typename T>
 static bool rowrot_applies(bsk_spline s)
 {
     return has_fixed_path(s) && s->nInd == 2 && (s->order[0] == 2 || s->order[0] == 4) &&
            (s->variant == 0 || s->variant == 9) && rowrot_lds_bytes<T>(s) <= s->lds_max;
+}
+
+// The LDS-staging kernels (eval_fixed / jac_fixed / eval_mixed / jac_mixed) keep at least the axis tables in LDS.
+static bool axis_tables_fit_lds(bsk_spline s)
+{
+    const size_t tab_len = s->dtype == BSK_F32 ? (size_t)s->d32.tab_len : (size_t)s->d64.tab_len;
+    return s->esize * (tab_len + 2) + 1024 <= s->lds_max;
+}
+
+// ------------------------------------------------------------------------------------
+// shape classifier
+// ------------------------------------------------------------------------------------
+// What the point paths ask about a spline, answered once per call by point_shape() and read by the two ladders
+// (dispatch_eval, dispatch_jac), by the launch functions they choose and by run_normal / run_curvature.  Nothing of it is
+// kept in the handle: bsk_spline_update may change uni and uniN.  A new rung of a ladder that asks a new question about
+// the shape gets its answer HERE, not a predicate call of its own.
+struct PointShape {
+    int omax;               // largest order of the variables
+    bool fixed;             // has_fixed_path: nInd 1..3, one common order 1..6
+    size_t lds;             // bytes of the LDS table image (tile_lds_bytes), 0: it does not fit
+    bool axis_lds;          // axis_tables_fit_lds: the LDS-staging kernels apply
+    size_t lds_rowrot;      // bytes of the odd-stride image of the rowrot family (only when `rowrot`)
+    bool rowrot;            // rowrot_applies: surface of order 2 / 4 whose odd-stride image fits LDS
+    bool uni, uniN;         // equally spaced knots: the table-free front ends (surfaces of order 2 / 4; the other LDS-resident shapes)
+    // The asm-LDS family (eval_stream / jac_stream and, inside it, the rowrot family) covers orders 1..5: at order 6 its
+    // register windows (36-value slabs, 20 table values per variable) no longer fit without spilling, which those
+    // kernels must never do (check_spills.py); order 6 runs on eval_fixed - except curves, whose single window row
+    // fits up to order 8.  BSK_VARIANT=1 pins eval_fixed.
+    bool lds_curve;         // curve of order 6..8 on a table image that fits
+    bool lds_nd;            // nInd 1..3 of one order 1..5 on a table image that fits
+};
+
+template <typename T>
+static PointShape point_shape(bsk_spline s)
+{
+    PointShape ps;
+    ps.omax = max_order(s);
+    ps.fixed = has_fixed_path(s);
+    ps.lds = tile_lds_bytes<T>(s);
+    ps.axis_lds = axis_tables_fit_lds(s);
+    ps.rowrot = rowrot_applies<T>(s);
+    ps.lds_rowrot = ps.rowrot ? rowrot_lds_bytes<T>(s) : 0;
+    ps.uni = s->uni;
+    ps.uniN = s->uniN;
+    ps.lds_curve = s->nInd == 1 && s->order[0] >= 6 && s->order[0] <= 8 && s->variant != 1 && ps.lds != 0;
+    ps.lds_nd = ps.fixed && s->variant != 1 && s->order[0] <= 5 && ps.lds != 0;
+    return ps;
+}
+
+// f(nInd, order) with both as template constants, for nInd 1..3 of one common order LO..HI (the rung has checked both)
+template <int LO, int HI, typename F>
+static bsk_status with_nind_order(bsk_spline s, F &&f)
+{
+    return with_range<1, 3>(s->nInd, [&](auto ni) {
+        return with_range<LO, HI>(s->order[0], [&](auto o) { return f(ni, o); });
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -735,12 +796,12 @@ static dim3 rr_grid(bsk_spline s, long long m, size_t lds)
 // The number of dependent variables is a template constant up to 3 (0 = run-time loop) in jac_uni / jac_rowrot;
 // the fused normal (NORMAL) instantiates one class of each.
 template <typename T, bool NORMAL>
-static bsk_status launch_jac_rowrot(bsk_spline s, const Params<T> &prm, long long n, T *out, int normalize, int negate,
-                                    hipStream_t st)
+static bsk_status launch_jac_rowrot(bsk_spline s, const PointShape &ps, const Params<T> &prm, long long n, T *out,
+                                    int normalize, int negate, hipStream_t st)
 {
     return with_int<4, 2>(s->order[0], [&](auto o) {
         constexpr int O = decltype(o)::value;
-        if (s->uni) {
+        if (ps.uni) {
             // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
             const UniDesc<T> &ud = uni_of<T>(s);
             const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
@@ -753,7 +814,7 @@ static bsk_status launch_jac_rowrot(bsk_spline s, const Params<T> &prm, long lon
             if constexpr (NORMAL) return go(std::integral_constant<int, 3>{});
             else return with_int<1, 2, 3, 0>(s->nDep, go);
         }
-        const size_t lds_rr = rowrot_lds_bytes<T>(s);
+        const size_t lds_rr = ps.lds_rowrot;
         auto go = [&](auto nd) {
             return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
                 return launch(s, "jac_rowrot", jac_rowrot<T, O, NORMAL, decltype(nd)::value>, rr_grid(s, m, lds_rr), dim3(TILE),
@@ -767,9 +828,10 @@ static bsk_status launch_jac_rowrot(bsk_spline s, const Params<T> &prm, long lon
 }
 
 template <typename T, int NIND, int O>
-static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm, long long n, T *out, long long ostride,
-                                  const Wrt &w, hipStream_t st)
+static bsk_status launch_eval_lds(bsk_spline s, const PointShape &ps, const Params<T> &prm, long long n, T *out,
+                                  long long ostride, const Wrt &w, hipStream_t st)
 {
+    const size_t lds = ps.lds;
     const Desc<T> &d = desc_of<T>(s);
     const TileDesc<T> &td = tile_of<T>(s);
     const T *tab = static_cast<const T *>(s->tab);
@@ -781,8 +843,8 @@ static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm
         constexpr bool DERIV = decltype(dv)::value;
         if constexpr (NIND == 2 && (O == 2 || O == 4)) {
             // surfaces of order 2 / 4: row rotation on an odd-stride LDS image
-            if (rowrot_applies<T>(s)) {
-                if (s->uni) {
+            if (ps.rowrot) {
+                if (ps.uni) {
                     // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
                     const UniDesc<T> &ud = uni_of<T>(s);
                     const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
@@ -806,7 +868,7 @@ static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm
                             });
                         });
                 }
-                const size_t lds_rr = rowrot_lds_bytes<T>(s);
+                const size_t lds_rr = ps.lds_rowrot;
                 return with_int<1, 2, 3, 0>(s->nDep, [&](auto nd) {         // 0 = run-time loop
                     return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
                         return launch(s, "eval_rowrot", eval_rowrot<T, O, DERIV, decltype(nd)::value>, rr_grid(s, m, lds_rr),
@@ -817,7 +879,7 @@ static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm
             }
         }
         if constexpr (O <= 5) {
-            if (s->uniN) {
+            if (ps.uniN) {
                 // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
                 const UniDescN<T> &un = uniN_of<T>(s);
                 const size_t lds_u = un.img_bytes;
@@ -831,30 +893,14 @@ static bsk_status launch_eval_lds(bsk_spline s, size_t lds, const Params<T> &prm
     });
 }
 
-// The LDS-staging kernels (eval_fixed / jac_fixed / eval_mixed) keep at least the axis tables in LDS.
-static bool axis_tables_fit_lds(bsk_spline s)
-{
-    const size_t tab_len = s->dtype == BSK_F32 ? (size_t)s->d32.tab_len : (size_t)s->d64.tab_len;
-    return s->esize * (tab_len + 2) + 1024 <= s->lds_max;
-}
-
-#define BSK_ORDER_SWITCH(NIND, CALL)                        \
-    switch (s->order[0]) {                                  \
-        case 1: return CALL(NIND, 1);                       \
-        case 2: return CALL(NIND, 2);                       \
-        case 3: return CALL(NIND, 3);                       \
-        case 4: return CALL(NIND, 4);                       \
-        case 5: return CALL(NIND, 5);                       \
-        case 6: return CALL(NIND, 6);                       \
-        default: break;                                     \
-    }
-
 template <typename T, int NIND, int O>
-static bsk_status launch_jac_stream(bsk_spline s, size_t lds, const Params<T> &prm, long long n, T *out, hipStream_t st)
+static bsk_status launch_jac_stream(bsk_spline s, const PointShape &ps, const Params<T> &prm, long long n, T *out,
+                                    hipStream_t st)
 {
+    const size_t lds = ps.lds;
     const long long ntiles = (n + STREAM_BLOCK - 1) / STREAM_BLOCK;
     if constexpr (O <= 5) {
-        if (s->uniN) {
+        if (ps.uniN) {
             const UniDescN<T> &un = uniN_of<T>(s);
             const size_t lds_u = un.img_bytes;
             return launch(s, "jac_stream_uni", jac_stream_uni<T, NIND, O>,
@@ -867,151 +913,109 @@ static bsk_status launch_jac_stream(bsk_spline s, size_t lds, const Params<T> &p
                   static_cast<const T *>(s->coef), prm, n, out, s->bad);
 }
 
-// The asm-LDS kernels (tile / stream) cover orders 1..5: at order 6 their register windows
-// (36-value slabs, 20 table values per variable) no longer fit without spilling, which those
-// kernels must never do (check_spills.py); order 6 runs on eval_fixed - except curves, whose single
-// window row fits up to order 8 (dispatched before this switch).
-#define BSK_ORDER_SWITCH5(NIND, CALL)                       \
-    switch (s->order[0]) {                                  \
-        case 1: return CALL(NIND, 1);                       \
-        case 2: return CALL(NIND, 2);                       \
-        case 3: return CALL(NIND, 3);                       \
-        case 4: return CALL(NIND, 4);                       \
-        case 5: return CALL(NIND, 5);                       \
-        default: break;                                     \
-    }
-
+// The evaluation ladder.  Every rung that turns nInd or an order into a template constant stands behind the range
+// check the rung itself makes: with_range hands its last value to any value outside its range.
 template <typename T>
-static bsk_status dispatch_eval(bsk_spline s, const Params<T> &prm, long long n, T *out, long long ostride,
-                                const Wrt &w, hipStream_t st)
+static bsk_status dispatch_eval(bsk_spline s, const PointShape &ps, const Params<T> &prm, long long n, T *out,
+                                long long ostride, const Wrt &w, hipStream_t st)
 {
     if (n <= 0) return BSK_OK;
-    if (s->nInd == 1 && s->order[0] >= 6 && s->order[0] <= 8 && s->variant != 1) {
+    if (ps.lds_curve)
         // curves of order 6..8: one window row per dependent variable still fits the registers
-        const size_t lds = tile_lds_bytes<T>(s);
-        if (lds != 0) switch (s->order[0]) {
-            case 6: return launch_eval_lds<T, 1, 6>(s, lds, prm, n, out, ostride, w, st);
-            case 7: return launch_eval_lds<T, 1, 7>(s, lds, prm, n, out, ostride, w, st);
-            default: return launch_eval_lds<T, 1, 8>(s, lds, prm, n, out, ostride, w, st);
-        }
-    }
-    if (has_fixed_path(s) && s->variant != 1 && s->order[0] <= 5) {
-        // table image fits in LDS: eval_rowrot (surfaces of order 2 / 4) or eval_stream
-        const size_t lds = tile_lds_bytes<T>(s);
-        if (lds != 0) {
-#define CALL_LDS(NIND, O) launch_eval_lds<T, NIND, O>(s, lds, prm, n, out, ostride, w, st)
-            if (s->nInd == 1) { BSK_ORDER_SWITCH5(1, CALL_LDS) }
-            else if (s->nInd == 2) { BSK_ORDER_SWITCH5(2, CALL_LDS) }
-            else { BSK_ORDER_SWITCH5(3, CALL_LDS) }
-#undef CALL_LDS
-        }
-    }
-    if (has_fixed_path(s) && s->coef_aos && s->variant != 1) {
+        return with_range<6, 8>(s->order[0], [&](auto o) {
+            return launch_eval_lds<T, 1, decltype(o)::value>(s, ps, prm, n, out, ostride, w, st);
+        });
+    if (ps.lds_nd)
+        // table image fits in LDS: the rowrot family (surfaces of order 2 / 4) or eval_stream
+        return with_nind_order<1, 5>(s, [&](auto ni, auto o) {
+            return launch_eval_lds<T, decltype(ni)::value, decltype(o)::value>(s, ps, prm, n, out, ostride, w, st);
+        });
+    if (ps.fixed && s->coef_aos && s->variant != 1) {
         // table too large for LDS: control-point-major gather / cell-order pipeline (bsk_gather_tu.hip)
         const bsk_status r = gather_or_binned_any<T>(s, false, prm, n, out, ostride, w, st);
         if (r != BSK_ERR_UNSUPPORTED) return r;
     }
-    if (has_fixed_path(s) && axis_tables_fit_lds(s)) {
+    if (ps.fixed && ps.axis_lds) {
         const Plan p = make_plan<T>(s, n);
-#define CALL_EVAL(NIND, O) launch_eval_fixed<T, NIND, O>(s, p, prm, n, out, ostride, w, st)
-        if (s->nInd == 1) { BSK_ORDER_SWITCH(1, CALL_EVAL) }
-        else if (s->nInd == 2) { BSK_ORDER_SWITCH(2, CALL_EVAL) }
-        else { BSK_ORDER_SWITCH(3, CALL_EVAL) }
-#undef CALL_EVAL
+        return with_nind_order<1, 6>(s, [&](auto ni, auto o) {
+            return launch_eval_fixed<T, decltype(ni)::value, decltype(o)::value>(s, p, prm, n, out, ostride, w, st);
+        });
     }
     // What is left: variables of different orders, or orders beyond the fixed-order kernels.
-    if (s->nInd >= 1 && s->nInd <= 5 && s->variant != 1 && axis_tables_fit_lds(s)) {
-        int omax = 0;
-        for (int iv = 0; iv < s->nInd; ++iv) omax = std::max(omax, s->order[iv]);
+    if (s->nInd >= 1 && s->nInd <= 5 && s->variant != 1 && ps.axis_lds) {
+        const int omax = ps.omax;
         if (!s->same_order && omax >= 2 && omax <= 6 && s->coef_aos) {
             // table too large for LDS: control-point-major gather / cell-order pipeline at O = omax; an LDS-resident
-            // surface: eval_slab2 with the whole table as its one slab (batches below 65536 points: eval_mixed)
+            // surface: eval_slab2 with the whole table as its one slab (batches below 2^20 points: eval_mixed)
             const bsk_status r = s->aos_small ? slab2_any<T>(s, true, prm, n, out, ostride, w, st)
                                               : gather_or_binned_any<T>(s, true, prm, n, out, ostride, w, st);
             if (r != BSK_ERR_UNSUPPORTED) return r;
         }
-        // eval_mixed: surfaces up to order 8, volumes up to 6, curves up to 12, four variables up to order 4, five up to 3
+        // eval_mixed: curves of order 9..12, surfaces up to order 8, volumes up to 6, four variables up to order 4, five up to 3
         const Plan p = make_plan<T>(s, n);
-#define MIXED_CASE(NIND, OM) case OM: return launch_eval_mixed<T, NIND, OM>(s, p, prm, n, out, ostride, w, st);
-        if (s->nInd == 1 && omax >= 9 && omax <= 12) {
-            switch (omax) { MIXED_CASE(1, 9) MIXED_CASE(1, 10) MIXED_CASE(1, 11) MIXED_CASE(1, 12) default: break; }
-        } else if (s->nInd == 2 && omax >= 2 && omax <= 8) {
-            switch (omax) { MIXED_CASE(2, 2) MIXED_CASE(2, 3) MIXED_CASE(2, 4) MIXED_CASE(2, 5) MIXED_CASE(2, 6) MIXED_CASE(2, 7) MIXED_CASE(2, 8) default: break; }
-        } else if (s->nInd == 3 && omax >= 2 && omax <= 6) {
-            switch (omax) { MIXED_CASE(3, 2) MIXED_CASE(3, 3) MIXED_CASE(3, 4) MIXED_CASE(3, 5) MIXED_CASE(3, 6) default: break; }
-        } else if (s->nInd == 4 && omax >= 2 && omax <= 4) {
-            switch (omax) { MIXED_CASE(4, 2) MIXED_CASE(4, 3) MIXED_CASE(4, 4) default: break; }
-        } else if (s->nInd == 5 && omax >= 2 && omax <= 3) {
-            switch (omax) { MIXED_CASE(5, 2) MIXED_CASE(5, 3) default: break; }
-        }
-#undef MIXED_CASE
+        auto mixed = [&](auto ni, auto om) {
+            return launch_eval_mixed<T, decltype(ni)::value, decltype(om)::value>(s, p, prm, n, out, ostride, w, st);
+        };
+        const auto in = [omax](int lo, int hi) { return omax >= lo && omax <= hi; };
+        if (s->nInd == 1 && in(9, 12)) return with_range<9, 12>(omax, [&](auto om) { return mixed(int_c<1>{}, om); });
+        if (s->nInd == 2 && in(2, 8)) return with_range<2, 8>(omax, [&](auto om) { return mixed(int_c<2>{}, om); });
+        if (s->nInd == 3 && in(2, 6)) return with_range<2, 6>(omax, [&](auto om) { return mixed(int_c<3>{}, om); });
+        if (s->nInd == 4 && in(2, 4)) return with_range<2, 4>(omax, [&](auto om) { return mixed(int_c<4>{}, om); });
+        if (s->nInd == 5 && in(2, 3)) return with_range<2, 3>(omax, [&](auto om) { return mixed(int_c<5>{}, om); });
     }
     return launch_eval_generic<T>(s, prm, n, out, ostride, w, st);
 }
 
+// The jacobian ladder: the rungs of dispatch_eval in the same order, with three exceptions, each a named condition below.
 template <typename T>
-static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, T *out, hipStream_t st)
+static bsk_status dispatch_jac(bsk_spline s, const PointShape &ps, const Params<T> &prm, long long n, T *out, hipStream_t st)
 {
     if (n <= 0) return BSK_OK;
-    if (rowrot_applies<T>(s)) return launch_jac_rowrot<T, false>(s, prm, n, out, 0, 0, st);
-    if (s->nInd == 1 && s->order[0] >= 6 && s->order[0] <= 8 && s->variant != 1) {
-        const size_t lds = tile_lds_bytes<T>(s);
-        if (lds != 0) switch (s->order[0]) {
-            case 6: return launch_jac_stream<T, 1, 6>(s, lds, prm, n, out, st);
-            case 7: return launch_jac_stream<T, 1, 7>(s, lds, prm, n, out, st);
-            default: return launch_jac_stream<T, 1, 8>(s, lds, prm, n, out, st);
-        }
+    // Exception 1: the rowrot family comes first and asks for its own odd-stride image alone (the evaluation reaches the
+    // family inside launch_eval_lds, behind the fit of the table image)
+    if (ps.rowrot) return launch_jac_rowrot<T, false>(s, ps, prm, n, out, 0, 0, st);
+    if (ps.lds_curve)
+        return with_range<6, 8>(s->order[0], [&](auto o) {
+            return launch_jac_stream<T, 1, decltype(o)::value>(s, ps, prm, n, out, st);
+        });
+    // Exception 2: three variables, order 5: two 25-value windows spill -> jac_fixed (jac_stream<T, 3, 5> is not instantiated)
+    const bool volume_order5 = s->nInd == 3 && s->order[0] == 5;
+    if (ps.lds_nd && !volume_order5) {
+        auto stream = [&](auto ni, auto o) {
+            return launch_jac_stream<T, decltype(ni)::value, decltype(o)::value>(s, ps, prm, n, out, st);
+        };
+        if (s->nInd == 3) return with_range<1, 4>(s->order[0], [&](auto o) { return stream(int_c<3>{}, o); });
+        return with_range<1, 2>(s->nInd, [&](auto ni) {
+            return with_range<1, 5>(s->order[0], [&](auto o) { return stream(ni, o); });
+        });
     }
-    if (has_fixed_path(s) && s->variant != 1 && s->order[0] <= 5) {
-        const size_t lds = tile_lds_bytes<T>(s);
-        if (lds != 0) {
-#define CALL_JACS(NIND, O) launch_jac_stream<T, NIND, O>(s, lds, prm, n, out, st)
-            if (s->nInd == 1) { BSK_ORDER_SWITCH5(1, CALL_JACS) }
-            else if (s->nInd == 2) { BSK_ORDER_SWITCH5(2, CALL_JACS) }
-            else {
-                switch (s->order[0]) {      // three variables, order 5: two 25-value windows spill -> jac_fixed
-                    case 1: return CALL_JACS(3, 1);
-                    case 2: return CALL_JACS(3, 2);
-                    case 3: return CALL_JACS(3, 3);
-                    case 4: return CALL_JACS(3, 4);
-                    default: break;
-                }
-            }
-#undef CALL_JACS
-        }
-    }
-    // L2-resident table and a batch large enough for the cell-order pipeline: nInd derivative passes through
+    // Exception 3: L2-resident table and a batch large enough for the cell-order pipeline: nInd derivative passes through
     // it beat jac_fixed's batch-order gathers (cfg5 shape, 10 M points: 4.8 -> 2.7 ms)
     const bool passes_in_cell_order = s->coef_aos && s->nInd >= 2 && n >= (1ll << 18) && s->variant != 7 && s->variant != 1;
-    if (has_fixed_path(s) && axis_tables_fit_lds(s) && !passes_in_cell_order) {
+    if (ps.fixed && ps.axis_lds && !passes_in_cell_order) {
         const Plan p = make_plan<T>(s, n);
-#define CALL_JAC(NIND, O) launch_jac_fixed<T, NIND, O>(s, p, prm, n, out, st)
-        if (s->nInd == 1) { BSK_ORDER_SWITCH(1, CALL_JAC) }
-        else if (s->nInd == 2) { BSK_ORDER_SWITCH(2, CALL_JAC) }
-        else { BSK_ORDER_SWITCH(3, CALL_JAC) }
-#undef CALL_JAC
+        return with_nind_order<1, 6>(s, [&](auto ni, auto o) {
+            return launch_jac_fixed<T, decltype(ni)::value, decltype(o)::value>(s, p, prm, n, out, st);
+        });
     }
     // variables of different orders (or orders beyond jac_fixed) with LDS-resident tables: jac_mixed
     // (mixed-order surface, 10 M points, order (3,4): jac_mixed 309 us; two derivative passes of eval_slab2 in one slab 286 us -
     //  measured, not worth a second path)
-    if ((s->nInd == 2 || s->nInd == 3) && s->variant != 1 && axis_tables_fit_lds(s)) {
-        int omax = 0;
-        for (int iv = 0; iv < s->nInd; ++iv) omax = std::max(omax, s->order[iv]);
+    if ((s->nInd == 2 || s->nInd == 3) && s->variant != 1 && ps.axis_lds) {
+        const int omax = ps.omax;
         const Plan p = make_plan<T>(s, n);
         if (p.lds_coefs && omax >= 2 && omax <= (s->nInd == 2 ? 8 : 6)) {
-            auto go = [&](auto ni, auto om) {
+            auto mixed = [&](auto ni, auto om) {
                 return launch(s, "jac_mixed", jac_mixed<T, decltype(ni)::value, decltype(om)::value>, dim3(p.grid),
                               dim3(p.block), p.lds_bytes, st, desc_of<T>(s),
                               static_cast<const T *>(s->tab), static_cast<const T *>(s->coef), prm, n, out, s->bad);
             };
-            const std::integral_constant<int, 2> two;
-            const std::integral_constant<int, 3> three;
-            if (s->nInd == 2) return with_int<2, 3, 4, 5, 6, 7, 8>(omax, [&](auto om) { return go(two, om); });
-            return with_int<2, 3, 4, 5, 6>(omax, [&](auto om) { return go(three, om); });
+            if (s->nInd == 2) return with_range<2, 8>(omax, [&](auto om) { return mixed(int_c<2>{}, om); });
+            return with_range<2, 6>(omax, [&](auto om) { return mixed(int_c<3>{}, om); });
         }
     }
     // large batches on L2-resident tables of three variables: the fused jacobian of the cell-order pipeline
-    if (s->nInd == 3 && has_fixed_path(s) && s->coef_aos && s->variant != 1) {
+    if (s->nInd == 3 && ps.fixed && s->coef_aos && s->variant != 1) {
         const bsk_status r = cellsort_jacobian_any<T>(s, prm, n, out, st);
         if (r != BSK_ERR_UNSUPPORTED) return r;
     }
@@ -1021,7 +1025,7 @@ static bsk_status dispatch_jac(bsk_spline s, const Params<T> &prm, long long n, 
         Wrt w;
         for (int iv = 0; iv < MAXI; ++iv) w.w[iv] = (iv == j);
         s->bin_reuse = j > 0;           // cell-order pipeline: the batch is counted, scanned and scattered once
-        bsk_status r = dispatch_eval<T>(s, prm, n, out + (long long)j * n, (long long)s->nInd * n, w, st);
+        bsk_status r = dispatch_eval<T>(s, ps, prm, n, out + (long long)j * n, (long long)s->nInd * n, w, st);
         s->bin_reuse = false;
         if (r != BSK_OK) return r;
     }
@@ -1452,8 +1456,9 @@ static bsk_status run_points(bsk_spline s, bool jac, const int *wrt, const void 
     const int outs = jac ? s->nDep * s->nInd : s->nDep;   // output rows per point
     if (first_bad) *first_bad = -1;
     if (n == 0) return BSK_OK;
+    const PointShape ps = point_shape<T>(s);
     auto points_chunk = [&](const Params<T> &prm, long long m, T *dout, hipStream_t ks) {
-        return jac ? dispatch_jac<T>(s, prm, m, dout, ks) : dispatch_eval<T>(s, prm, m, dout, m, w, ks);
+        return jac ? dispatch_jac<T>(s, ps, prm, m, dout, ks) : dispatch_eval<T>(s, ps, prm, m, dout, m, w, ks);
     };
     if (mem == BSK_DEVICE) return points_chunk(device_params<T>(s, uvw), n, static_cast<T *>(out), st);
     return run_host<T>(s, uvw, n, outs, out, st, first_bad, 0, points_chunk);
@@ -1478,8 +1483,7 @@ extern "C" bsk_status bsk_evaluate(bsk_spline s, const int *wrt, const void *con
     if (r != BSK_OK) return r;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32 ? run_points<float>(s, false, wrt, uvw, n, mem, out, st, first_bad)
-                               : run_points<double>(s, false, wrt, uvw, n, mem, out, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) { return run_points<decltype(z)>(s, false, wrt, uvw, n, mem, out, st, first_bad); });
 }
 
 extern "C" bsk_status bsk_jacobian(bsk_spline s, const void *const *uvw, int64_t n, bsk_mem mem, void *out,
@@ -1489,8 +1493,7 @@ extern "C" bsk_status bsk_jacobian(bsk_spline s, const void *const *uvw, int64_t
     if (r != BSK_OK) return r;
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32 ? run_points<float>(s, true, nullptr, uvw, n, mem, out, st, first_bad)
-                               : run_points<double>(s, true, nullptr, uvw, n, mem, out, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) { return run_points<decltype(z)>(s, true, nullptr, uvw, n, mem, out, st, first_bad); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1504,13 +1507,14 @@ static bsk_status run_normal(bsk_spline s, const void *const *uvw, long long n, 
     if (first_bad) *first_bad = -1;
     if (n == 0) return BSK_OK;
     // surface in 3-D on the LDS image: the normal is fused into the jacobian kernel, tangents never leave the registers
-    const bool fused = s->nDep == 3 && rowrot_applies<T>(s);
+    const PointShape ps = point_shape<T>(s);
+    const bool fused = s->nDep == 3 && ps.rowrot;
     const size_t jac_b = fused ? 0 : sizeof(T) * (size_t)s->nDep * s->nInd;     // jacobian workspace (aux_ws) per point
     // one chunk of m points on stream ks
     auto normal_chunk = [&](const Params<T> &prm, long long m, T *dout, hipStream_t ks) -> bsk_status {
-        if (fused) return launch_jac_rowrot<T, true>(s, prm, m, dout, normalize, negate, ks);
+        if (fused) return launch_jac_rowrot<T, true>(s, ps, prm, m, dout, normalize, negate, ks);
         T *dj = static_cast<T *>(s->aux_ws.p);
-        const bsk_status r = dispatch_jac<T>(s, prm, m, dj, ks);
+        const bsk_status r = dispatch_jac<T>(s, ps, prm, m, dj, ks);
         if (r != BSK_OK) return r;
         return launch(s, nullptr, normal_epilogue<T>, dim3(persistent_grid(s, (m + 255) / 256, 8)), dim3(256), 0, ks, dj,
                       s->nInd, s->nDep, m, normalize, negate, dout);
@@ -1530,8 +1534,7 @@ extern "C" bsk_status bsk_normal(bsk_spline s, const void *const *uvw, int64_t n
     if (std::max(s->nInd, s->nDep) > 4) return fail(BSK_ERR_UNSUPPORTED, "normal supports max(nInd, nDep) <= 4");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32 ? run_normal<float>(s, uvw, n, mem, normalize, negate, out, st, first_bad)
-                               : run_normal<double>(s, uvw, n, mem, normalize, negate, out, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) { return run_normal<decltype(z)>(s, uvw, n, mem, normalize, negate, out, st, first_bad); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1543,8 +1546,9 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
 {
     if (first_bad) *first_bad = -1;
     if (n == 0) return BSK_OK;
+    const PointShape ps = point_shape<T>(s);
     const bool surface = s->nInd == 2;
-    const bool fused = surface && s->nDep == 3 && rowrot_applies<T>(s);   // curv_rowrot: no intermediates at all
+    const bool fused = surface && s->nDep == 3 && ps.rowrot;   // curv_rowrot: no intermediates at all
     const int nbuf = fused ? 0 : (surface ? 6 : 2);      // derivative buffers (+ normal) of nDep rows each
     const long long chunk = std::min<long long>(n, mem == BSK_HOST ? host_chunk_points() : (1ll << 22));
     // derivative workspace: persistent on the handle (no allocation, free or synchronisation per call)
@@ -1558,7 +1562,7 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
             for (int iv = 0; iv < MAXI; ++iv) wr.w[iv] = 0;
             wr.w[0] = w0;
             wr.w[1] = w1;
-            return dispatch_eval<T>(s, prm, m, dst, m, wr, ks);
+            return dispatch_eval<T>(s, ps, prm, m, dst, m, wr, ks);
         };
         const dim3 block(256), grid(persistent_grid(s, (m + 255) / 256, 8));
         bsk_status r;
@@ -1568,7 +1572,7 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
             return launch(s, nullptr, curvature_curve<T>, grid, block, 0, ks, w, w + one, s->nDep, m, o);
         }
         if (fused) {
-            const size_t lds_rr = rowrot_lds_bytes<T>(s);
+            const size_t lds_rr = ps.lds_rowrot;
             return with_int<4, 2>(s->order[0], [&](auto ord) {
                 return for_rr_chunks<T>(s, prm, m, [&](const Params<T> &cp, long long mm, long long c0) {
                     return launch(s, "curv_rowrot", curv_rowrot<T, decltype(ord)::value>, rr_grid(s, mm, lds_rr), dim3(TILE),
@@ -1583,12 +1587,12 @@ static bsk_status run_curvature(bsk_spline s, const void *const *uvw, long long 
         if ((r = deriv(1, 1, w + 3 * one)) != BSK_OK) return r;
         if ((r = deriv(0, 2, w + 4 * one)) != BSK_OK) return r;
         // unit normal (fused into the jacobian kernel when the image fits LDS)
-        if (rowrot_applies<T>(s)) {
-            if ((r = launch_jac_rowrot<T, true>(s, prm, m, w + 5 * one, 1, 0, ks)) != BSK_OK) return r;
+        if (ps.rowrot) {
+            if ((r = launch_jac_rowrot<T, true>(s, ps, prm, m, w + 5 * one, 1, 0, ks)) != BSK_OK) return r;
         } else {
             if ((r = ws_reserve(s->aux_ws, sizeof(T) * (size_t)m * s->nDep * s->nInd, ks)) != BSK_OK) return r;
             T *djac = static_cast<T *>(s->aux_ws.p);
-            if ((r = dispatch_jac<T>(s, prm, m, djac, ks)) != BSK_OK) return r;
+            if ((r = dispatch_jac<T>(s, ps, prm, m, djac, ks)) != BSK_OK) return r;
             if ((r = launch(s, nullptr, normal_epilogue<T>, grid, block, 0, ks, djac, 2, 3, m, 1, 0,
                             w + 5 * one)) != BSK_OK) return r;
         }
@@ -1618,8 +1622,7 @@ extern "C" bsk_status bsk_curvature(bsk_spline s, const void *const *uvw, int64_
         return fail(BSK_ERR_UNSUPPORTED, "curvature needs a curve with nDep >= 2 or a surface with nDep == 3");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32 ? run_curvature<float>(s, uvw, n, mem, out, st, first_bad)
-                               : run_curvature<double>(s, uvw, n, mem, out, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) { return run_curvature<decltype(z)>(s, uvw, n, mem, out, st, first_bad); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1753,8 +1756,7 @@ extern "C" bsk_status bsk_evaluate_grid(bsk_spline s, const int *wrt, const void
         if (!grid[iv] && ngrid[iv] > 0) return fail(BSK_ERR_INVALID, "NULL grid pointer");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32 ? run_grid<float>(s, wrt, grid, ngrid, mem, out, st, first_bad)
-                               : run_grid<double>(s, wrt, grid, ngrid, mem, out, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) { return run_grid<decltype(z)>(s, wrt, grid, ngrid, mem, out, st, first_bad); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1854,9 +1856,9 @@ extern "C" bsk_status bsk_tessellate(const bsk_spline *splines, int count, const
         if (!grid[iv] && ngrid[iv] > 0) return fail(BSK_ERR_INVALID, "NULL grid pointer");
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return s->dtype == BSK_F32
-               ? run_tessellate<float>(splines, count, grid, ngrid, mem, normalize, negate, positions, normals, st, first_bad)
-               : run_tessellate<double>(splines, count, grid, ngrid, mem, normalize, negate, positions, normals, st, first_bad);
+    return with_dtype(s->dtype, [&](auto z) {
+        return run_tessellate<decltype(z)>(splines, count, grid, ngrid, mem, normalize, negate, positions, normals, st, first_bad);
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1970,14 +1972,12 @@ extern "C" bsk_status bsk_bspline_values(bsk_dtype dtype, int device, const void
         for (int64_t i = 0; i < n; ++i)
             if (knot_in[i] < order || knot_in[i] > nknots - order)
                 return fail(BSK_ERR_INVALID, "explicit knot index outside [order, len(knots) - order]");
-    if (dtype == BSK_F32)
-        return run_basis<float>(device, static_cast<const float *>(knots), nknots, order, static_cast<const float *>(u),
-                                n, derivative_order, taylor_coefs, knot_in, ix_out, static_cast<float *>(basis_out));
-    if (dtype == BSK_F64)
-        return run_basis<double>(device, static_cast<const double *>(knots), nknots, order,
-                                 static_cast<const double *>(u), n, derivative_order, taylor_coefs, knot_in, ix_out,
-                                 static_cast<double *>(basis_out));
-    return fail(BSK_ERR_INVALID, "dtype must be BSK_F32 or BSK_F64");
+    if (dtype != BSK_F32 && dtype != BSK_F64) return fail(BSK_ERR_INVALID, "dtype must be BSK_F32 or BSK_F64");
+    return with_dtype(dtype, [&](auto z) {
+        using T = decltype(z);
+        return run_basis<T>(device, static_cast<const T *>(knots), nknots, order, static_cast<const T *>(u), n,
+                            derivative_order, taylor_coefs, knot_in, ix_out, static_cast<T *>(basis_out));
+    });
 }
 
 // ------------------------------------------------------------------------------------

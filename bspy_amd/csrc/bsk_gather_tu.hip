@@ -13,25 +13,13 @@ static bsk_status launch_eval_gather(bsk_spline s, const Params<T> &prm, long lo
     const Desc<T> &d = desc_of<T>(s);
     const size_t lds = sizeof(T) * (size_t)d.tab_len;
     if (lds > s->lds_max / 2) return BSK_ERR_UNSUPPORTED;        // axis tables too large for LDS: the caller falls back
+    if (s->nDep > 4) return fail(BSK_ERR_INVALID, "internal: eval_gather needs nDep <= 4");
     const int block = 256;
-    const long long blocks = (n + block - 1) / block;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(blocks, (long long)s->num_cu * 8));
-    const T *tab = static_cast<const T *>(s->tab);
-    const T *aos = static_cast<const T *>(s->coef_aos);
-#define GATHER_ND(ND)                                                                                             \
-    case ND:                                                                                                      \
-        HIPCHK(allow_lds(eval_gather<T, NIND, O, ND, MIXED>, lds));                                               \
-        s->last_kernel = "eval_gather";                                                                           \
-        hipLaunchKernelGGL((eval_gather<T, NIND, O, ND, MIXED>), dim3(grid), dim3(block), lds, st, d, tab, aos, prm, n,  \
-                           out, ostride, w, s->bad);                                                              \
-        break;
-    switch (s->nDep) {
-        GATHER_ND(1) GATHER_ND(2) GATHER_ND(3) GATHER_ND(4)
-        default: return fail(BSK_ERR_INVALID, "internal: eval_gather needs nDep <= 4");
-    }
-#undef GATHER_ND
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    return with_range<1, 4>(s->nDep, [&](auto nd) {
+        return launch(s, "eval_gather", eval_gather<T, NIND, O, decltype(nd)::value, MIXED>,
+                      dim3(persistent_grid(s, (n + block - 1) / block, 8)), dim3(block), lds, st, d,
+                      static_cast<const T *>(s->tab), static_cast<const T *>(s->coef_aos), prm, n, out, ostride, w, s->bad);
+    });
 }
 
 // Cell-order evaluation of large batches on L2-resident tables (bsk_binned.hpp).  Returns
@@ -42,8 +30,8 @@ constexpr long long BIN_MIN_POINTS = 1 << 18;
 #endif
 
 // Three variables of one order on an L2-resident table (BASELINE cfg5): the round-3 pipeline of bsk_binned.hpp,
-//   bin_totals -> bin_scatter_tag -> eval_cellsort -> bin_unpermute_stream
-// (4 launches; round 2: 6).  A record's tag holds its destination in chunk order and its span key in 32 bits, so a
+//   bin_totals -> bin_starts -> bin_scatter_tag -> eval_cellsort -> bin_unpermute_stream
+// (5 launches; round 2: 6).  A record's tag holds its destination in chunk order and its span key in 32 bits, so a
 // launch takes at most 2^26 - 1 points (span keys < 64) or 2^24 - 1 (< 256): larger batches run piece by piece.
 template <typename T, int O>
 static bsk_status launch_cellsort_pipeline(bsk_spline s, BinPlan bp, const Params<T> &prm, long long n, T *out, long long ostride,
@@ -99,8 +87,10 @@ static bsk_status launch_cellsort_pipeline(bsk_spline s, BinPlan bp, const Param
     for (int iv = 0; iv < 3; ++iv) deriv |= w.w[iv] != 0;
     constexpr bool MF = sizeof(T) == 4;
     const bool mfma = MF && s->variant != 12;
-    s->last_kernel = jac ? "cell-order pipeline (eval_cellsort, MFMA, fused jacobian)"
-                         : mfma ? "cell-order pipeline (eval_cellsort, MFMA)" : "cell-order pipeline (eval_cellsort, VALU)";
+    const char *family = jac ? "cell-order pipeline (eval_cellsort, MFMA, fused jacobian)"
+                             : mfma ? "cell-order pipeline (eval_cellsort, MFMA)" : "cell-order pipeline (eval_cellsort, VALU)";
+    const std::true_type yes;
+    const std::false_type no;
 
     for (long long off = 0; off < n; off += piece) {
         const long long np = std::min(piece, n - off);
@@ -109,60 +99,50 @@ static bsk_status launch_cellsort_pipeline(bsk_spline s, BinPlan bp, const Param
         bp.chunks = (int)((np + chunk_max - 1) / chunk_max);
         bp.chunk = ((np + bp.chunks - 1) / bp.chunks + 7) & ~7ll;        // multiples of 8 points: chunks keep the batch's 16-byte alignment
         bp.ranges = bp.rlen = 1;
-        const int pgrid = std::min(bp.chunks, s->num_cu);
+        const int pgrid = persistent_grid(s, bp.chunks, 1);
+        bsk_status r;
         stage_mark(s, st, "start", true);
         if (!reuse) {
-            HIPCHK(allow_lds(bin_totals<T>, lds_tot));
-            hipLaunchKernelGGL((bin_totals<T>), dim3(pgrid), dim3(1024), lds_tot, st, d, td, bp, tab, s->lut, pp, np, rows);
+            if ((r = launch(s, nullptr, bin_totals<T>, dim3(pgrid), dim3(1024), lds_tot, st, d, td, bp, tab, s->lut, pp, np,
+                            rows)) != BSK_OK) return r;
             stage_mark(s, st, "bin_totals");
-            hipLaunchKernelGGL(bin_starts, dim3((bp.cells + 63) / 64), dim3(1024), 0, st, bp.cells, pgrid, rows, tot, start, done);
+            if ((r = launch(s, nullptr, bin_starts, dim3((bp.cells + 63) / 64), dim3(1024), 0, st, bp.cells, pgrid, rows, tot,
+                            start, done)) != BSK_OK) return r;
             stage_mark(s, st, "bin_starts");
             const size_t lds_s = bins_b + (((size_t)bp.chunk * (sizeof(BinRec<T, 3>) + 2) + 15) & ~(size_t)15) + tabs_b;
-            HIPCHK(allow_lds(bin_scatter_tag<T>, lds_s));
-            hipLaunchKernelGGL((bin_scatter_tag<T>), dim3(pgrid), dim3(1024), lds_s, st, bp, pp, np, off, rows, start, rec, lpos, d, td, tab,
-                               s->lut, dest_bits, s->bad);
+            if ((r = launch(s, nullptr, bin_scatter_tag<T>, dim3(pgrid), dim3(1024), lds_s, st, bp, pp, np, off, rows, start, rec,
+                            lpos, d, td, tab, s->lut, dest_bits, s->bad)) != BSK_OK) return r;
             stage_mark(s, st, "bin_scatter_tag");
         }
         const size_t cs_lds_jac = cs_lds_mfma - 4 * sizeof(T) * (size_t)cs_per<T>() * (CS_BLOCK - cs_block<true>());   // shorter tiles
-        const int cgrid = (int)std::max<long long>(1, std::min<long long>((np + 4 * CS_BLOCK - 1) / (4 * CS_BLOCK), (long long)s->num_cu * (env_cs > 0 ? env_cs : jac ? 6 : 4)));   // (fused jacobian: three workgroups resident per CU)
-#define CS_ND(ND)                                                                                                        \
-    case ND: {                                                                                                           \
-        BinOut<T, ND> *tmp = reinterpret_cast<BinOut<T, ND> *>(ws + o_tmp);                                              \
-        if constexpr (MF) if (jac) {                                                                                     \
-            HIPCHK(allow_lds(eval_cellsort<T, O, ND, MF, true, MF>, cs_lds_jac));                                        \
-            hipLaunchKernelGGL((eval_cellsort<T, O, ND, MF, true, MF>), dim3(cgrid), dim3(cs_block<true>()), cs_lds_jac, st, d,  \
-                               bp, tab, aos, start, rec, np, tmp, w, dest_bits);                                         \
-        }                                                                                                                \
-        if (jac) {                                                                                                       \
-        } else if (mfma) {                                                                                               \
-            if (deriv) {                                                                                                 \
-                HIPCHK(allow_lds(eval_cellsort<T, O, ND, MF, true>, cs_lds_mfma));                                       \
-                hipLaunchKernelGGL((eval_cellsort<T, O, ND, MF, true>), dim3(cgrid), dim3(CS_BLOCK), cs_lds_mfma, st, d, \
-                                   bp, tab, aos, start, rec, np, tmp, w, dest_bits);                                     \
-            } else {                /* plain evaluation: the recursion without its derivative branches */              \
-                HIPCHK(allow_lds(eval_cellsort<T, O, ND, MF, !MF>, cs_lds_mfma));                                        \
-                hipLaunchKernelGGL((eval_cellsort<T, O, ND, MF, !MF>), dim3(cgrid), dim3(CS_BLOCK), cs_lds_mfma, st, d,  \
-                                   bp, tab, aos, start, rec, np, tmp, w, dest_bits);                                     \
-            }                                                                                                            \
-        } else {                                                                                                         \
-            HIPCHK(allow_lds(eval_cellsort<T, O, ND, false>, cs_lds_valu));                                              \
-            hipLaunchKernelGGL((eval_cellsort<T, O, ND, false>), dim3(cgrid), dim3(CS_BLOCK), cs_lds_valu, st, d, bp,    \
-                               tab, aos, start, rec, np, tmp, w, dest_bits);                                             \
-        }                                                                                                                \
-        stage_mark(s, st, "eval_cellsort");                                                                              \
-        const size_t lds_u = (size_t)bp.chunk * sizeof(BinOut<T, ND>);                                                   \
-        HIPCHK(allow_lds(bin_unpermute_stream<T, ND>, lds_u));                                                           \
-        for (int j = 0; j < (jac ? 3 : 1); ++j)                                                                          \
-            hipLaunchKernelGGL((bin_unpermute_stream<T, ND>), dim3(pgrid), dim3(1024), lds_u, st, bp, np, lpos, tmp + (size_t)j * np, \
-                               out + (long long)j * n + off, ostride);                                                   \
-        stage_mark(s, st, "bin_unpermute_stream");                                                                       \
-    } break;
-        switch (s->nDep) {
-            CS_ND(1) CS_ND(2) CS_ND(3) CS_ND(4)
-            default: return BSK_ERR_UNSUPPORTED;
-        }
-#undef CS_ND
-        HIPCHK(hipGetLastError());
+        // (fused jacobian: three workgroups resident per CU)
+        const int cgrid = persistent_grid(s, (np + 4 * CS_BLOCK - 1) / (4 * CS_BLOCK), env_cs > 0 ? env_cs : jac ? 6 : 4);
+        r = with_range<1, 4>(s->nDep, [&](auto ndc) -> bsk_status {       // nDep <= 4: launch_eval_binned has checked
+            constexpr int ND = decltype(ndc)::value;
+            BinOut<T, ND> *tmp = reinterpret_cast<BinOut<T, ND> *>(ws + o_tmp);
+            // eval_cellsort<T, O, ND, MFMA, DERIV, JAC>: the fused jacobian and the plain evaluation (DERIV false: the recursion
+            // without its derivative branches) exist in the MFMA form only
+            auto cellsort = [&](auto mf, auto dv, auto jc, size_t lds) {
+                constexpr bool JAC = decltype(jc)::value;
+                return launch(s, family, eval_cellsort<T, O, ND, decltype(mf)::value, decltype(dv)::value, JAC>, dim3(cgrid),
+                              dim3(cs_block<JAC>()), lds, st, d, bp, tab, aos, start, rec, np, tmp, w, dest_bits);
+            };
+            bsk_status rc = BSK_OK;
+            if (!mfma) rc = cellsort(no, yes, no, cs_lds_valu);
+            else if constexpr (MF) {
+                if (jac) rc = cellsort(yes, yes, yes, cs_lds_jac);
+                else rc = with_bool(deriv, [&](auto dv) { return cellsort(yes, dv, no, cs_lds_mfma); });
+            }
+            if (rc != BSK_OK) return rc;
+            stage_mark(s, st, "eval_cellsort");
+            const size_t lds_u = (size_t)bp.chunk * sizeof(BinOut<T, ND>);
+            for (int j = 0; j < (jac ? 3 : 1); ++j)
+                if ((rc = launch(s, nullptr, bin_unpermute_stream<T, ND>, dim3(pgrid), dim3(1024), lds_u, st, bp, np, lpos,
+                                 tmp + (size_t)j * np, out + (long long)j * n + off, ostride)) != BSK_OK) return rc;
+            stage_mark(s, st, "bin_unpermute_stream");
+            return BSK_OK;
+        });
+        if (r != BSK_OK) return r;
     }
     return BSK_OK;
 }
@@ -238,7 +218,7 @@ static bsk_status launch_eval_binned(bsk_spline s, const Params<T> &prm, long lo
         };
         const T *tab = static_cast<const T *>(s->tab);
         const T *aos = static_cast<const T *>(s->coef_aos);
-        const int egrid = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)s->num_cu * 8));
+        const int egrid = persistent_grid(s, (n + 255) / 256, 8);
         // rows of one cell staged in LDS (eval_binned_lds) when they fit beside the axis tables twice per CU
         const size_t rows_b = (size_t)((1 << bp.sh0) + s->order[0] - 1) * (NIND == 3 ? (size_t)((1 << bp.sh1) + s->order[1] - 1) : 1);
         const size_t bundle_b = ((rows_b * (size_t)s->ncoef[NIND - 1] * s->nDep * sizeof(T)) + 15) & ~(size_t)15;
@@ -262,54 +242,47 @@ static bsk_status launch_eval_binned(bsk_spline s, const Params<T> &prm, long lo
             }
         }
         if (jac) return BSK_ERR_UNSUPPORTED;                      // the fused jacobian exists on the eval_cellsort pipeline only
-#define BINNED_ND(ND)                                                                                                    \
-    case ND: {                                                                                                           \
-        layout(sizeof(BinOut<T, ND>));                                                                                   \
-        HIPCHK(s->bin_ws.reserve(total));                                                                                \
-        char *ws = static_cast<char *>(s->bin_ws.p);                                                                     \
-        unsigned short *cell = reinterpret_cast<unsigned short *>(ws + o_cell);                                          \
-        unsigned *slot = reinterpret_cast<unsigned *>(ws + o_slot);                                                      \
-        BinRec<T, NIND> *rec = reinterpret_cast<BinRec<T, NIND> *>(ws + o_rec);                                          \
-        BinOut<T, ND> *tmp = reinterpret_cast<BinOut<T, ND> *>(ws + o_tmp);                                              \
-        unsigned *M = reinterpret_cast<unsigned *>(ws + o_M);                                                            \
-        unsigned *Tr = reinterpret_cast<unsigned *>(ws + o_Tr);                                                          \
-        unsigned *start = reinterpret_cast<unsigned *>(ws + o_start);                                                    \
-        HIPCHK(allow_lds(bin_count<T, NIND, O>, lds_count));                                                             \
-        s->last_kernel = "cell-order pipeline (eval_binned_lds)";                                                        \
-        unsigned short *pbin = reinterpret_cast<unsigned short *>(ws + o_pbin);                                          \
-        unsigned *Lb = reinterpret_cast<unsigned *>(ws + o_Lb);                                                          \
-        if (!s->bin_reuse) {         /* later derivative passes of a jacobian find the batch sorted (dispatch_jac) */    \
-        hipLaunchKernelGGL((bin_count<T, NIND, O>), dim3(bp.chunks), dim3(bin_block), lds_count, st, d, td, bp, tab,     \
-                           s->lut, prm, n, cell, M, s->bad);                                                             \
-        hipLaunchKernelGGL(bin_scan_ranges, dim3((bp.cells + 255) / 256, bp.ranges), dim3(256), 0, st, bp, M, Tr);       \
-        hipLaunchKernelGGL(bin_scan_top, dim3(1), dim3(1024), 0, st, bp, Tr, start);                                     \
-        if (wc) {                                                                                                        \
-            size_t lds_s = ((12 * (size_t)bp.cells + 15) & ~(size_t)15) + (size_t)bp.chunk * (sizeof(BinRec<T, NIND>) + 2); \
-            HIPCHK(allow_lds(bin_scatter_wc<T, NIND>, lds_s));                                                           \
-            hipLaunchKernelGGL((bin_scatter_wc<T, NIND>), dim3(std::min(bp.chunks, s->num_cu)), dim3(1024), lds_s, st, bp, prm, n, cell, M,   \
-                               Tr, start, rec, reinterpret_cast<unsigned short *>(slot), pbin, Lb, d, td, tab, s->lut, s->bad);                        \
-        } else                                                                                                           \
-        hipLaunchKernelGGL((bin_scatter<T, NIND>), dim3(bp.chunks), dim3(bin_block), sizeof(unsigned) * (size_t)bp.cells, \
-                           st, bp, prm, n, cell, M, Tr, start, rec, slot, d, td, tab, s->lut, s->bad);             \
-        }                                                                                                                \
-        HIPCHK(allow_lds(eval_binned_lds<T, NIND, O, ND, MIXED>, tab_b + bundle_b));                                     \
-        hipLaunchKernelGGL((eval_binned_lds<T, NIND, O, ND, MIXED>), dim3(egrid), dim3(256), tab_b + bundle_b, st, d,    \
-                           bp, tab, aos, start, rec, n, tmp, w);                                                         \
-        if (wc) {                                                                                                        \
-            const size_t lds_u = ((8 * (size_t)bp.cells + 15) & ~(size_t)15) + (size_t)bp.chunk * sizeof(BinOut<T, ND>); \
-            HIPCHK(allow_lds(bin_unpermute_wc<T, ND>, lds_u));                                                           \
-            hipLaunchKernelGGL((bin_unpermute_wc<T, ND>), dim3(std::min(bp.chunks, s->num_cu)), dim3(1024), lds_u, st, bp, n,    \
-                               reinterpret_cast<const unsigned short *>(slot), M, Tr, start, Lb, pbin, tmp, out, ostride);                                                      \
-        } else                                                                                                           \
-        hipLaunchKernelGGL((bin_unpermute<T, ND>), dim3(ugrid), dim3(256), 0, st, n, slot, tmp, out, ostride);           \
-    } break;
-        switch (s->nDep) {
-            BINNED_ND(1) BINNED_ND(2) BINNED_ND(3) BINNED_ND(4)
-            default: return BSK_ERR_UNSUPPORTED;
-        }
-#undef BINNED_ND
-        HIPCHK(hipGetLastError());
-        return BSK_OK;
+        const int wgrid = persistent_grid(s, bp.chunks, 1);       // the write-combining kernels: persistent, a workgroup per CU
+        return with_range<1, 4>(s->nDep, [&](auto ndc) -> bsk_status {    // nDep <= 4: checked above
+            constexpr int ND = decltype(ndc)::value;
+            layout(sizeof(BinOut<T, ND>));
+            HIPCHK(s->bin_ws.reserve(total));
+            char *ws = static_cast<char *>(s->bin_ws.p);
+            unsigned short *cell = reinterpret_cast<unsigned short *>(ws + o_cell);
+            unsigned *slot = reinterpret_cast<unsigned *>(ws + o_slot);
+            BinRec<T, NIND> *rec = reinterpret_cast<BinRec<T, NIND> *>(ws + o_rec);
+            BinOut<T, ND> *tmp = reinterpret_cast<BinOut<T, ND> *>(ws + o_tmp);
+            unsigned *M = reinterpret_cast<unsigned *>(ws + o_M);
+            unsigned *Tr = reinterpret_cast<unsigned *>(ws + o_Tr);
+            unsigned *start = reinterpret_cast<unsigned *>(ws + o_start);
+            unsigned short *pbin = reinterpret_cast<unsigned short *>(ws + o_pbin);
+            unsigned *Lb = reinterpret_cast<unsigned *>(ws + o_Lb);
+            bsk_status r;
+            if (!s->bin_reuse) {         // later derivative passes of a jacobian find the batch sorted (dispatch_jac)
+                if ((r = launch(s, nullptr, bin_count<T, NIND, O>, dim3(bp.chunks), dim3(bin_block), lds_count, st, d, td, bp, tab,
+                                s->lut, prm, n, cell, M, s->bad)) != BSK_OK) return r;
+                if ((r = launch(s, nullptr, bin_scan_ranges, dim3((bp.cells + 255) / 256, bp.ranges), dim3(256), 0, st, bp, M,
+                                Tr)) != BSK_OK) return r;
+                if ((r = launch(s, nullptr, bin_scan_top, dim3(1), dim3(1024), 0, st, bp, Tr, start)) != BSK_OK) return r;
+                if (wc) {
+                    const size_t lds_s = ((12 * (size_t)bp.cells + 15) & ~(size_t)15) + (size_t)bp.chunk * (sizeof(BinRec<T, NIND>) + 2);
+                    r = launch(s, nullptr, bin_scatter_wc<T, NIND>, dim3(wgrid), dim3(1024), lds_s, st, bp, prm, n, cell, M, Tr,
+                               start, rec, reinterpret_cast<unsigned short *>(slot), pbin, Lb, d, td, tab, s->lut, s->bad);
+                } else {
+                    r = launch(s, nullptr, bin_scatter<T, NIND>, dim3(bp.chunks), dim3(bin_block), sizeof(unsigned) * (size_t)bp.cells,
+                               st, bp, prm, n, cell, M, Tr, start, rec, slot, d, td, tab, s->lut, s->bad);
+                }
+                if (r != BSK_OK) return r;
+            }
+            if ((r = launch(s, "cell-order pipeline (eval_binned_lds)", eval_binned_lds<T, NIND, O, ND, MIXED>, dim3(egrid), dim3(256),
+                            tab_b + bundle_b, st, d, bp, tab, aos, start, rec, n, tmp, w)) != BSK_OK) return r;
+            if (wc) {
+                const size_t lds_u = ((8 * (size_t)bp.cells + 15) & ~(size_t)15) + (size_t)bp.chunk * sizeof(BinOut<T, ND>);
+                return launch(s, nullptr, bin_unpermute_wc<T, ND>, dim3(wgrid), dim3(1024), lds_u, st, bp, n,
+                              reinterpret_cast<const unsigned short *>(slot), M, Tr, start, Lb, pbin, tmp, out, ostride);
+            }
+            return launch(s, nullptr, bin_unpermute<T, ND>, dim3(ugrid), dim3(256), 0, st, n, slot, tmp, out, ostride);
+        });
     }
 }
 
@@ -329,24 +302,24 @@ static bsk_status gather_or_binned(bsk_spline s, const Params<T> &prm, long long
 }
 
 
+// One common order 1..6 of one to three variables, or (`mixed`) surfaces and volumes whose largest order is 2..6
 template <typename T>
 bsk_status gather_or_binned_any(bsk_spline s, bool mixed, const Params<T> &prm, long long n, T *out, long long ostride,
                                 const Wrt &w, hipStream_t st)
 {
-    int omax = 0;
-    for (int iv = 0; iv < s->nInd; ++iv) omax = std::max(omax, s->order[iv]);
+    const int omax = max_order(s);
     if (s->nInd < 1 || s->nInd > 3 || omax < 1 || omax > 6 || !s->coef_aos) return BSK_ERR_UNSUPPORTED;
-#define GB_CASE(NIND, O, MIXED) case O: return gather_or_binned<T, NIND, O, MIXED>(s, prm, n, out, ostride, w, st);
-    if (!mixed) {
-        if (s->nInd == 1) switch (omax) { GB_CASE(1, 1, false) GB_CASE(1, 2, false) GB_CASE(1, 3, false) GB_CASE(1, 4, false) GB_CASE(1, 5, false) GB_CASE(1, 6, false) default: break; }
-        else if (s->nInd == 2) switch (omax) { GB_CASE(2, 1, false) GB_CASE(2, 2, false) GB_CASE(2, 3, false) GB_CASE(2, 4, false) GB_CASE(2, 5, false) GB_CASE(2, 6, false) default: break; }
-        else switch (omax) { GB_CASE(3, 1, false) GB_CASE(3, 2, false) GB_CASE(3, 3, false) GB_CASE(3, 4, false) GB_CASE(3, 5, false) GB_CASE(3, 6, false) default: break; }
-    } else {
-        if (s->nInd == 2) switch (omax) { GB_CASE(2, 2, true) GB_CASE(2, 3, true) GB_CASE(2, 4, true) GB_CASE(2, 5, true) GB_CASE(2, 6, true) default: break; }
-        else if (s->nInd == 3) switch (omax) { GB_CASE(3, 2, true) GB_CASE(3, 3, true) GB_CASE(3, 4, true) GB_CASE(3, 5, true) GB_CASE(3, 6, true) default: break; }
-    }
-#undef GB_CASE
-    return BSK_ERR_UNSUPPORTED;
+    auto go = [&](auto ni, auto o, auto mx) {
+        return gather_or_binned<T, decltype(ni)::value, decltype(o)::value, decltype(mx)::value>(s, prm, n, out, ostride, w, st);
+    };
+    if (!mixed)
+        return with_range<1, 3>(s->nInd, [&](auto ni) {
+            return with_range<1, 6>(omax, [&](auto o) { return go(ni, o, std::false_type{}); });
+        });
+    if (s->nInd < 2 || omax < 2) return BSK_ERR_UNSUPPORTED;
+    return with_range<2, 3>(s->nInd, [&](auto ni) {
+        return with_range<2, 6>(omax, [&](auto o) { return go(ni, o, std::true_type{}); });
+    });
 }
 
 // Fused jacobian of a large batch on an L2-resident table (three variables of one order, fp32: the eval_cellsort
@@ -358,12 +331,9 @@ bsk_status cellsort_jacobian_any(bsk_spline s, const Params<T> &prm, long long n
     if (s->nInd != 3 || !s->same_order || !s->coef_aos || s->order[0] < 1 || s->order[0] > 6) return BSK_ERR_UNSUPPORTED;
     Wrt w;
     for (int iv = 0; iv < MAXI; ++iv) w.w[iv] = 0;
-    switch (s->order[0]) {
-#define CJ_CASE(O) case O: return launch_eval_binned<T, 3, O, false>(s, prm, n, out, 3 * n, w, st, true);
-        CJ_CASE(1) CJ_CASE(2) CJ_CASE(3) CJ_CASE(4) CJ_CASE(5) CJ_CASE(6)
-#undef CJ_CASE
-        default: return BSK_ERR_UNSUPPORTED;
-    }
+    return with_range<1, 6>(s->order[0], [&](auto o) {
+        return launch_eval_binned<T, 3, decltype(o)::value, false>(s, prm, n, out, 3 * n, w, st, true);
+    });
 }
 template bsk_status cellsort_jacobian_any<float>(bsk_spline, const Params<float> &, long long, float *, hipStream_t);
 template bsk_status cellsort_jacobian_any<double>(bsk_spline, const Params<double> &, long long, double *, hipStream_t);

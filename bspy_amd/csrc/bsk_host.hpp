@@ -1,7 +1,11 @@
 // Host-side declarations shared by the translation units of libbspy_amd.so: error reporting, the
-// spline handle, and small launch helpers.  (The kernels of the large-table paths - control-point
-// major gather and the cell-order pipeline - are two thirds of the device code; they are compiled
-// in their own translation unit, bsk_gather_tu.hip, in parallel with bsk_api.hip.)
+// spline handle, the launch helpers (launch, launch_lanes, persistent_grid, lds_per_cu) and the
+// run-time value -> template constant helpers (with_bool, with_int, with_range, with_dtype).
+// The point paths are three units that compile in parallel: bsk_api.hip (C ABI, the LDS-resident
+// families and the ladders that choose a family), bsk_gather_tu.hip (large tables: control-point-major
+// gather and the cell-order pipeline) and bsk_slab_tu.hip (eval_slab2); the entry points of the last
+// two are declared at the end of this file.  The other units (the handle-free families bsk_*_tu.hip,
+// bsk_multi.hip) take the error reporting and the helpers from here.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -163,6 +167,12 @@ inline hipError_t allow_lds(K kernel, size_t bytes)
     return err;
 }
 
+// The largest order of the spline's variables: the kernels of mixed orders are instantiated for it.
+inline int max_order(bsk_spline s)
+{
+    return *std::max_element(s->order, s->order + s->nInd);
+}
+
 // Workgroups of a persistent launch: one per unit of work, at most per_cu on every CU.
 inline int persistent_grid(bsk_spline s, long long units, long long per_cu)
 {
@@ -205,6 +215,9 @@ inline bsk_status launch_lanes(K kernel, long long lanes, hipStream_t st, const 
 // Run-time value -> template constant: f receives a std::integral_constant.  with_int<A, B, ..., Z>(v, f) hands over
 // v's own class, and Z for every value that is not listed (callers check the range, or Z is the "any" class);
 // with_range<LO, HI> is with_int<LO, LO + 1, ..., HI>.  with_dtype hands over a zero of the element type.
+// int_c<N>{} is the constant a caller passes on by hand.
+template <int N>
+using int_c = std::integral_constant<int, N>;
 template <typename F>
 inline bsk_status with_bool(bool b, F &&f)
 {

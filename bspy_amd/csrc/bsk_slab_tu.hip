@@ -1,5 +1,6 @@
-// eval_slab2 (bsk_slab.hpp) in its own translation unit: 80 instantiations (fp32 / fp64 x orders 2 - 6 x nDep 1 - 4 x
-// one common order / mixed orders) compile beside bsk_gather_tu.hip instead of behind it.  Entry: slab2_any<T>.
+// eval_slab2 (bsk_slab.hpp) in its own translation unit: 176 instantiations (fp32 / fp64 x one common order 1 - 6 or mixed
+// orders up to 2 - 6 x nDep 1 - 4 x with / without derivative branches) compile beside bsk_gather_tu.hip instead of
+// behind it.  Entry: slab2_any<T>.
 #include "bsk_host.hpp"
 #include "bsk_tile.hpp"
 #include "bsk_gather.hpp"
@@ -67,47 +68,35 @@ static bsk_status launch_eval_slab2(bsk_spline s, const Params<T> &prm, long lon
     if (sp.npass == 1 && MIXED)
         sp.chunk = (int)std::max<long long>(1024, std::min<long long>(SLAB_CHUNK, ((n + 2 * s->num_cu - 1) / (2 * s->num_cu) + 1023) / 1024 * 1024));
     const long long nchunks = (n + sp.chunk - 1) / sp.chunk;
-    int grid = (int)std::min<long long>(nchunks, (long long)s->num_cu);
+    int grid = persistent_grid(s, nchunks, 1);
     if (const char *g = getenv("BSK_SLAB_GRID")) grid = std::max(1, std::min(grid, atoi(g)));          // test knob: few workgroups = several rounds each
     static const int slab_dbg = getenv("BSK_SLAB_DBG") ? atoi(getenv("BSK_SLAB_DBG")) : 0;     // timing-only switches (tools/)
     const T *tab = static_cast<const T *>(s->tab);
     const T *aos = static_cast<const T *>(s->coef_aos);
     bool deriv = false;
     for (int iv = 0; iv < 2; ++iv) deriv |= w.w[iv] != 0;
-#define SLAB_ND(ND)                                                                                               \
-    case ND:                                                                                                      \
-        if (deriv) {                                                                                              \
-            HIPCHK(allow_lds(eval_slab2<T, O, ND, MIXED, true>, sp.total));                                       \
-            hipLaunchKernelGGL((eval_slab2<T, O, ND, MIXED, true>), dim3(grid), dim3(SLAB_BLOCK), sp.total, st, d, td, sp, tab, s->lut, aos, \
-                               prm, n, 0ll, spts, sidx, out, ostride, w, s->bad, slab_dbg);                       \
-        } else {          /* plain evaluation: the recursions without their derivative branches */              \
-            HIPCHK(allow_lds(eval_slab2<T, O, ND, MIXED, false>, sp.total));                                      \
-            hipLaunchKernelGGL((eval_slab2<T, O, ND, MIXED, false>), dim3(grid), dim3(SLAB_BLOCK), sp.total, st, d, td, sp, tab, s->lut, aos, \
-                               prm, n, 0ll, spts, sidx, out, ostride, w, s->bad, slab_dbg);                       \
-        }                                                                                                         \
-        break;
-    switch (s->nDep) {
-        SLAB_ND(1) SLAB_ND(2) SLAB_ND(3) SLAB_ND(4)
-        default: return BSK_ERR_UNSUPPORTED;
-    }
-#undef SLAB_ND
-    s->last_kernel = "eval_slab2";
-    HIPCHK(hipGetLastError());
-    return BSK_OK;
+    // DERIV false = plain evaluation: the recursions without their derivative branches (nDep <= 4: checked above)
+    return with_range<1, 4>(s->nDep, [&](auto nd) {
+        return with_bool(deriv, [&](auto dv) {
+            return launch(s, "eval_slab2", eval_slab2<T, O, decltype(nd)::value, MIXED, decltype(dv)::value>, dim3(grid),
+                          dim3(SLAB_BLOCK), sp.total, st, d, td, sp, tab, s->lut, aos, prm, n, 0ll, spts, sidx, out, ostride, w,
+                          s->bad, slab_dbg);
+        });
+    });
 }
 
+// One common order 1..6, or mixed orders whose largest is 2..6 (`mixed` is the caller's: see gather_or_binned_any)
 template <typename T>
 bsk_status slab2_any(bsk_spline s, bool mixed, const Params<T> &prm, long long n, T *out, long long ostride, const Wrt &w,
                      hipStream_t st)
 {
-    int omax = 0;
-    for (int iv = 0; iv < s->nInd; ++iv) omax = std::max(omax, s->order[iv]);
-    if (s->nInd != 2 || omax < 1 || omax > 6) return BSK_ERR_UNSUPPORTED;
-#define SLAB_CASE(O, M) case O: return launch_eval_slab2<T, O, M>(s, prm, n, out, ostride, w, st);
-    if (!mixed) switch (omax) { SLAB_CASE(1, false) SLAB_CASE(2, false) SLAB_CASE(3, false) SLAB_CASE(4, false) SLAB_CASE(5, false) SLAB_CASE(6, false) default: break; }
-    else switch (omax) { SLAB_CASE(2, true) SLAB_CASE(3, true) SLAB_CASE(4, true) SLAB_CASE(5, true) SLAB_CASE(6, true) default: break; }
-#undef SLAB_CASE
-    return BSK_ERR_UNSUPPORTED;
+    const int omax = max_order(s);
+    if (s->nInd != 2 || omax < (mixed ? 2 : 1) || omax > 6) return BSK_ERR_UNSUPPORTED;
+    auto go = [&](auto o, auto mx) {
+        return launch_eval_slab2<T, decltype(o)::value, decltype(mx)::value>(s, prm, n, out, ostride, w, st);
+    };
+    if (mixed) return with_range<2, 6>(omax, [&](auto o) { return go(o, std::true_type{}); });
+    return with_range<1, 6>(omax, [&](auto o) { return go(o, std::false_type{}); });
 }
 
 template bsk_status slab2_any<float>(bsk_spline, bool, const Params<float> &, long long, float *, long long, const Wrt &, hipStream_t);

@@ -73,13 +73,28 @@ hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipLaunchKernel(const void *, dim3, dim3, void **, size_t, hipStream_t) { ++g_launches; return hipSuccess; }
+// the calling thread's most recent launch: grid.x, grid.y, block.x, dynamic LDS bytes (driver.cpp's launch table)
+static thread_local unsigned long long t_last_launch[4] = {0, 0, 0, 0};
+void hipstub_last_launch(unsigned long long out[4]) { memcpy(out, t_last_launch, sizeof(t_last_launch)); }
+hipError_t hipLaunchKernel(const void *, dim3 grid, dim3 block, void **, size_t lds, hipStream_t)
+{
+    ++g_launches;
+    t_last_launch[0] = grid.x;
+    t_last_launch[1] = grid.y;
+    t_last_launch[2] = block.x;
+    t_last_launch[3] = lds;
+    return hipSuccess;
+}
 
 // fat-binary registration emitted by hipcc for every translation unit with kernels
 void **__hipRegisterFatBinary(const void *) { static void *h; return &h; }
 void __hipUnregisterFatBinary(void **) {}
 void __hipRegisterFunction(void **, const void *, char *, const char *, unsigned, void *, void *, void *, void *, int *) {}
 void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, int) {}
-hipError_t __hipPushCallConfiguration(dim3, dim3, size_t, hipStream_t) { return hipSuccess; }
-hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *s, hipStream_t *st) { *g = dim3(1); *b = dim3(1); *s = 0; *st = nullptr; return hipSuccess; }
+// kernel<<<grid, block, lds, stream>>>: the configuration travels from the call site to the kernel's host stub
+static thread_local dim3 t_cfg_grid(1), t_cfg_block(1);
+static thread_local size_t t_cfg_lds = 0;
+static thread_local hipStream_t t_cfg_stream = nullptr;
+hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t s, hipStream_t st) { t_cfg_grid = g; t_cfg_block = b; t_cfg_lds = s; t_cfg_stream = st; return hipSuccess; }
+hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *s, hipStream_t *st) { *g = t_cfg_grid; *b = t_cfg_block; *s = t_cfg_lds; *st = t_cfg_stream; return hipSuccess; }
 }

@@ -578,22 +578,30 @@ def test_tessellation_oracle_matches_reference_goldens():
             assert np.abs(nrm[:, ok] - ref[:, ok]).max() <= (2e-3 if "f32" in name else 1e-9), (name, p)
 
 
-def test_host_code_under_address_and_thread_sanitizer(tmp_path):
-    """The host half of bsk_api.hip (handle life cycle, workspaces, the small-call path's pinned buffer, the
-    pipelined BSK_HOST path: copy-thread pool + double-buffered pinned staging + three streams) compiled
-    host-only with AddressSanitizer / ThreadSanitizer against a host-memory stand-in for the HIP runtime
-    (tests/hipstub/) and driven from two threads on two handles.  GPU sanitizer runs are not available on the
-    GPU pool; this is the CPU-side hardening SURVEY.md section 5 asks for."""
+@pytest.fixture(scope="module")
+def hipstub_drivers(tmp_path_factory):
+    """tests/hipstub/driver.cpp on the stub runtime, built once under AddressSanitizer and under ThreadSanitizer:
+    the folder that holds asan/driver and tsan/driver."""
     import shutil
-    import subprocess
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
+    tmp_path = tmp_path_factory.mktemp("hipstub")
     stub = os.path.join(ROOT, "tests", "hipstub")
     procs = {k: subprocess.Popen(["bash", os.path.join(stub, "build.sh"), k, str(tmp_path / k)], stdout=subprocess.PIPE,
                                  stderr=subprocess.STDOUT, text=True) for k in ("asan", "tsan")}
     for k, p in procs.items():
         out, _ = p.communicate(timeout=900)
         assert p.returncode == 0, f"{k} build failed:\n{out[-3000:]}"
+    return tmp_path
+
+
+def test_host_code_under_address_and_thread_sanitizer(hipstub_drivers):
+    """The host half of bsk_api.hip (handle life cycle, workspaces, the small-call path's pinned buffer, the
+    pipelined BSK_HOST path: copy-thread pool + double-buffered pinned staging + three streams) compiled
+    host-only with AddressSanitizer / ThreadSanitizer against a host-memory stand-in for the HIP runtime
+    (tests/hipstub/) and driven from two threads on two handles.  GPU sanitizer runs are not available on the
+    GPU pool; this is the CPU-side hardening SURVEY.md section 5 asks for."""
+    tmp_path = hipstub_drivers
     for k, big in (("asan", "4500000"), ("tsan", "2200000")):
         # three fake devices: the multi-device entry points run the REAL single-device host code on each of them
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", TSAN_OPTIONS="halt_on_error=1",
@@ -601,6 +609,25 @@ def test_host_code_under_address_and_thread_sanitizer(tmp_path):
         r = subprocess.run([str(tmp_path / k / "driver"), big], capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0 and "hipstub driver ok" in r.stdout, f"{k}:\n{r.stdout[-2000:]}\n{r.stderr[-6000:]}"
         assert "Sanitizer" not in r.stderr, r.stderr[-6000:]
+
+
+def test_point_ladders_launch_what_they_launched(hipstub_drivers):
+    """`driver launches` walks the point-path ladders of bsk_api.hip (evaluate, a derivative, jacobian, normal, curvature)
+    over a table of shapes with at least one per rung, on the stub runtime's 256 CUs and 160 KiB of LDS, and prints the
+    family, the number of launches and the last launch's grid, block and dynamic LDS of every call.
+    tests/golden/point_launches.txt is that output from the host code as it was before the ladders were rewritten on one
+    shape classifier: line for line the same, or a shape has moved to another rung or another launch geometry."""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
+               LD_LIBRARY_PATH=str(hipstub_drivers / "asan") + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
+    r = subprocess.run([str(hipstub_drivers / "asan" / "driver"), "launches"], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr, f"{r.stdout[-2000:]}\n{r.stderr[-6000:]}"
+    with open(os.path.join(ROOT, "tests", "golden", "point_launches.txt")) as f:
+        golden = f.read().splitlines()
+    got = r.stdout.splitlines()
+    assert len(golden) > 150
+    for g, o in zip(golden, got):
+        assert o == g
+    assert len(got) == len(golden)
 
 
 def test_multi_device_entry_points_on_fake_devices(tmp_path):
