@@ -40,6 +40,8 @@ PRODUCT_SYMBOLS = (
     "bsk_contour_flag_host", "bsk_contour_flag", "bsk_contour_march_host", "bsk_contour_march", "bsk_contour_last_kernel",
     "bsk_rays_boxes_host", "bsk_rays_boxes", "bsk_rays_count_host", "bsk_rays_count", "bsk_rays_emit_host", "bsk_rays_emit",
     "bsk_rays_isolate_host", "bsk_rays_isolate", "bsk_rays_reduce_host", "bsk_rays_reduce", "bsk_rays_last_kernel",
+    "bsk_ssx_count_host", "bsk_ssx_count", "bsk_ssx_emit_host", "bsk_ssx_emit", "bsk_ssx_isolate_host", "bsk_ssx_isolate",
+    "bsk_ssx_merge_host", "bsk_ssx_merge", "bsk_ssx_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -227,6 +229,20 @@ def lib():
     L.bsk_rays_reduce.argtypes = reduce_r + [_vp]
     L.bsk_rays_last_kernel.argtypes = []
     L.bsk_rays_last_kernel.restype = ctypes.c_char_p
+    side = surface + surface + [ctypes.c_int, _i64]
+    search_s = side + [_i64, _i64, _i64, ctypes.c_int, _vp, _vp]
+    isolate_s = side + [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+    merge_s = [ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]
+    L.bsk_ssx_count_host.argtypes = search_s + [_vp]
+    L.bsk_ssx_count.argtypes = search_s + [_vp, _vp]
+    L.bsk_ssx_emit_host.argtypes = search_s + [_vp, _vp, _vp, _i64]
+    L.bsk_ssx_emit.argtypes = search_s + [_vp, _vp, _vp, _i64, _vp]
+    L.bsk_ssx_isolate_host.argtypes = isolate_s
+    L.bsk_ssx_isolate.argtypes = isolate_s + [_vp]
+    L.bsk_ssx_merge_host.argtypes = merge_s
+    L.bsk_ssx_merge.argtypes = merge_s + [_vp]
+    L.bsk_ssx_last_kernel.argtypes = []
+    L.bsk_ssx_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -236,7 +252,8 @@ def lib():
     for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_rays_last_kernel"):
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_rays_last_kernel",
+                        "bsk_ssx_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

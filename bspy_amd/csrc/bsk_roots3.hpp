@@ -80,9 +80,11 @@ constexpr int slots(int K0, int K1, int K2)
 }
 
 // One cell of one system in the extracted rows: component d, coefficient (i0, i1, i2) at p[d * sd + i0 * s0 + i1 * s1 + i2].
+// A cell is anything with at(d, i0, i1, i2): CellRef reads its coefficients, bsk_ssx.hpp's PairCell forms them.
 struct CellRef {
     const double *p;
     long long sd, s0, s1;
+    BSK_HD double at(int d, int i0, int i1, int i2) const { return p[d * sd + i0 * s0 + i1 * s1 + i2]; }
 };
 
 // ------------------------------------------------------------------------------------------ the two waves
@@ -95,13 +97,13 @@ struct HostWave {
     int bcast(int x) const { return x; }
     double get0(const V &x) const { return x.a[0]; }
 
-    template <int K0, int K1, int K2>
-    void load(const CellRef &ref, V *c) const
+    template <int K0, int K1, int K2, class Ref>
+    void load(const Ref &ref, V *c) const
     {
         for (int d = 0; d < 3; ++d)
             for (int l = 0; l < ROOTS3_WAVE; ++l) {
                 const int i0 = l / (K1 * K2), i1 = (l / K2) % K1, i2 = l % K2;
-                c[d].a[l] = l < K0 * K1 * K2 ? ref.p[d * ref.sd + i0 * ref.s0 + i1 * ref.s1 + i2] : 0.0;
+                c[d].a[l] = l < K0 * K1 * K2 ? ref.at(d, i0, i1, i2) : 0.0;
             }
     }
     template <int K, int STRIDE>
@@ -172,12 +174,12 @@ struct LaneWave {
     __device__ int bcast(int x) const { return __shfl(x, 0); }
     __device__ double get0(const V &x) const { return __shfl(x, 0); }
 
-    template <int K0, int K1, int K2>
-    __device__ void load(const CellRef &ref, V *c) const
+    template <int K0, int K1, int K2, class Ref>
+    __device__ void load(const Ref &ref, V *c) const
     {
         const int i0 = lane / (K1 * K2), i1 = (lane / K2) % K1, i2 = lane % K2;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) c[d] = lane < K0 * K1 * K2 ? ref.p[d * ref.sd + i0 * ref.s0 + i1 * ref.s1 + i2] : 0.0;
+        for (int d = 0; d < 3; ++d) c[d] = lane < K0 * K1 * K2 ? ref.at(d, i0, i1, i2) : 0.0;
     }
     template <int K, int STRIDE>
     __device__ void left_part(V *x, double s, double t) const
@@ -412,8 +414,8 @@ BSK_HD void leaf(const W &wave, const typename W::V *own, const double *lo, cons
 }
 
 // out: R x 3 slots (the zeros in front, NaN behind), near: R bytes.  The cell is a candidate (roots3_flag said 1).
-template <class W, int K0, int K1, int K2>
-BSK_HD void isolate_cell(const W &wave, const CellRef &ref, const double *t0, const double *t1, const double *S, double *out,
+template <class W, int K0, int K1, int K2, class Ref>
+BSK_HD void isolate_cell(const W &wave, const Ref &ref, const double *t0, const double *t1, const double *S, double *out,
                          uint8_t *near, int32_t *count_out, uint8_t *status_out, int32_t *nodes_out)
 {
     constexpr int R = slots(K0, K1, K2);
@@ -568,7 +570,7 @@ BSK_HD void isolate_wave(const W &wave, const Grid &g, long long slot, const Bre
     const double t0[3] = {br.b0[ijk[0]], br.b1[ijk[1]], br.b2[ijk[2]]};
     const double t1[3] = {br.b0[ijk[0] + 1], br.b1[ijk[1] + 1], br.b2[ijk[2] + 1]};
     const double S[3] = {scale[3 * b], scale[3 * b + 1], scale[3 * b + 2]};
-    isolate_cell<W, K0, K1, K2>(wave, ref, t0, t1, S, out, near + slot * R, count + slot, status + slot, nodes + slot);
+    isolate_cell<W, K0, K1, K2, CellRef>(wave, ref, t0, t1, S, out, near + slot * R, count + slot, status + slot, nodes + slot);
 }
 
 // roots: [ncand, R, 3]; cand: [ncand]; flags, table: [nsys, nc0, nc1, nc2]; which: [nnear] flat (candidate, slot); keep: [ncand, R]
@@ -623,7 +625,8 @@ __attribute__((noinline, aligned(64))) void isolate_host(const Grid &g, const Br
         isolate_wave<HostWave, K0, K1, K2>(wave, g, slot, br, scale, cand, roots, near, count, status, nodes);
 }
 
-#ifdef __HIPCC__
+// BSK_ROOTS3_FUNCTIONS_ONLY: a unit that takes the walk for cells of its own (bsk_ssx.hpp) leaves the kernels to bsk_roots3_tu.hip
+#if defined(__HIPCC__) && !defined(BSK_ROOTS3_FUNCTIONS_ONLY)
 template <int K0, int K1, int K2>
 __global__ __launch_bounds__(ROOTS3_BLOCK) void roots3_flag(Grid g, const uint8_t *__restrict__ mask, uint8_t *__restrict__ flags)
 {

@@ -490,6 +490,23 @@ class Spline:
         from . import rays as _rays
         return _rays.intersect_rays(self, origins, directions, tmin=tmin, tmax=tmax, **kwargs)
 
+    def intersect_surface(self, other, depth=None, tolerance=None, **kwargs):
+        """The curves along which this surface meets another one (the reference's ``intersect`` of two surfaces; both
+        nInd 2, nDep 3, orders 2 .. 4, anything else raises NotImplementedError): a list of ``(curve_on_self,
+        curve_on_other)``, one pair per connected piece.  Both curves (nInd 1, nDep 2, on [0, 1], order <= 4) are fitted to
+        the same chord-length parameters of one polyline, so ``self(*ca(t))`` is ``other(*cb(t))`` up to the resolution of
+        the lattice; a closed piece has equal end points.  Each surface carries 2^depth lattice lines per knot cell and
+        variable (depth 0 .. 6; default 2, or chosen from ``tolerance``, which is also the tolerance of the fit) and every
+        vertex is a hit of a lattice line of one surface on the other: a ``zeros3`` system that is formed in registers,
+        never stored, and walked by one wave.  The curve is decided on the two lattices: a piece inside one product leaf
+        is missed without a flag, tangential contact and coincident regions give a status bit at best, and nothing is
+        certified; what is computed is stated in bspy_amd/surfaces.py.  One RuntimeWarning when a status bit is set
+        (``bspy_amd.surfaces.trace_pair`` returns the raw polylines and the status).  Results are bitwise reproducible
+        and the same on both paths.  ``_path="device"`` / ``"host"`` pins the path of the trace; the fit
+        (``Spline.least_squares``) needs the device on either path, ``surfaces.trace_pair`` does not."""
+        from . import surfaces as _surfaces
+        return _surfaces.intersect_surface(self, other, depth=depth, tolerance=tolerance, **kwargs)
+
     def contours(self, tolerance=None, depth=None, **kwargs):
         """The level curves {f = 0} of a scalar spline in two variables (nInd == 2, nDep == 1; reference spline.py
         ``contours``, whose other shapes are not built): a list of curves (nInd 1, nDep 2, on [0, 1], order 4, f >= 0 on

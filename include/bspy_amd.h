@@ -542,6 +542,88 @@ bsk_status bsk_rays_reduce(int K0, int K1, const double *rows, int64_t R0, int64
 const char *bsk_rays_last_kernel(void);
 
 /*
+ * Surface-surface intersection (Spline.intersect_surface, bspy_amd.surfaces.trace_pair; the statement is in
+ * bspy_amd/surfaces.py and DESIGN.md section 23).  The family keeps no handle.  Both surfaces (nInd 2, nDep 3) are brought
+ * to Bezier form as for bsk_rays_*: X is (KX0, KX1, rowsX[3][RX0][RX1], ncX0, ncX1, firstX0, firstX1), Y likewise.  A call
+ * serves one family of lattice lines: the lines of X with variable `ax` (0 or 1) fixed, G = 2^depth per knot cell
+ * (1 <= G <= 64), against the cells of Y.  Line n, 0 <= n <= nc_ax G, is owned by cell c = min(n / G, nc_ax - 1) at the
+ * local value (n - c G) / G; its segment on running cell e has the index n * ncrun + e, ncrun the cells of the other
+ * variable, and is a Bezier curve of KR points (KR the order of the running variable).  The pair (segment, cell (p, q) of
+ * Y) is the three-variable system with the Bernstein coefficients L_i - Y_jk, formed where it is needed and never stored.
+ * scale[3] = max |coefficient of X| + max |coefficient of Y| per component.  An index that is no segment, no cell or no
+ * pair, or a window that leaves the rows, gives nothing instead of an access out of bounds.
+ *   bsk_ssx_count(_host)  : the segments seg0 .. seg0 + nseg - 1 against Y's cells in chunks of `chunk`, nchunks =
+ *                           ceil(cells / chunk) <= 65535; boxes = bsk_rays_boxes of Y.  partial[nseg][nchunks] (int32) =
+ *                           the pairs of the chunk that are flat (the boxes of the segment's points and of the cell are
+ *                           not strictly disjoint and a component is below scale eps on the whole pair) or not strictly
+ *                           of one sign in any component.  prefilter != 0 drops a pair with strictly disjoint boxes
+ *                           before its window is read: the same result.
+ *   bsk_ssx_emit(_host)   : the same search; offset[nseg][nchunks] (int64) = the exclusive sums of partial in that order;
+ *                           pair_seg (the segment's index in the family), pair_cell[npairs] (int32), npairs >= 1, sorted by
+ *                           (segment, cell).
+ *   bsk_ssx_isolate(_host): per pair the walk of bsk_roots3_isolate on the formed system, one wave a pair:
+ *                           roots[npairs][R][3] as (w, s, t), w the running parameter of X, (s, t) Y's;
+ *                           R = min(6 (KR - 1)(KY0 - 1)(KY1 - 1), 32); near, count, status, nodes as there; status bit
+ *                           16 = a flat pair: not walked.
+ *   bsk_ssx_merge(_host)  : pair_key[npairs] (int64, ascending) = segment * ncY0 * ncY1 + cell over all pairs of the family;
+ *                           which[nnear] = the flat indices (pair, slot) of the zeros with near set.  keep[npairs][R]
+ *                           (bytes) of such a zero becomes 0 when one of the 13 pairs of the same line that precede it in
+ *                           (e, p, q) holds a zero within 2^-20 of the cell widths on all three axes.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; orders 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above).  No atomics, no waiting, no LDS; the host drivers and the kernels give the same bits.
+ *   bsk_ssx_last_kernel   : "ssx_count", "ssx_emit", "ssx_isolate", "ssx_merge" or the same behind "host ".
+ */
+bsk_status bsk_ssx_count_host(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                              const int32_t *firstX0, const int32_t *firstX1,
+                              int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                              const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                              int64_t seg0, int64_t nseg, int64_t chunk, int prefilter, const double *boxes, const double *scale,
+                              int32_t *partial);
+bsk_status bsk_ssx_count(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                         const int32_t *firstX0, const int32_t *firstX1,
+                         int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                         const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                         int64_t seg0, int64_t nseg, int64_t chunk, int prefilter, const double *boxes, const double *scale,
+                         int32_t *partial,
+                         void *stream);
+bsk_status bsk_ssx_emit_host(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                             const int32_t *firstX0, const int32_t *firstX1,
+                             int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                             const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                             int64_t seg0, int64_t nseg, int64_t chunk, int prefilter, const double *boxes, const double *scale,
+                             const int64_t *offset, int32_t *pair_seg, int32_t *pair_cell, int64_t npairs);
+bsk_status bsk_ssx_emit(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                        const int32_t *firstX0, const int32_t *firstX1,
+                        int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                        const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                        int64_t seg0, int64_t nseg, int64_t chunk, int prefilter, const double *boxes, const double *scale,
+                        const int64_t *offset, int32_t *pair_seg, int32_t *pair_cell, int64_t npairs,
+                        void *stream);
+bsk_status bsk_ssx_isolate_host(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                                const int32_t *firstX0, const int32_t *firstX1,
+                                int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                                const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                                const double *breaks_run, const double *breaksY0, const double *breaksY1, const double *scale,
+                                const int32_t *pair_seg, const int32_t *pair_cell, int64_t npairs, double *roots, uint8_t *near,
+                                int32_t *count, uint8_t *status, int32_t *nodes);
+bsk_status bsk_ssx_isolate(int KX0, int KX1, const double *rowsX, int64_t RX0, int64_t RX1, int64_t ncX0, int64_t ncX1,
+                           const int32_t *firstX0, const int32_t *firstX1,
+                           int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,
+                           const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G,
+                           const double *breaks_run, const double *breaksY0, const double *breaksY1, const double *scale,
+                           const int32_t *pair_seg, const int32_t *pair_cell, int64_t npairs, double *roots, uint8_t *near,
+                           int32_t *count, uint8_t *status, int32_t *nodes,
+                           void *stream);
+bsk_status bsk_ssx_merge_host(int R, const double *roots, int64_t ncrun, int64_t ncY0, int64_t ncY1, const double *breaks_run,
+                              const double *breaksY0, const double *breaksY1, const int64_t *pair_key, int64_t npairs,
+                              const int64_t *which, int64_t nnear, uint8_t *keep);
+bsk_status bsk_ssx_merge(int R, const double *roots, int64_t ncrun, int64_t ncY0, int64_t ncY1, const double *breaks_run,
+                         const double *breaksY0, const double *breaksY1, const int64_t *pair_key, int64_t npairs,
+                         const int64_t *which, int64_t nnear, uint8_t *keep,
+                         void *stream);
+const char *bsk_ssx_last_kernel(void);
+
+/*
  * Isolated common zeros of three scalar splines in three variables (Spline.zeros3; the statement of what a zero is and of
  * the arithmetic is in bspy_amd/roots3.py and DESIGN.md section 19).  The family keeps no handle.  The caller brings the
  * three variables to Bezier form with the band operator: rows[nsys][3][R0][R1][R2] (doubles) holds nsys systems of three

@@ -1,0 +1,409 @@
+"""
+The exact oracle of the surface-surface tests: the lattice, the pair systems, the product-leaf rule and the linking of
+bspy_amd/surfaces.py restated in rationals (``fractions.Fraction``), and the generator of tests/golden/surfaces.npz
+(``python tests/surfaces_ref.py``).  Every pair's system F_ijk = L_i - Y_jk is formed from the exact Bezier coefficients
+(``zeros2_ref.bezier_cells``) and solved by ``zeros3_ref.solve_cell``, imported and not edited: each vertex comes with a
+certificate (a box that holds exactly one zero, and the preconditioner of its error bound).  This file decides how many
+vertices a lattice line has, which product leaves they bound and how they are joined; it shares no code with the
+library.
+
+A vertex is identified by (family, line n, rank along the line by its running coordinate), which does not depend on the
+order in which a walk reports the zeros of one pair.
+"""
+import os
+from fractions import Fraction
+
+import numpy as np
+
+import zeros2_ref
+import zeros3_ref
+
+LEAF_BITS = 15
+ODD, MANY = 32, 64
+
+
+class Surface:
+    """One surface in exact Bezier form: breaks[2] (Fractions) and cells[i][j] = [x, y, z], each K0 rows of K1 Fractions."""
+
+    def __init__(self, order, knots, coefs):
+        coefs = np.asarray(coefs)
+        self.order = [int(k) for k in order]
+        b0, b1, xy = zeros2_ref.bezier_cells(order, knots, coefs[:2])
+        _, _, zz = zeros2_ref.bezier_cells(order, knots, coefs[[2, 2]])
+        self.breaks = [b0, b1]
+        self.ncells = [len(b0) - 1, len(b1) - 1]
+        self.cells = [[[xy[i][j][0], xy[i][j][1], zz[i][j][0]] for j in range(self.ncells[1])] for i in range(self.ncells[0])]
+
+    def value(self, u, v):
+        """The surface at the rational parameters (u, v)."""
+        at = []
+        for x, b in zip((u, v), self.breaks):
+            c = max(n for n in range(len(b) - 1) if b[n] <= x or n == 0)
+            at.append((c, (x - b[c]) / (b[c + 1] - b[c])))
+        (i, x), (j, y) = at
+        return [castel([castel(row, y) for row in comp], x) for comp in self.cells[i][j]]
+
+
+def castel(c, x):
+    b = list(c)
+    while len(b) > 1:
+        b = [(1 - x) * p + x * q for p, q in zip(b[:-1], b[1:])]
+    return b[0]
+
+
+def owner(n, G, nc):
+    c = min(n // G, nc - 1)
+    return c, Fraction(n - c * G, G)
+
+
+def line_value(breaks, n, G):
+    """The exact parameter of lattice line n."""
+    c, x = owner(n, G, len(breaks) - 1)
+    return breaks[c] + x * (breaks[c + 1] - breaks[c])
+
+
+def line_points(window, ax, x):
+    K0, K1 = len(window[0]), len(window[0][0])
+    if ax == 0:
+        return [[castel([window[d][r][i] for r in range(K0)], x) for d in range(3)] for i in range(K1)]
+    return [[castel(window[d][i], x) for d in range(3)] for i in range(K0)]
+
+
+def system(L, ywindow):
+    """[component (KR, K1, K2) object array] of F_ijk = L_i - Y_jk."""
+    K1, K2 = len(ywindow[0]), len(ywindow[0][0])
+    out = []
+    for d in range(3):
+        comp = np.empty((len(L), K1, K2), object)
+        for i in range(len(L)):
+            for j in range(K1):
+                for k in range(K2):
+                    comp[i, j, k] = L[i][d] - ywindow[d][j][k]
+        out.append(comp)
+    return out
+
+
+def pair_system(X, Y, ax, G, seg, cell):
+    """The exact system of one pair and its frame: (system, (t0 (3), h (3)), n, e)."""
+    ncrun, ncfix = X.ncells[1 - ax], X.ncells[ax]
+    n, e = divmod(seg, ncrun)
+    c, x = owner(n, G, ncfix)
+    i, j = (c, e) if ax == 0 else (e, c)
+    p, q = divmod(cell, Y.ncells[1])
+    brun = X.breaks[1 - ax]
+    t0 = (brun[e], Y.breaks[0][p], Y.breaks[1][q])
+    h = (brun[e + 1] - brun[e], Y.breaks[0][p + 1] - t0[1], Y.breaks[1][q + 1] - t0[2])
+    return system(line_points(X.cells[i][j], ax, x), Y.cells[p][q]), (t0, h), n, e
+
+
+def family_zeros(X, Y, ax, G, faces=None):
+    """All certified zeros of one family: [dict(seg, cell, n, e, lo, hi, Y, x, radius, t0, h)], sorted by (seg, cell, lo).
+    A pair whose zeros cannot all be certified raises ArithmeticError, unless ``faces`` is a list: it then receives
+    (seg, cell) and the pair reports nothing (the recorded edge and corner hits: a zero on a face of its cell)."""
+    ncrun, ncfix = X.ncells[1 - ax], X.ncells[ax]
+    out = []
+    for seg in range((ncfix * G + 1) * ncrun):
+        for cell in range(Y.ncells[0] * Y.ncells[1]):
+            F, (t0, h), n, e = pair_system(X, Y, ax, G, seg, cell)
+            if any(zeros3_ref.one_sign(comp) for comp in F):
+                continue
+            try:
+                certs = zeros3_ref.solve_cell(F)
+            except ArithmeticError:
+                if faces is None:
+                    raise
+                faces.append((seg, cell))
+                continue
+            for cert in certs:
+                for radius in zeros3_ref.RADII:                # the widest certificate that lies in one leaf per variable
+                    if radius <= cert["radius"] and straddles(cert, G):
+                        cert = zeros3_ref.certify(F, cert["x"], radius) or cert
+                out.append(dict(cert, seg=seg, cell=cell, n=n, e=e, t0=t0, h=h))
+    return out
+
+
+def leaf_range(cert, k, G):
+    lo, hi = int(cert["lo"][k] * G), int(cert["hi"][k] * G)
+    return lo, hi - 1 if cert["hi"][k] * G == hi else hi
+
+
+def straddles(cert, G):
+    return any(len(set(leaf_range(cert, k, G))) > 1 for k in range(3))
+
+
+def vertices(A, B, G, faces=None):
+    """The exact vertices of the four families in key order, each with ``fam``, ``rank`` (along its line, by the running
+    coordinate) and ``leaves`` (the one or two packed product leaves it bounds).  A certificate that straddles a leaf
+    boundary raises ArithmeticError: the case is not generic."""
+    out = []
+    for fam in range(4):
+        ax = fam & 1
+        X, Y = (A, B) if fam < 2 else (B, A)
+        zs = family_zeros(X, Y, ax, G, faces)
+        ncfix = X.ncells[ax]
+        for z in zs:
+            free = []
+            for k, cellat in enumerate((z["e"], z["cell"] // Y.ncells[1], z["cell"] % Y.ncells[1])):
+                lo, hi = leaf_range(z, k, G)
+                if lo != hi:
+                    raise ArithmeticError(f"a vertex of family {fam} within its certificate of a leaf boundary")
+                free.append(cellat * G + min(lo, G - 1))
+            z["leaves"] = []
+            for side in (z["n"] - 1, z["n"]):
+                if 0 <= side < ncfix * G:
+                    mine = [side, free[0]] if ax == 0 else [free[0], side]
+                    four = mine + free[1:] if fam < 2 else free[1:] + mine
+                    z["leaves"].append((four[0] << 3 * LEAF_BITS) | (four[1] << 2 * LEAF_BITS) | (four[2] << LEAF_BITS) | four[3])
+            z["fam"] = fam
+            z["w"] = z["t0"][0] + (z["lo"][0] + z["hi"][0]) / 2 * z["h"][0]
+        zs.sort(key=lambda z: (z["n"], z["w"]))
+        for n in sorted({z["n"] for z in zs}):
+            for rank, z in enumerate([z for z in zs if z["n"] == n]):
+                z["rank"] = rank
+        out.extend(zs)
+    return out
+
+
+def link(verts):
+    """(segments, components, findings): segments = {frozenset of two vertex ids}, components = [(closed, frozenset of
+    ids)], findings = {packed leaf: 32 | 64}; an id is (fam, n, rank)."""
+    by_leaf = {}
+    for z in verts:
+        for leaf in z["leaves"]:
+            by_leaf.setdefault(leaf, []).append((z["fam"], z["n"], z["rank"]))
+    segments, findings, adj = set(), {}, {}
+    for leaf, ids in by_leaf.items():
+        if len(ids) == 2:
+            segments.add(frozenset(ids))
+            adj.setdefault(ids[0], []).append(ids[1])
+            adj.setdefault(ids[1], []).append(ids[0])
+        else:
+            findings[leaf] = ODD if len(ids) == 1 else MANY
+    seen, components = set(), []
+    for start in adj:
+        if start in seen:
+            continue
+        comp, stack = set(), [start]
+        while stack:
+            v = stack.pop()
+            if v not in comp:
+                comp.add(v)
+                stack.extend(adj[v])
+        seen |= comp
+        components.append((all(len(adj[v]) == 2 for v in comp), frozenset(comp)))
+    return segments, components, findings
+
+
+def chains(verts, segments):
+    """The components as ordered lists of vertices (an open chain from one end, a loop from any vertex, closed by it)."""
+    by_id = {(z["fam"], z["n"], z["rank"]): z for z in verts}
+    adj = {}
+    for seg in segments:
+        a, b = tuple(seg)
+        adj.setdefault(a, []).append(b)
+        adj.setdefault(b, []).append(a)
+    seen, out = set(), []
+    for start in sorted(adj, key=lambda v: (len(adj[v]), v)):      # ends first
+        if start in seen:
+            continue
+        chain, at, prev = [start], start, None
+        seen.add(start)
+        while True:
+            onward = [v for v in adj[at] if v != prev and (v not in seen or (v == start and len(chain) > 2))]
+            if not onward:
+                break
+            prev, at = at, onward[0]
+            chain.append(at)
+            if at == start:
+                break
+            seen.add(at)
+        out.append([by_id[v] for v in chain])
+    return out
+
+
+def point4(z, A, B, G):
+    """(u, v, s, t) of a vertex: the centre of its certificate and the exact value of its line."""
+    ax = z["fam"] & 1
+    X = A if z["fam"] < 2 else B
+    mid = [z["t0"][k] + (z["lo"][k] + z["hi"][k]) / 2 * z["h"][k] for k in range(3)]
+    fixed = line_value(X.breaks[ax], z["n"], G)
+    own = [fixed, mid[0]] if ax == 0 else [mid[0], fixed]
+    return own + mid[1:] if z["fam"] < 2 else mid[1:] + own
+
+
+def lipschitz(S):
+    """A bound on |dS/du| + |dS/dv|: the largest difference of neighbouring Bezier points per unit of the parameter."""
+    total = 0.0
+    for ax in range(2):
+        K = S.order[ax]
+        h = min(float(b1 - b0) for b0, b1 in zip(S.breaks[ax][:-1], S.breaks[ax][1:]))
+        worst = 0.0
+        for line in S.cells:
+            for cell in line:
+                pts = np.array([[[float(v) for v in row] for row in comp] for comp in cell])
+                worst = max(worst, float(np.sqrt((np.diff(pts, axis=ax + 1) ** 2).sum(axis=0)).max()))
+        total += (K - 1) * worst / h
+    return total
+
+
+def polyline_gap(A, B, chain, G, samples=33):
+    """The largest |a(q_a(t)) - b(q_b(t))| over ``samples`` values of t, q the polyline through the exact vertices, linear in
+    the normalised chord length measured in space on a (the chords' lengths rounded to floats, everything else exact), over
+    the sagitta bound (M_a + M_b) (h / G)^2 / L (1 + L) of tests/test_surfaces_host.py."""
+    pts = [point4(z, A, B, G) for z in chain]
+    xyz = [A.value(p[0], p[1]) for p in pts]
+    at = [Fraction(0)]
+    for p, q in zip(xyz[:-1], xyz[1:]):
+        at.append(at[-1] + Fraction(float(sum((x - y) ** 2 for x, y in zip(p, q))) ** 0.5))
+    worst = Fraction(0)
+    for n in range(samples):
+        t = at[-1] * Fraction(n, samples - 1)
+        k = max(i for i in range(len(at) - 1) if at[i] <= t)
+        lam = (t - at[k]) / (at[k + 1] - at[k])
+        q = [(1 - lam) * x + lam * y for x, y in zip(pts[k], pts[k + 1])]
+        pa, pb = A.value(q[0], q[1]), B.value(q[2], q[3])
+        worst = max(worst, max(abs(x - y) for x, y in zip(pa, pb)))
+    L = max(float(S.breaks[ax][-1] - S.breaks[ax][0]) for S in (A, B) for ax in range(2))
+    h = max(float(b1 - b0) for S in (A, B) for ax in range(2) for b0, b1 in zip(S.breaks[ax][:-1], S.breaks[ax][1:]))
+    return float(worst) / ((lipschitz(A) + lipschitz(B)) * (h / G) ** 2 / L * (1.0 + L))
+
+
+# ------------------------------------------------------------------------------------------ the recorded cases
+def knots_of(order, breaks, dtype=np.float64):
+    breaks = np.asarray(breaks, np.float64)
+    return np.concatenate(([breaks[0]] * (order - 1), breaks, [breaks[-1]] * (order - 1))).astype(dtype)
+
+
+def greville(order, knots):
+    knots = np.asarray(knots, np.float64)
+    return np.array([knots[i + 1:i + order].mean() for i in range(len(knots) - order)])
+
+
+def patch(order, breaks, fx, fy, fz, dtype=np.float64, knots=None):
+    """(order, knots, coefs): the surface whose control points are (fx, fy, fz) at the Greville abscissae."""
+    knots = [knots_of(order[d], breaks[d], dtype) for d in range(2)] if knots is None else knots
+    U, V = np.meshgrid(greville(order[0], knots[0]), greville(order[1], knots[1]), indexing="ij")
+    return list(order), knots, np.stack([fx(U, V), fy(U, V), fz(U, V)]).astype(dtype)
+
+
+def cases():
+    """name -> dict(a, b, depth, kind).  The footprints are skewed by odd amounts so that no vertex lies on a lattice line
+    of both surfaces (the generator asserts it: such a vertex raises in ``vertices``)."""
+    out = {}
+    bump3x2 = patch((4, 4), ([0.0, 0.3, 0.7, 1.0], [0.0, 0.45, 1.0]), lambda u, v: u, lambda u, v: v,
+                    lambda u, v: 0.9 * np.sin(3 * u) * np.cos(2 * v))
+    # a plane patch over the whole footprint of the bump: z = 0.31 + 0.1 x + 0.05 y
+    plane = patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: -0.13 + 1.31 * u + 0.07 * v, lambda u, v: -0.09 + 0.05 * u + 1.23 * v,
+                  lambda u, v: 0.31 + 0.1 * (-0.13 + 1.31 * u + 0.07 * v) + 0.05 * (-0.09 + 0.05 * u + 1.23 * v))
+    for depth in (0, 1, 2):
+        out[f"plane_d{depth}"] = dict(a=plane, b=bump3x2, depth=depth, kind="plane")
+    cap = patch((4, 4), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: 0.9 - 3.0 * ((u - 0.47) ** 2 + (v - 0.53) ** 2))
+    sheet = patch((4, 4), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: -0.11 + 1.19 * u + 0.06 * v, lambda u, v: -0.08 - 0.04 * u + 1.21 * v,
+                  lambda u, v: 0.22 + 0.07 * u - 0.05 * v + 0.1 * u * v)
+    out["loop"] = dict(a=cap, b=sheet, depth=1, kind="loop")
+    wide = patch((3, 4), ([0.0, 0.4, 0.75, 1.0], [0.0, 0.55, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: 0.3 + 0.4 * u - 0.2 * v + 0.3 * u * v)
+    small = patch((4, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: 0.23 + 0.41 * u + 0.03 * v, lambda u, v: 0.19 + 0.02 * u + 0.47 * v,
+                  lambda u, v: 0.45 + 0.2 * np.sin(2 * u) - 0.1 * v)
+    out["open_b"] = dict(a=wide, b=small, depth=1, kind="open_b")
+    many = patch((4, 4), ([0.0, 0.2, 0.45, 0.6, 0.8, 1.0], [0.0, 0.3, 0.5, 0.8, 1.0]), lambda u, v: u, lambda u, v: v,
+                 lambda u, v: 0.5 + 0.3 * np.sin(5 * u) * np.cos(4 * v))
+    out["cells5x4"] = dict(a=plane, b=many, depth=0, kind="cells")
+    dk = [np.array([0, 0, 0, 0, 0.35, 0.35, 0.7, 1, 1, 1, 1.0]), knots_of(4, [0.0, 0.45, 1.0])]
+    out["double_knot"] = dict(a=plane, b=patch((4, 4), None, lambda u, v: u, lambda u, v: v, lambda u, v: 0.9 * np.sin(3 * u) * np.cos(2 * v), knots=dk),
+                              depth=1, kind="plane")
+    out["float32"] = dict(a=tuple(patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: -0.13 + 1.31 * u + 0.07 * v,
+                                        lambda u, v: -0.09 + 0.05 * u + 1.23 * v, lambda u, v: 0.33 + 0.13 * u + 0.06 * v, np.float32)),
+                          b=patch((4, 4), ([0.0, 0.3, 0.7, 1.0], [0.0, 0.45, 1.0]), lambda u, v: u, lambda u, v: v,
+                                  lambda u, v: 0.9 * np.sin(3 * u) * np.cos(2 * v), np.float32), depth=1, kind="plane")
+    far = patch((4, 4), ([100.0, 101.0, 102.5, 103.0], [-40.0, -39.25, -38.0]), lambda u, v: 5000.0 * (u - 100.0) / 3.0,
+                lambda u, v: 5000.0 * (v + 40.0) / 2.0, lambda u, v: 4500.0 * np.sin(u - 100.0) * np.cos(v + 40.0))
+    farplane = patch((2, 2), ([100.0, 103.0], [-40.0, -38.0]), lambda u, v: -650.0 + 6550.0 * (u - 100.0) / 3.0 + 175.0 * (v + 40.0),
+                     lambda u, v: -450.0 + 83.0 * (u - 100.0) + 6150.0 * (v + 40.0) / 2.0,
+                     lambda u, v: 1550.0 + 166.0 * (u - 100.0) + 125.0 * (v + 40.0))
+    out["shifted"] = dict(a=farplane, b=far, depth=1, kind="plane")
+    # a hit on a shared cell edge and one on a cell corner of Y: Y is the plane z = 0 on 2 x 2 cells with the knot lines
+    # s = 1/2, t = 1/2; line u = 1/2 of X is (1/2, y, v - 3/8), dyadic numbers throughout
+    flat2x2 = patch((2, 2), ([0.0, 0.5, 1.0], [0.0, 0.5, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: 0.0 * u)
+    out["edge"] = dict(a=patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: 0.25 + 0.5 * u, lambda u, v: 0.25 + 0.25 * u, lambda u, v: v - 0.375),
+                       b=flat2x2, depth=1, kind="edge")
+    out["corner"] = dict(a=patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: 0.25 + 0.5 * u, lambda u, v: 0.25 + 0.5 * u, lambda u, v: v - 0.375),
+                         b=flat2x2, depth=1, kind="corner")
+    high = patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: 5.0 + 0.1 * u)
+    out["disjoint"] = dict(a=high, b=bump3x2, depth=1, kind="none")
+    # boxes that overlap without a hit: the plane z = 1/2 + x stays above 0.9 sin 3x, the bump's ridge
+    steep = patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: 0.5 + u + 0.0 * v)
+    out["overlap_nohit"] = dict(a=steep, b=bump3x2, depth=1, kind="none")
+    level = patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: 0.1 + 0.8 * u, lambda u, v: 0.1 + 0.8 * v, lambda u, v: 0.0 * u)
+    out["coincident"] = dict(a=level, b=flat2x2, depth=0, kind="flat")
+    saddle = patch((4, 4), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: u, lambda u, v: v, lambda u, v: (u - 0.47) ** 2 - (v - 0.52) ** 2)
+    out["two_in_leaf"] = dict(a=patch((2, 2), ([0.0, 1.0], [0.0, 1.0]), lambda u, v: -0.1 + 1.2 * u + 0.03 * v, lambda u, v: -0.1 + 0.02 * u + 1.2 * v,
+                                      lambda u, v: 0.02 + 0.0 * u), b=saddle, depth=0, kind="many")
+    return out
+
+
+def generate(path):
+    store = {}
+    for name, case in cases().items():
+        A, B = Surface(*case["a"]), Surface(*case["b"])
+        G = 1 << case["depth"]
+        kind = case["kind"]
+        for side in "ab":
+            order, knots, coefs = case[side]
+            store[f"{name}/{side}_order"] = np.array(order)
+            store[f"{name}/{side}_knots0"], store[f"{name}/{side}_knots1"], store[f"{name}/{side}_coefs"] = knots[0], knots[1], coefs
+        store[f"{name}/depth"], store[f"{name}/kind"] = np.array(case["depth"]), np.array(kind)
+        if kind == "flat":                                     # nothing to certify: every pair is coincident
+            verts, faces = [], []
+        else:
+            faces = [] if kind in ("edge", "corner") else None
+            try:
+                verts = vertices(A, B, G, faces)
+            except ArithmeticError:
+                if kind not in ("edge", "corner"):
+                    raise
+                verts = None                                   # b's own line through the hit: a vertex on two lattices
+        if kind in ("edge", "corner"):
+            want = {(0, 0), (1, 0)} if kind == "edge" else {(0, 0), (0, 1), (1, 0), (1, 1)}
+            assert {divmod(cell, B.ncells[1]) for _, cell in faces} >= want, (name, faces)
+            point = (Fraction(1, 2), Fraction(3, 8), Fraction(1, 2), Fraction(3, 8) if kind == "edge" else Fraction(1, 2))
+            assert A.value(*point[:2]) == B.value(*point[2:]), name
+            store[f"{name}/point"] = np.array([float(x) for x in point])
+            verts = []
+        segments, components, findings = link(verts)
+        if kind == "none":
+            assert not verts, name
+        if kind == "loop":
+            assert len(components) == 1 and components[0][0] and not findings, name
+        if kind == "open_b":
+            ends = [z for z in verts if len(z["leaves"]) == 1]
+            assert len(components) == 1 and not components[0][0] and len(ends) == 2 and all(z["fam"] >= 2 for z in ends), name
+        if kind in ("plane", "cells"):
+            assert verts and all(not closed for closed, _ in components), name      # coarse depths may hold two branches in a leaf
+        if kind == "many":
+            assert MANY in findings.values() and not segments, name
+        if name == "plane_d0":                                 # chains that run into the leaf with two branches and end there
+            inside = {v for z in verts for v in [(z["fam"], z["n"], z["rank"])] if any(findings.get(leaf) == MANY for leaf in z["leaves"])}
+            assert len(components) == 3 and all(len(c & inside) >= 1 for _, c in components), name
+        gaps = [polyline_gap(A, B, chain, G) for chain in chains(verts, segments)]
+        assert len(gaps) == len(components) and all(g <= 1.0 for g in gaps), (name, gaps)   # the reference alone passes
+        store[f"{name}/polyline_gap"] = np.array(gaps)
+        ids = [(z["fam"], z["n"], z["rank"]) for z in verts]
+        store[f"{name}/vert_id"] = np.array(ids, np.int64).reshape(-1, 3)
+        store[f"{name}/vert_pair"] = np.array([(z["seg"], z["cell"]) for z in verts], np.int64).reshape(-1, 2)
+        store[f"{name}/vert_x"] = np.array([[float(v) for v in z["x"]] for z in verts]).reshape(-1, 3)
+        store[f"{name}/vert_radius"] = np.array([float(z["radius"]) for z in verts])
+        store[f"{name}/vert_Y"] = np.array([[[float(v) for v in row] for row in z["Y"]] for z in verts]).reshape(-1, 3, 3)
+        where = {v: k for k, v in enumerate(ids)}
+        store[f"{name}/segments"] = np.array(sorted(sorted(where[v] for v in s) for s in segments), np.int64).reshape(-1, 2)
+        comp = sorted((sorted(where[v] for v in c), closed) for closed, c in components)
+        store[f"{name}/comp_offsets"] = np.cumsum([0] + [len(c) for c, _ in comp])
+        store[f"{name}/comp_vertices"] = np.array([v for c, _ in comp for v in c], np.int64)
+        store[f"{name}/comp_closed"] = np.array([closed for _, closed in comp], bool)
+        store[f"{name}/findings"] = np.array(sorted(findings.items()), np.int64).reshape(-1, 2)
+        print(name, "vertices", len(verts), "segments", len(segments), "components", [(closed, len(c)) for closed, c in components],
+              "findings", sorted(findings.values()), "polyline gap / bound", [round(g, 5) for g in gaps], flush=True)
+    np.savez_compressed(path, **store)
+
+
+if __name__ == "__main__":
+    generate(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "surfaces.npz"))
