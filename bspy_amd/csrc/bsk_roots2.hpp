@@ -55,8 +55,8 @@ constexpr int ROOTS2_BLOCK = 256;                   // roots2_flag, roots2_merge
 constexpr int ROOTS2_ISOLATE_BLOCK = 64;            // one wave: the walk may use the whole register file
 constexpr int ROOTS2_DEPTH = 24;                    // halvings per axis
 constexpr int ROOTS2_NEWTON = 8;
-// nodes a walk may visit: 4 x 820, the largest count on the recorded cases, rounded up to a power of two
-constexpr int ROOTS2_WALK = 4096;
+// nodes a walk may visit: 4 x 5052, the largest count on the recorded cases, rounded up to a power of two
+constexpr int ROOTS2_WALK = 32768;
 constexpr double ROOTS2_LEAF_W = 0x1p-24;
 constexpr double ROOTS2_GROW = 0x1p-44;
 constexpr double ROOTS2_SAME = 0x1p-20;

@@ -64,8 +64,8 @@ LAST_PATHS = []
 EPS = roots.EPS
 DEPTH = 24                 # halvings per axis
 NEWTON = 8
-# nodes a walk may visit: 4 x 820, the largest count on the recorded cases, rounded up to a power of two
-WALK = 4096
+# nodes a walk may visit: 4 x 5052, the largest count on the recorded cases, rounded up to a power of two
+WALK = 32768
 LEAF_W = 2.0 ** -24
 GROW = 2.0 ** -44
 SAME = 2.0 ** -20

@@ -341,67 +341,73 @@ def cases():
     return out
 
 
+def record(store, name, case):
+    """The entries of one case, certified or an AssertionError / ArithmeticError."""
+    A, B = Surface(*case["a"]), Surface(*case["b"])
+    G = 1 << case["depth"]
+    kind = case["kind"]
+    for side in "ab":
+        order, knots, coefs = case[side]
+        store[f"{name}/{side}_order"] = np.array(order)
+        store[f"{name}/{side}_knots0"], store[f"{name}/{side}_knots1"], store[f"{name}/{side}_coefs"] = knots[0], knots[1], coefs
+    store[f"{name}/depth"], store[f"{name}/kind"] = np.array(case["depth"]), np.array(kind)
+    if kind == "flat":                                     # nothing to certify: every pair is coincident
+        verts, faces = [], []
+    else:
+        faces = [] if kind in ("edge", "corner") else None
+        try:
+            verts = vertices(A, B, G, faces)
+        except ArithmeticError:
+            if kind not in ("edge", "corner"):
+                raise
+            verts = None                                   # b's own line through the hit: a vertex on two lattices
+    if kind in ("edge", "corner"):
+        want = {(0, 0), (1, 0)} if kind == "edge" else {(0, 0), (0, 1), (1, 0), (1, 1)}
+        assert {divmod(cell, B.ncells[1]) for _, cell in faces} >= want, (name, faces)
+        point = (Fraction(1, 2), Fraction(3, 8), Fraction(1, 2), Fraction(3, 8) if kind == "edge" else Fraction(1, 2))
+        assert A.value(*point[:2]) == B.value(*point[2:]), name
+        store[f"{name}/point"] = np.array([float(x) for x in point])
+        verts = []
+    segments, components, findings = link(verts)
+    if kind == "none":
+        assert not verts, name
+    if kind == "loop":
+        assert len(components) == 1 and components[0][0] and not findings, name
+    if kind == "open_b":
+        ends = [z for z in verts if len(z["leaves"]) == 1]
+        assert len(components) == 1 and not components[0][0] and len(ends) == 2 and all(z["fam"] >= 2 for z in ends), name
+    if kind in ("plane", "cells"):
+        assert verts and all(not closed for closed, _ in components), name      # coarse depths may hold two branches in a leaf
+    if kind == "many":
+        assert MANY in findings.values() and not segments, name
+    if name == "plane_d0":                                 # chains that run into the leaf with two branches and end there
+        inside = {v for z in verts for v in [(z["fam"], z["n"], z["rank"])] if any(findings.get(leaf) == MANY for leaf in z["leaves"])}
+        assert len(components) == 3 and all(len(c & inside) >= 1 for _, c in components), name
+    gaps = [polyline_gap(A, B, chain, G) for chain in chains(verts, segments)]
+    assert len(gaps) == len(components) and all(g <= 1.0 for g in gaps), (name, gaps)   # the reference alone passes
+    store[f"{name}/polyline_gap"] = np.array(gaps)
+    ids = [(z["fam"], z["n"], z["rank"]) for z in verts]
+    store[f"{name}/vert_id"] = np.array(ids, np.int64).reshape(-1, 3)
+    store[f"{name}/vert_pair"] = np.array([(z["seg"], z["cell"]) for z in verts], np.int64).reshape(-1, 2)
+    store[f"{name}/vert_x"] = np.array([[float(v) for v in z["x"]] for z in verts]).reshape(-1, 3)
+    store[f"{name}/vert_radius"] = np.array([float(z["radius"]) for z in verts])
+    store[f"{name}/vert_Y"] = np.array([[[float(v) for v in row] for row in z["Y"]] for z in verts]).reshape(-1, 3, 3)
+    where = {v: k for k, v in enumerate(ids)}
+    store[f"{name}/segments"] = np.array(sorted(sorted(where[v] for v in s) for s in segments), np.int64).reshape(-1, 2)
+    comp = sorted((sorted(where[v] for v in c), closed) for closed, c in components)
+    store[f"{name}/comp_offsets"] = np.cumsum([0] + [len(c) for c, _ in comp])
+    store[f"{name}/comp_vertices"] = np.array([v for c, _ in comp for v in c], np.int64)
+    store[f"{name}/comp_closed"] = np.array([closed for _, closed in comp], bool)
+    store[f"{name}/findings"] = np.array(sorted(findings.items()), np.int64).reshape(-1, 2)
+    print(name, "vertices", len(verts), "segments", len(segments), "components", [(closed, len(c)) for closed, c in components],
+          "findings", sorted(findings.values()), "polyline gap / bound", [round(g, 5) for g in gaps], flush=True)
+    return verts, findings
+
+
 def generate(path):
     store = {}
     for name, case in cases().items():
-        A, B = Surface(*case["a"]), Surface(*case["b"])
-        G = 1 << case["depth"]
-        kind = case["kind"]
-        for side in "ab":
-            order, knots, coefs = case[side]
-            store[f"{name}/{side}_order"] = np.array(order)
-            store[f"{name}/{side}_knots0"], store[f"{name}/{side}_knots1"], store[f"{name}/{side}_coefs"] = knots[0], knots[1], coefs
-        store[f"{name}/depth"], store[f"{name}/kind"] = np.array(case["depth"]), np.array(kind)
-        if kind == "flat":                                     # nothing to certify: every pair is coincident
-            verts, faces = [], []
-        else:
-            faces = [] if kind in ("edge", "corner") else None
-            try:
-                verts = vertices(A, B, G, faces)
-            except ArithmeticError:
-                if kind not in ("edge", "corner"):
-                    raise
-                verts = None                                   # b's own line through the hit: a vertex on two lattices
-        if kind in ("edge", "corner"):
-            want = {(0, 0), (1, 0)} if kind == "edge" else {(0, 0), (0, 1), (1, 0), (1, 1)}
-            assert {divmod(cell, B.ncells[1]) for _, cell in faces} >= want, (name, faces)
-            point = (Fraction(1, 2), Fraction(3, 8), Fraction(1, 2), Fraction(3, 8) if kind == "edge" else Fraction(1, 2))
-            assert A.value(*point[:2]) == B.value(*point[2:]), name
-            store[f"{name}/point"] = np.array([float(x) for x in point])
-            verts = []
-        segments, components, findings = link(verts)
-        if kind == "none":
-            assert not verts, name
-        if kind == "loop":
-            assert len(components) == 1 and components[0][0] and not findings, name
-        if kind == "open_b":
-            ends = [z for z in verts if len(z["leaves"]) == 1]
-            assert len(components) == 1 and not components[0][0] and len(ends) == 2 and all(z["fam"] >= 2 for z in ends), name
-        if kind in ("plane", "cells"):
-            assert verts and all(not closed for closed, _ in components), name      # coarse depths may hold two branches in a leaf
-        if kind == "many":
-            assert MANY in findings.values() and not segments, name
-        if name == "plane_d0":                                 # chains that run into the leaf with two branches and end there
-            inside = {v for z in verts for v in [(z["fam"], z["n"], z["rank"])] if any(findings.get(leaf) == MANY for leaf in z["leaves"])}
-            assert len(components) == 3 and all(len(c & inside) >= 1 for _, c in components), name
-        gaps = [polyline_gap(A, B, chain, G) for chain in chains(verts, segments)]
-        assert len(gaps) == len(components) and all(g <= 1.0 for g in gaps), (name, gaps)   # the reference alone passes
-        store[f"{name}/polyline_gap"] = np.array(gaps)
-        ids = [(z["fam"], z["n"], z["rank"]) for z in verts]
-        store[f"{name}/vert_id"] = np.array(ids, np.int64).reshape(-1, 3)
-        store[f"{name}/vert_pair"] = np.array([(z["seg"], z["cell"]) for z in verts], np.int64).reshape(-1, 2)
-        store[f"{name}/vert_x"] = np.array([[float(v) for v in z["x"]] for z in verts]).reshape(-1, 3)
-        store[f"{name}/vert_radius"] = np.array([float(z["radius"]) for z in verts])
-        store[f"{name}/vert_Y"] = np.array([[[float(v) for v in row] for row in z["Y"]] for z in verts]).reshape(-1, 3, 3)
-        where = {v: k for k, v in enumerate(ids)}
-        store[f"{name}/segments"] = np.array(sorted(sorted(where[v] for v in s) for s in segments), np.int64).reshape(-1, 2)
-        comp = sorted((sorted(where[v] for v in c), closed) for closed, c in components)
-        store[f"{name}/comp_offsets"] = np.cumsum([0] + [len(c) for c, _ in comp])
-        store[f"{name}/comp_vertices"] = np.array([v for c, _ in comp for v in c], np.int64)
-        store[f"{name}/comp_closed"] = np.array([closed for _, closed in comp], bool)
-        store[f"{name}/findings"] = np.array(sorted(findings.items()), np.int64).reshape(-1, 2)
-        print(name, "vertices", len(verts), "segments", len(segments), "components", [(closed, len(c)) for closed, c in components],
-              "findings", sorted(findings.values()), "polyline gap / bound", [round(g, 5) for g in gaps], flush=True)
+        record(store, name, case)
     np.savez_compressed(path, **store)
 
 
