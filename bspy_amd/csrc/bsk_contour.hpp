@@ -42,15 +42,17 @@
 #include <cmath>
 #include <cstdint>
 
+#include "bsk_box2.hpp"
 #include "bsk_roots.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bskcontour {
 
+using bskbox2::halve;
+using bskbox2::restrict_box;
 using bskroots::lerp;
 using bskroots::restrict_to;
-using bskroots::split;
 using bskroots::value;
 
 constexpr int CONTOUR_BLOCK = 256;                  // contour_flag
@@ -268,61 +270,17 @@ BSK_HD void leaf(const Grid &g, const double *breaks0, const double *breaks1, lo
     }
 }
 
-// the halves of cur along AXIS (a compile-time axis: the two axes never store to one array under a run-time index)
-template <int K0, int K1, int AXIS>
-BSK_HD void halve(const double *cur, double *left, double *right)
-{
-    constexpr int K = AXIS == 0 ? K0 : K1, LINES = AXIS == 0 ? K1 : K0;
-    constexpr int STEP = AXIS == 0 ? K1 : 1, LINE = AXIS == 0 ? 1 : K1;
-#pragma unroll
-    for (int n = 0; n < LINES; ++n) {
-        double line[K], l[K], r[K];
-#pragma unroll
-        for (int e = 0; e < K; ++e) line[e] = cur[n * LINE + e * STEP];
-        split<K>(line, 0.5, l, r);
-#pragma unroll
-        for (int e = 0; e < K; ++e) {
-            left[n * LINE + e * STEP] = l[e];
-            right[n * LINE + e * STEP] = r[e];
-        }
-    }
-}
-
 // One step down from a live node: cur becomes its left live child, else its right live one (0, 1), or stays (-1).
 template <int K0, int K1, int AXIS>
 BSK_HD int descend(double *cur, double tau)
 {
     constexpr int N = K0 * K1;
     double left[N], right[N];
-    halve<K0, K1, AXIS>(cur, left, right);
+    halve<1, K0, K1, AXIS>(cur, left, right);
     const bool liveL = !one_side<N>(left, tau), liveR = !one_side<N>(right, tau);
 #pragma unroll
     for (int e = 0; e < N; ++e) cur[e] = liveL ? left[e] : (liveR ? right[e] : cur[e]);
     return liveL ? 0 : (liveR ? 1 : -1);
-}
-
-// the cell's coefficients c on the box [lo0, lo0 + w0] x [lo1, lo1 + w1]: every column, then every row
-template <int K0, int K1>
-BSK_HD void restrict_box(const double *c, double lo0, double w0, double lo1, double w1, double *out)
-{
-#pragma unroll
-    for (int s = 0; s < K1; ++s) {
-        double col[K0], res[K0];
-#pragma unroll
-        for (int r = 0; r < K0; ++r) col[r] = c[r * K1 + s];
-        restrict_to<K0>(col, lo0, w0, res);
-#pragma unroll
-        for (int r = 0; r < K0; ++r) out[r * K1 + s] = res[r];
-    }
-#pragma unroll
-    for (int r = 0; r < K0; ++r) {
-        double row[K1], res[K1];
-#pragma unroll
-        for (int s = 0; s < K1; ++s) row[s] = out[r * K1 + s];
-        restrict_to<K1>(row, lo1, w1, res);
-#pragma unroll
-        for (int s = 0; s < K1; ++s) out[r * K1 + s] = res[s];
-    }
 }
 
 // node (depth, path) below a top box: index and halvings per axis, axis 0 first
@@ -395,7 +353,7 @@ BSK_HD void march_lane(const Grid &g, const double *breaks0, const double *break
             tau = tau_of<K0, K1>(g.scale[b]);
             const double w = 1.0 / (double)(1 << P);
             if (P > 0) {
-                restrict_box<K0, K1>(own, (double)qi * w, w, (double)qj * w, w, cur);
+                restrict_box<1, K0, K1>(own, (double)qi * w, w, (double)qj * w, w, cur);
             } else {
 #pragma unroll
                 for (int e = 0; e < N; ++e) cur[e] = own[e];
@@ -423,7 +381,7 @@ BSK_HD void march_lane(const Grid &g, const double *breaks0, const double *break
                 const double w0 = 1.0 / (double)(1 << (P + h0)), w1 = 1.0 / (double)(1 << (P + h1));
                 double own[N];
                 load_cell<K0, K1>(g, b, i, j, own);            // the cell's own coefficients, read again
-                restrict_box<K0, K1>(own, (double)((qi << h0) + i0) * w0, w0, (double)((qj << h1) + i1) * w1, w1, cur);
+                restrict_box<1, K0, K1>(own, (double)((qi << h0) + i0) * w0, w0, (double)((qj << h1) + i1) * w1, w1, cur);
                 live = !one_side<N>(cur, tau);
             }
         } else if (depth_now == 2 * D) {

@@ -41,15 +41,16 @@
 #include <cmath>
 #include <cstdint>
 
+#include "bsk_box2.hpp"
 #include "bsk_roots.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bskroots2 {
 
+using bskbox2::halve;
+using bskbox2::restrict_box;
 using bskroots::lerp;
-using bskroots::restrict_to;
-using bskroots::split;
 
 constexpr int ROOTS2_BLOCK = 256;                   // roots2_flag, roots2_merge
 constexpr int ROOTS2_ISOLATE_BLOCK = 64;            // one wave: the walk may use the whole register file
@@ -101,29 +102,6 @@ BSK_HD bool excluded(const double *c)
     return one_sign<K0 * K1>(c) || one_sign<K0 * K1>(c + K0 * K1);
 }
 
-// the halves of cur along AXIS (a compile-time axis: the two axes never store to one array under a run-time index)
-template <int K0, int K1, int AXIS>
-BSK_HD void halve(const double *cur, double *left, double *right)
-{
-    constexpr int K = AXIS == 0 ? K0 : K1, LINES = AXIS == 0 ? K1 : K0;
-    constexpr int STEP = AXIS == 0 ? K1 : 1, LINE = AXIS == 0 ? 1 : K1;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int n = 0; n < LINES; ++n) {
-            const int base = d * K0 * K1 + n * LINE;
-            double line[K], l[K], r[K];
-#pragma unroll
-            for (int e = 0; e < K; ++e) line[e] = cur[base + e * STEP];
-            split<K>(line, 0.5, l, r);
-#pragma unroll
-            for (int e = 0; e < K; ++e) {
-                left[base + e * STEP] = l[e];
-                right[base + e * STEP] = r[e];
-            }
-        }
-}
-
 // One step down from a live node: cur becomes its left live child, else its right live one (0, 1), or stays (-1: both
 // children are dropped).  The halves are locals of the step and cur is written once, in index order.
 template <int K0, int K1, int AXIS>
@@ -131,39 +109,11 @@ BSK_HD int descend(double *cur)
 {
     constexpr int N = 2 * K0 * K1;
     double left[N], right[N];
-    halve<K0, K1, AXIS>(cur, left, right);
+    halve<2, K0, K1, AXIS>(cur, left, right);
     const bool liveL = !excluded<K0, K1>(left), liveR = !excluded<K0, K1>(right);
 #pragma unroll
     for (int e = 0; e < N; ++e) cur[e] = liveL ? left[e] : (liveR ? right[e] : cur[e]);
     return liveL ? 0 : (liveR ? 1 : -1);
-}
-
-// the cell's coefficients c on the box [lo0, lo0 + w0] x [lo1, lo1 + w1]: every column, then every row
-template <int K0, int K1>
-BSK_HD void restrict_box(const double *c, double lo0, double w0, double lo1, double w1, double *out)
-{
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        const int base = d * K0 * K1;
-#pragma unroll
-        for (int j = 0; j < K1; ++j) {
-            double col[K0], res[K0];
-#pragma unroll
-            for (int i = 0; i < K0; ++i) col[i] = c[base + i * K1 + j];
-            restrict_to<K0>(col, lo0, w0, res);
-#pragma unroll
-            for (int i = 0; i < K0; ++i) out[base + i * K1 + j] = res[i];
-        }
-#pragma unroll
-        for (int i = 0; i < K0; ++i) {
-            double row[K1], res[K1];
-#pragma unroll
-            for (int j = 0; j < K1; ++j) row[j] = out[base + i * K1 + j];
-            restrict_to<K1>(row, lo1, w1, res);
-#pragma unroll
-            for (int j = 0; j < K1; ++j) out[base + i * K1 + j] = res[j];
-        }
-    }
 }
 
 // value and derivative of K Bernstein coefficients at x
@@ -338,7 +288,7 @@ BSK_HD void isolate_cell(const Ref &ref, double t0u, double t1u, double t0v, dou
                 node_box(depth, path, lo0, w0, lo1, w1);
                 double own[N];
                 load_cell<K0, K1>(ref, own);                   // the cell's own coefficients, read again
-                restrict_box<K0, K1>(own, lo0, w0, lo1, w1, cur);
+                restrict_box<2, K0, K1>(own, lo0, w0, lo1, w1, cur);
                 live = !excluded<K0, K1>(cur);
             }
         } else if (depth == 2 * ROOTS2_DEPTH) {

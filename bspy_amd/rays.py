@@ -131,10 +131,10 @@ def frame(o, d, C):
 
 
 def form_cell(window, fr):
-    """The cell [g_1, g_2] of ``roots2`` from the window [x, y, z] (each K0 rows of K1 floats) and the ray's frame."""
+    """The cell ((K0, K1), [g_1, g_2]) of ``roots2`` from the window [x, y, z] (each K0 rows of K1 floats) and the ray's frame."""
     K0, K1 = len(window[0]), len(window[0][0])
-    return [[[w0 * (window[p][i][j] - fr.o[p]) + w1 * (window[q][i][j] - fr.o[q]) for j in range(K1)] for i in range(K0)]
-            for p, q, w0, w1 in fr.terms]
+    return (K0, K1), [[w0 * (window[p][i][j] - fr.o[p]) + w1 * (window[q][i][j] - fr.o[q]) for i in range(K0) for j in range(K1)]
+                      for p, q, w0, w1 in fr.terms]
 
 
 def box_of(window):
@@ -170,8 +170,8 @@ def slab_test(fr, box, tmin, tmax):
 
 def pair_kind(cell, S, inbox):
     """0: no pair; 1: a candidate; 2: a flat pair."""
-    for comp, scale in zip(cell, S):
-        if all(abs(x) < scale * EPS for row in comp for x in row) or scale == 0.0:
+    for comp, scale in zip(cell[1], S):
+        if all(abs(x) < scale * EPS for x in comp) or scale == 0.0:
             return 2 if inbox else 0
     return 0 if roots2.excluded(cell) else 1
 
@@ -195,7 +195,8 @@ def reduce_ray(fr, pairs, windows, breaks0, breaks1, nc1, tmin, tmax):
                             keep = False
             if not keep:
                 continue
-            value = roots2.eval2(windows[cell][fr.c], (u - t0u) / hu, (v - t0v) / hv)[0]
+            comp = windows[cell][fr.c]
+            value = roots2.eval2((len(comp), len(comp[0])), [x for row in comp for x in row], (u - t0u) / hu, (v - t0v) / hv)[0]
             t = (value - fr.o[fr.c]) / fr.d[fr.c]
             if t >= tmin and t <= tmax:
                 hits.append((u, v, t, cell))
@@ -241,9 +242,8 @@ def statement(rows, plan, cmax, origins, directions, tmin=0.0, tmax=INF, prefilt
             i, j = divmod(at, nc1)
             zeros, close, st, visited = [], [], STATUS_FLAT, 0
             if kind == 1:
-                zeros, close, st, visited = roots2.isolate_cell(formed, float(plan.breaks[0][i]), float(plan.breaks[0][i + 1]),
-                                                                float(plan.breaks[1][j]), float(plan.breaks[1][j + 1]),
-                                                                fr.S[0], fr.S[1], walk)
+                zeros, close, st, visited = roots2.isolate_cell(formed, [float(plan.breaks[0][i]), float(plan.breaks[1][j])],
+                                                                [float(plan.breaks[0][i + 1]), float(plan.breaks[1][j + 1])], fr.S, walk)
             pair_ray.append(ray)
             pair_cell.append(at)
             found.append((zeros, close))

@@ -57,18 +57,22 @@ the two paths.
 
 ``_path="device" | "host"`` (or ``roots3.FORCE_PATH``) pins the path; ``roots3.LAST_PATHS`` lists what the last call ran.
 """
-import numpy as np
+import functools
+import sys
 
+from . import _box
 from . import _cells
-from . import refinement
 from . import roots
 from ._cells import zero_cells
+
+_THIS = sys.modules[__name__]          # the family that ``_box`` and ``_cells`` are handed
 
 # Systems x cells from which the device path is taken.  Measured with tools/roots3_time.py on an MI355X (DESIGN.md section 19):
 # on candidate-dense systems the device wins from 8 cells on and by a factor 2 at 64; on sparse ones the host wins up to
 # about 7000 cells, by at most the 6 ms a device call costs whatever its size.
 DEVICE_MIN_CELLS = 64
 MIN_K, MAX_K = 2, 4
+DEVICE_MIN_K, DEVICE_MAX_K = MIN_K, MAX_K          # the kernels take every order the family does
 FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
 
@@ -92,58 +96,10 @@ def slots(K0, K1, K2):
 
 
 # ------------------------------------------------------------------------------------------ the statement
-# a cell is (dims, [component 0, 1, 2]); a component is the flat list of its K0 K1 K2 floats, the last index fastest
-def _one_sign(comp):
-    return all(x > 0.0 for x in comp) or all(x < 0.0 for x in comp)
-
-
-def excluded(cell):
-    return any(_one_sign(comp) for comp in cell[1])
-
-
-def _along(dims, comp, axis, f):
-    """f on every line of a component along ``axis``; f returns a tuple of lines -> a tuple of components."""
-    stride = [dims[1] * dims[2], dims[2], 1][axis]
-    K = dims[axis]
-    outs = None
-    for start in range(len(comp)):
-        if (start // stride) % K:
-            continue
-        res = f([comp[start + e * stride] for e in range(K)])
-        if outs is None:
-            outs = [list(comp) for _ in res]
-        for which, line in enumerate(res):
-            for e in range(len(line)):
-                outs[which][start + e * stride] = line[e]
-    return tuple(outs)
-
-
-def halve(cell, axis):
-    """(left, right) halves of a cell along ``axis``."""
-    dims, comps = cell
-    parts = [_along(dims, comp, axis, lambda line: roots.split(line, 0.5)) for comp in comps]
-    return (dims, [p[0] for p in parts]), (dims, [p[1] for p in parts])
-
-
-def restrict_box(cell, lo, w):
-    dims, comps = cell
-    out = []
-    for comp in comps:
-        for axis in range(3):
-            comp = _along(dims, comp, axis, lambda line: (roots.restrict(line, lo[axis], w[axis]),))[0]
-        out.append(comp)
-    return dims, out
-
-
-def eval1(c, x):
-    """Value and derivative of the Bernstein coefficients c at x."""
-    b = list(c)
-    K = len(b)
-    s = 1.0 - x
-    for r in range(1, K - 1):
-        for i in range(K - r):
-            b[i] = s * b[i] + x * b[i + 1]
-    return s * b[0] + x * b[1], float(K - 1) * (b[1] - b[0])
+# ``_box`` has the box and its walk for any number of axes; what is particular to three variables is the leaf.  A cell is
+# (dims, [component 0, 1, 2]); a component is the flat list of its K0 K1 K2 floats, the last index fastest.
+excluded, halve, restrict_box = _box.excluded, _box.halve, _box.restrict_box
+eval1, flag_cell, _outside = _box.eval1, _box.flag_cell, _box._outside
 
 
 def eval3(dims, comp, x):
@@ -165,25 +121,6 @@ def det3(a00, a01, a02, a10, a11, a12, a20, a21, a22):
     m1 = a10 * a22 - a12 * a20
     m2 = a10 * a21 - a11 * a20
     return (a00 * m0 - a01 * m1) + a02 * m2
-
-
-def node_box(depth, path):
-    at, w = [0, 0, 0], [1.0, 1.0, 1.0]
-    for k in range(depth):
-        bit = (path >> (depth - 1 - k)) & 1
-        at[k % 3], w[k % 3] = 2 * at[k % 3] + bit, 0.5 * w[k % 3]
-    return [float(at[a]) * w[a] for a in range(3)], w
-
-
-def flag_cell(cell, mask):
-    """What ``roots3_flag`` writes for one cell."""
-    return 0 if mask or excluded(cell) else 1
-
-
-def _outside(x, lo, w):
-    if x != x:
-        return float("inf")
-    return max(0.0, lo - x, x - (lo + w))
 
 
 def _leaf(cell, lo, t0, h, S, out, near, R):
@@ -236,124 +173,23 @@ def _leaf(cell, lo, t0, h, S, out, near, R):
     return 0
 
 
-def isolate_cell(cell, t0, t1, S, walk=None):
-    """What ``roots3_isolate`` returns for one candidate cell, in plain Python floats:
-    (zeros [(u, v, w)], near bytes, status, nodes visited)."""
-    dims, comps = cell
-    R = slots(*dims)
-    cell = (dims, [[float(x) for x in comp] for comp in comps])
-    h = [t1[a] - t0[a] for a in range(3)]
-    out, near = [], []
-    cur, depth, path = cell, 0, 0
-    live, done = True, False
-    status = nodes = 0
-    for _ in range(WALK if walk is None else walk):
-        nodes += 1
-        if not live:
-            while path & 1:
-                path >>= 1
-                depth -= 1
-            if depth == 0:
-                done = True
-                break
-            path |= 1
-            cur = restrict_box(cell, *node_box(depth, path))
-            live = not excluded(cur)
-        elif depth == 3 * DEPTH:
-            status |= _leaf(cell, node_box(depth, path)[0], t0, h, S, out, near, R)
-            live = False
-        else:
-            left, right = halve(cur, depth % 3)
-            if not excluded(left):
-                cur, path, depth = left, path << 1, depth + 1
-            elif not excluded(right):
-                cur, path, depth = right, (path << 1) | 1, depth + 1
-            else:
-                live = False
-    if not done:
-        status |= STATUS_WALK
-    return out, near, status, nodes
-
-
-def merge_keep(found, flags, cand, breaks):
-    """The keep bytes of ``roots3_merge`` in Python: found = the (zeros, near) pairs of the candidates, in their order."""
-    nsys, nc0, nc1, nc2 = flags.shape
-    slot_of = {int(at): n for n, at in enumerate(cand)}
-    before = [(di, dj, dk) for di in (-1, 0, 1) for dj in (-1, 0, 1) for dk in (-1, 0, 1)][:13]
-    keep = []
-    for n, (zeros, near) in enumerate(found):
-        b, cell = divmod(int(cand[n]), nc0 * nc1 * nc2)
-        ijk = (cell // (nc1 * nc2), (cell // nc2) % nc1, cell % nc2)
-        tol = [SAME * (float(breaks[a][ijk[a] + 1]) - float(breaks[a][ijk[a]])) for a in range(3)]
-        row = []
-        for z, close in zip(zeros, near):
-            k = 1
-            if close:
-                for delta in before:
-                    ni, nj, nk = (ijk[a] + delta[a] for a in range(3))
-                    if min(ni, nj, nk) < 0 or ni >= nc0 or nj >= nc1 or nk >= nc2 or not flags[b, ni, nj, nk]:
-                        continue
-                    for other in found[slot_of[((b * nc0 + ni) * nc1 + nj) * nc2 + nk]][0]:
-                        if all(abs(other[a] - z[a]) <= tol[a] for a in range(3)):
-                            k = 0
-            row.append(k)
-        keep.append(row)
-    return keep
-
-
-def statement(rows, plan, mask, scale, walk=None):
-    """flags, candidates, zeros (NaN padded), near, count, status, nodes and keep of the extracted rows (B, 3, R0, R1, R2),
-    from the functions above: what the host drivers and the kernels return, bit for bit."""
-    K0, K1, K2 = plan.order
-    R = slots(K0, K1, K2)
-    B, nc0, nc1, nc2 = mask.shape
-    f0, f1, f2 = plan.first
-
-    def cell_of(b, i, j, k):
-        return plan.order, [[float(x) for x in rows[b, d, f0[i]:f0[i] + K0, f1[j]:f1[j] + K1, f2[k]:f2[k] + K2].reshape(-1)]
-                            for d in range(3)]
-
-    def where(at):
-        b, cell = divmod(int(at), nc0 * nc1 * nc2)
-        return b, cell // (nc1 * nc2), (cell // nc2) % nc1, cell % nc2
-
-    flags = np.zeros(mask.shape, np.uint8)
-    for at in range(mask.size):
-        flags[where(at)] = flag_cell(cell_of(*where(at)), int(mask[where(at)]))
-    cand = np.flatnonzero(flags).astype(np.int64)
-    out = np.full((len(cand), R, 3), np.nan)
-    near = np.zeros((len(cand), R), np.uint8)
-    count, status, nodes = np.zeros(len(cand), np.int32), np.zeros(len(cand), np.uint8), np.zeros(len(cand), np.int32)
-    found = []
-    for n, at in enumerate(cand):
-        b, i, j, k = where(at)
-        t0 = [float(plan.breaks[a][c]) for a, c in enumerate((i, j, k))]
-        t1 = [float(plan.breaks[a][c + 1]) for a, c in enumerate((i, j, k))]
-        zeros, close, status[n], nodes[n] = isolate_cell(cell_of(b, i, j, k), t0, t1, [float(s) for s in scale[b]], walk)
-        found.append((zeros, close))
-        count[n] = len(zeros)
-        out[n, :len(zeros)] = np.array(zeros).reshape(-1, 3)
-        near[n, :len(zeros)] = close
-    keep = np.zeros((len(cand), R), np.uint8)
-    for n, row in enumerate(merge_keep(found, flags, cand, plan.breaks)):
-        keep[n, :len(row)] = row
-    return dict(flags=flags, cand=cand, roots=out, near=near, count=count, status=status, nodes=nodes, keep=keep)
+# (zeros [(u, v, w)], near bytes, status, nodes visited) of one candidate cell on [t0, t1] with the scales S, the keep bytes
+# of the candidates' (zeros, near) pairs, and all that the host drivers and the kernels return for extracted rows, bit for bit
+isolate_cell = functools.partial(_box.isolate_cell, _THIS)          # (cell, t0, t1, S, walk=None): what ``roots3_isolate`` returns
+merge_keep = functools.partial(_box.merge_keep, same=SAME)          # (found, flags, cand, breaks): what ``roots3_merge`` writes
+statement = functools.partial(_box.statement, _THIS)                # (rows, plan, mask, scale, walk=None) -> dict
 
 
 # ------------------------------------------------------------------------------------------ plans and launches
 Plan3 = _cells.TensorPlan          # one ``roots.BezierPlan`` per axis; the band steps on the axes 1, 2 and 3 of (M, n0, n1, n2)
+NIND, WORD, PREFIX = 3, "three", "bsk_roots3"
 
 
-def extract_host(data, plan):
-    """NumPy (M, n0, n1, n2) float64 -> (M, R0, R1, R2) in Bezier form (``_cells.band_host``)."""
-    return _cells.band_host(data, plan.steps, LAST_PATHS)
-
-
-def _run_host(rows, plan, mask, scale):
-    """rows: NumPy float64 (B, 3, R0, R1, R2) in Bezier form; mask: uint8 (B, nc0, nc1, nc2); scale: float64 (B, 3).
-    -> dict of flags, cand, roots (ncand, R, 3), near, count, status, nodes, keep (``_cells.isolate_cells``)."""
-    rows, scale = np.ascontiguousarray(rows, np.float64), np.ascontiguousarray(scale, np.float64)
-    return _cells.isolate_cells(_cells.Host(), "bsk_roots3", rows, plan, mask, scale, slots(*plan.order), LAST_PATHS)
+# rows: NumPy float64 (B, 3, R0, R1, R2) in Bezier form; mask: uint8 (B, *ncells); scale: float64 (B, 3).  -> dict of flags, cand,
+# roots (ncand, R, 3), near, count, status, nodes, keep (``_cells.isolate_cells``)
+_run_host = functools.partial(_cells.run_host, _THIS)
+# (spline, coefs=None) -> the host path's tables of a system: (plan, rows, mask (B, *ncells), scale (B, 3)), all NumPy
+tables = functools.partial(_cells.tables, _THIS)
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -362,21 +198,6 @@ def _check_spline(spline):
         raise NotImplementedError("zeros3: three independent variables only (curves: Spline.zeros, two variables: Spline.zeros2)")
     if min(spline.order) < MIN_K or max(spline.order) > MAX_K:
         raise NotImplementedError(f"zeros3: orders from {MIN_K} to {MAX_K} (one wave holds the 64 coefficients of a cell)")
-
-
-def tables(spline, coefs=None):
-    """The host path's tables of a system: (plan, rows (B, 3, R0, R1, R2), mask (B, nc0, nc1, nc2), scale (B, 3)), all NumPy."""
-    plan = Plan3(spline.order, spline.knots)
-    data = np.asarray(spline.coefs if coefs is None else coefs)
-    data = data.reshape((-1, 3) + data.shape[-3:]).astype(np.float64)            # float32 is widened BEFORE the extraction
-    wide = np.abs(data)
-    scale = np.ascontiguousarray(wide.max(axis=(2, 3, 4)))
-    small = (wide < (scale * EPS)[:, :, None, None, None]) | (scale == 0.0)[:, :, None, None, None]
-    mask = zero_cells(small, plan).astype(np.uint8)
-    rows = data
-    if plan.steps:
-        rows = extract_host(data.reshape((-1,) + data.shape[2:]), plan).reshape(data.shape[:2] + tuple(plan.rowlen))
-    return plan, rows, mask, scale
 
 
 def zeros3_batch(spline, coefs=None, _path=None):
@@ -390,74 +211,10 @@ def zeros3_batch(spline, coefs=None, _path=None):
     The zero cells are found on the host: the comparison |coefficient| < S_d eps runs on the device, its result (one
     byte per coefficient, 3 B n0 n1 n2 bytes) is read back and the windowed sums over the cells are NumPy's
     (``zero_cells``), as in roots2.  The coefficients themselves, the extracted rows and the zeros stay on the device."""
-    del LAST_PATHS[:]
-    path = _cells.pick_path(_path, FORCE_PATH)
-    _check_spline(spline)
-    K = tuple(int(k) for k in spline.order)
-    n0, n1, n2 = (len(spline.knots[d]) - spline.order[d] for d in range(3))
-    on_device = coefs is not None and _cells.is_torch(coefs)
-    if coefs is None:
-        if spline.nDep != 3:
-            raise ValueError("zeros3_batch takes three dependent variables, or coefs (B, 3, n0, n1, n2)")
-        coefs = spline.coefs[None]
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("zeros3_batch takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != 5 or tuple(coefs.shape[1:]) != (3, n0, n1, n2):
-        raise ValueError(f"coefs must have the shape (B, 3, {n0}, {n1}, {n2})")
-    B = int(coefs.shape[0])
-    plan = Plan3(spline.order, spline.knots)
-    ncell = int(np.prod(plan.ncells))
-    kdtype = np.result_type(*(spline.knots[d].dtype for d in range(3)))
-    if path is None:
-        path = "device" if B * ncell >= DEVICE_MIN_CELLS else "host"
-
-    if B == 0:
-        return _cells.collect(_cells.Device(coefs.device) if on_device else _cells.Host(), plan, kdtype, 0)
-
-    if path == "device":
-        import torch
-        data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        be = _cells.Device(data.device)
-        wide = data.abs()
-        scale = wide.amax(dim=(2, 3, 4)).contiguous()
-        small = ((wide < (scale * EPS)[:, :, None, None, None]) | (scale == 0.0)[:, :, None, None, None]).cpu().numpy()
-        mask = zero_cells(small, plan).astype(np.uint8)
-        rows = data.reshape((3 * B, n0, n1, n2))
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            LAST_PATHS.extend(ran)
-        res = _cells.isolate_cells(be, "bsk_roots3", rows.contiguous(), plan, mask, scale, slots(*K), LAST_PATHS)
-    else:
-        be = _cells.Host()
-        _, rows, mask, scale = tables(spline, coefs)
-        res = _run_host(rows, plan, mask, scale)             # makes rows and scale contiguous
-    return _cells.collect(be, plan, kdtype, B, slots(*K), res, mask, numpy_out=not on_device)
+    return _cells.zeros_batch(_THIS, spline, coefs, _path)
 
 
 def zeros3(self, _path=None):
     """``Spline.zeros3``: a list, sorted by (u, v, w), of length-3 arrays (u, v, w) in the knots' dtype for isolated zeros and
     of ((u0, v0, w0), (u1, v1, w1)) tuples for cells on which a component vanishes."""
-    if not (self.nInd == self.nDep):
-        raise ValueError("The number of independent variables (nInd) must match the number of dependent variables (nDep).")
-    _check_spline(self)
-    values, _, cells, status = zeros3_batch(self, _path=_path)
-    if status.any():
-        _, i, j, k = (int(x) for x in np.argwhere(status)[0])
-        bits = int(status[0, i, j, k])
-        u, v, w = Plan3(self.order, self.knots).breaks
-        why = ", ".join(text for bit, text in STATUS_TEXT.items() if bits & bit)
-        raise ValueError(f"zeros3: {why} in the cell [{float(u[i])}, {float(u[i + 1])}] x [{float(v[j])}, {float(v[j + 1])}] x "
-                         f"[{float(w[k])}, {float(w[k + 1])}]")
-    kdtype = values.dtype
-    found = [(tuple(float(x) for x in r), r) for r in values]
-    for _, u0, u1, v0, v1, w0, w1 in cells.astype(kdtype):
-        found.append(((float(u0), float(v0), float(w0)), ((u0, v0, w0), (u1, v1, w1))))
-    found.sort(key=lambda item: item[0])
-    return [item[1] for item in found]
+    return _cells.zeros(_THIS, self, _path)

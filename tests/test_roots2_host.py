@@ -298,12 +298,12 @@ def test_the_halving_never_flips_a_hull():
     rng = np.random.default_rng(5)
     for K0, K1 in ((2, 2), (3, 4), (4, 4), (6, 5)):
         for _ in range(100):
-            cell = [[[abs(float(x)) + 1e-300 for x in row] for row in rng.standard_normal((K0, K1)) * 10.0 ** rng.integers(-8, 8)]
-                    for _ in range(2)]
+            cell = (K0, K1), [[abs(float(x)) + 1e-300 for x in (rng.standard_normal((K0, K1)) * 10.0 ** rng.integers(-8, 8)).reshape(-1)]
+                              for _ in range(2)]
             for axis in (0, 1):
                 for part in roots2.halve(cell, axis):
                     assert roots2.excluded(part)
-            assert roots2.restrict_box(cell, 0.0, 1.0, 0.0, 1.0) == cell           # exact on the whole cell
+            assert roots2.restrict_box(cell, [0.0, 0.0], [1.0, 1.0]) == cell       # exact on the whole cell
 
 
 # ------------------------------------------------------------------------------------------ the library's own uses
