@@ -1,7 +1,9 @@
 """
 What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``, ``rays``, ``surfaces``) share, written
-once: the host band loop, the per-axis Bezier plan, the zero-cell table, and ``zeros2_batch`` / ``zeros3_batch`` whole, on
-the two backends of bspy_amd/_backend.py (``Host``, ``Device``, the path switch: passed on under their names here).
+once: the host band loop, the per-axis Bezier plan (``JumpFreePlan``: the one of ``contours`` and ``surfaces``, which refuses
+a jump), the zero-cell table, and ``zeros2_batch`` / ``zeros3_batch`` whole, on the two backends of bspy_amd/_backend.py
+(``Host``, ``Device``, the path switch: passed on under their names here).  The layer that ``rays`` and ``surfaces`` put on
+top, one surface's tables and the passes of the pair search, is written once in bspy_amd/_pairs.py.
 
 A driver is a function of a backend: it allocates with ``be.empty``, hands ``be.ptr(a)`` to ``be.call(name, ...)`` and uses
 the backend's few array operations.  The families differ in their kernels and in the plain-Python statement that says what a
@@ -85,6 +87,22 @@ class TensorPlan:
         self.first = [p.first for p in self.axes]
         self.rowlen = [p.rowlen for p in self.axes]
         self.ncells = [p.nspans for p in self.axes]
+
+
+class JumpFreePlan(TensorPlan):
+    """``TensorPlan`` of two variables that refuses a jump: an interior knot of multiplicity >= K.  A subclass sets ``who``,
+    the caller's name, and ``what``, the thing that cannot cross the knot (``contours``: a contour; ``surfaces``: a curve)."""
+    who = what = None
+
+    def __init__(self, order, knots):
+        for d in range(2):
+            k, t = int(order[d]), np.asarray(knots[d])
+            values, counts = np.unique(t, return_counts=True)
+            inside = (values > t[k - 1]) & (values < t[len(t) - k]) & (counts >= k)
+            if inside.any():
+                raise ValueError(f"{self.who}: the knot {float(values[inside][0])} of variable {d} has multiplicity {int(counts[inside][0])}"
+                                 f" >= order {k} (a jump: no {self.what} crosses it; trim the spline there)")
+        super().__init__(order, knots)
 
 
 def zero_cells(small, plan):

@@ -390,18 +390,9 @@ def _run_host(rows, plan, levels, scale, depth, split):
 
 
 # ------------------------------------------------------------------------------------------ public
-class Plan(_cells.TensorPlan):
+class Plan(_cells.JumpFreePlan):
     """``_cells.TensorPlan`` that refuses a jump: an interior knot of multiplicity >= K."""
-
-    def __init__(self, order, knots):
-        for d in range(2):
-            k, t = int(order[d]), np.asarray(knots[d])
-            values, counts = np.unique(t, return_counts=True)
-            inside = (values > t[k - 1]) & (values < t[len(t) - k]) & (counts >= k)
-            if inside.any():
-                raise ValueError(f"contours: the knot {float(values[inside][0])} of variable {d} has multiplicity {int(counts[inside][0])}"
-                                 f" >= order {k} (a jump: no contour crosses it; trim the spline there)")
-        super().__init__(order, knots)
+    who, what = "contours", "contour"
 
 
 def _check_spline(spline):
@@ -514,12 +505,12 @@ def trace_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=
     return vertices, offsets, closed, comp_field, cells, status
 
 
-def fit_polyline(points, tolerance=None, closed=False):
-    """One polyline (n, 2) -> a Spline curve (nInd 1, nDep 2) on [0, 1]: normalised chord length, order 4.  ``closed``: the
-    last coefficient is set to the first one, so that the end points of the curve are equal to the bit."""
+def fit_chords(points, step, groups, tolerance=None, closed=False):
+    """The points (n, m) of one polyline and the lengths ``step`` (n - 1) of its chords -> one Spline curve (nInd 1, on
+    [0, 1], order 4) per group of columns (``groups``: slices), all fitted to the same normalised chord-length parameters.
+    Points behind a chord of length 0 are dropped; ``closed``: the last coefficient is set to the first one, so that the
+    end points of the curve are equal to the bit."""
     from .spline import Spline
-    points = np.asarray(points, np.float64)
-    step = np.hypot(*np.diff(points, axis=0).T) if len(points) > 1 else np.zeros(0)
     keep = np.concatenate(([True], step > 0.0))
     points = points[keep]
     if len(points) < 2:
@@ -532,12 +523,22 @@ def fit_polyline(points, tolerance=None, closed=False):
         if np.any(np.diff(t) <= 0.0):                      # chords below the resolution of [0, 1]: index them instead
             t = np.linspace(0.0, 1.0, len(points))
     order = min(4, len(points))
-    curve = Spline.least_squares(t, points.T.copy(), order=[order], tolerance=tolerance)
-    if closed:
-        coefs = np.array(curve.coefs)
-        coefs[:, -1] = coefs[:, 0]
-        curve = Spline(1, 2, curve.order, curve.nCoef, curve.knots, coefs)
-    return curve
+    curves = []
+    for cols in groups:
+        curve = Spline.least_squares(t, points[:, cols].T.copy(), order=[order], tolerance=tolerance)
+        if closed:
+            coefs = np.array(curve.coefs)
+            coefs[:, -1] = coefs[:, 0]
+            curve = Spline(1, curve.nDep, curve.order, curve.nCoef, curve.knots, coefs)
+        curves.append(curve)
+    return curves
+
+
+def fit_polyline(points, tolerance=None, closed=False):
+    """One polyline (n, 2) -> a Spline curve (nInd 1, nDep 2) on [0, 1]: normalised chord length, order 4 (``fit_chords``)."""
+    points = np.asarray(points, np.float64)
+    step = np.hypot(*np.diff(points, axis=0).T) if len(points) > 1 else np.zeros(0)
+    return fit_chords(points, step, [slice(None)], tolerance, closed)[0]
 
 
 def contours(self, tolerance=None, depth=None, _path=None):

@@ -39,6 +39,7 @@
 #include <cstdint>
 
 #define BSK_ROOTS2_FUNCTIONS_ONLY
+#include "bsk_pairs.hpp"
 #include "bsk_roots2.hpp"
 
 #pragma clang fp contract(off)
@@ -75,6 +76,8 @@ BSK_HD void load_cell(const RayCell &rc, double *c)
 
 namespace bskrays {
 
+using bskpairs::Surface;                            // the tables of a launch (bsk_pairs.hpp); K0, K1 are template constants here
+using bskpairs::window;
 using bskroots2::RayCell;
 using bskroots2::ROOTS2_EPS;
 using bskroots2::ROOTS2_SAME;
@@ -84,13 +87,6 @@ constexpr int RAYS_BLOCK = 256;                     // ray_boxes, ray_search, ra
 constexpr int RAYS_ISOLATE_BLOCK = 64;              // one wave: the walk may use the whole register file
 constexpr unsigned STATUS_SKIPPED = 8, STATUS_FLAT = 16;
 constexpr double RAYS_TINY = 0x1p-1070;
-
-// The tables of a launch.  rows: [3, R0, R1]; first0: [nc0]; first1: [nc1].
-struct Surface {
-    const double *rows;
-    long long R0, R1, nc0, nc1;
-    const int32_t *first0, *first1;
-};
 
 // origins, dirs: [3, nrays]; cmax: [3]
 struct Rays {
@@ -154,25 +150,12 @@ BSK_HD RayCell ray_cell(const Frame &f, const double *p, long long sd, long long
     return rc;
 }
 
-// the window of cell (i, j); false: it leaves the rows
-template <int K0, int K1>
-BSK_HD bool window(const Surface &s, long long cell, const double *&p, long long &i, long long &j)
-{
-    if (cell < 0 || cell >= s.nc0 * s.nc1) return false;
-    i = cell / s.nc1;
-    j = cell - i * s.nc1;
-    const long long f0 = s.first0[i], f1 = s.first1[j];
-    if (f0 < 0 || f0 + K0 > s.R0 || f1 < 0 || f1 + K1 > s.R1) return false;
-    p = s.rows + f0 * s.R1 + f1;
-    return true;
-}
-
 template <int K0, int K1>
 BSK_HD void boxes_lane(const Surface &s, long long cell, double *boxes)
 {
     const double *p;
     long long i, j;
-    const bool ok = window<K0, K1>(s, cell, p, i, j);
+    const bool ok = window(s, K0, K1, cell, p, i, j);
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
         double lo = __builtin_inf(), hi = -__builtin_inf();      // no window: lo > hi; search_lane drops the pair by the same window test
@@ -264,7 +247,7 @@ BSK_HD void search_lane(const Surface &s, const Rays &r, const Search &a, long l
             if (PREFILTER && !inbox) continue;
             const double *p;
             long long i, j;
-            if (!window<K0, K1>(s, cell, p, i, j)) continue;
+            if (!window(s, K0, K1, cell, p, i, j)) continue;
             const RayCell rc = ray_cell(f, p, s.R0 * s.R1, s.R1);
             if (pair_kind<K0, K1>(rc, f.S1, f.S2, inbox) == 0) continue;
             if (EMIT && base + n >= 0 && base + n < a.npairs) {
@@ -300,7 +283,7 @@ BSK_HD void isolate_lane(const Surface &s, const Rays &r, const Isolate &a, long
     const long long ray = a.pair_ray[lane];
     const double *p = nullptr;
     long long i = 0, j = 0;
-    bool walk = ray >= 0 && ray < r.nrays && window<K0, K1>(s, a.pair_cell[lane], p, i, j);
+    bool walk = ray >= 0 && ray < r.nrays && window(s, K0, K1, a.pair_cell[lane], p, i, j);
     unsigned status = 0;
     if (walk) {
         const Frame f = make_frame(r, ray);
@@ -362,7 +345,7 @@ BSK_HD void reduce_lane(const Surface &s, const Rays &r, const Reduce &a, long l
         const double *w;
         long long i, j;
         const long long cell = a.pair_cell[p];
-        if (!window<K0, K1>(s, cell, w, i, j)) continue;
+        if (!window(s, K0, K1, cell, w, i, j)) continue;
         const double t0u = a.breaks0[i], t0v = a.breaks1[j];
         const double hu = a.breaks0[i + 1] - t0u, hv = a.breaks1[j + 1] - t0v;
         const double tolu = ROOTS2_SAME * hu, tolv = ROOTS2_SAME * hv;

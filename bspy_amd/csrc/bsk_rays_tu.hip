@@ -13,23 +13,6 @@ static thread_local const char *g_rays_kernel = "";
 
 constexpr int RAYS_MAX_K = 4;
 
-struct RaysCall {
-    int K0, K1;
-    Surface s;
-};
-
-static bsk_status check_surface(const RaysCall &c, const std::string &w)
-{
-    if (!c.s.rows || !c.s.first0 || !c.s.first1) return fail(BSK_ERR_INVALID, w + ": NULL argument");
-    if (c.K0 < 2 || c.K1 < 2) return fail(BSK_ERR_INVALID, w + ": orders must be >= 2");
-    if (c.K0 > RAYS_MAX_K || c.K1 > RAYS_MAX_K) return fail(BSK_ERR_UNSUPPORTED, w + ": order above " + std::to_string(RAYS_MAX_K));
-    if (c.s.nc0 < 1 || c.s.nc1 < 1) return fail(BSK_ERR_INVALID, w + ": nc0 and nc1 must be >= 1");
-    if (c.s.R0 < c.K0 || c.s.R1 < c.K1) return fail(BSK_ERR_INVALID, w + ": the rows must hold one cell (R0 >= K0, R1 >= K1)");
-    if ((double)c.s.nc0 * (double)c.s.nc1 > 2.0e9 || 3.0 * (double)c.s.R0 * (double)c.s.R1 > 9.0e15)
-        return fail(BSK_ERR_INVALID, w + ": array too large");
-    return BSK_OK;
-}
-
 static bsk_status check_rays(const Rays &r, const std::string &w)
 {
     if (!r.origins || !r.dirs || !r.cmax) return fail(BSK_ERR_INVALID, w + ": NULL argument");
@@ -38,26 +21,26 @@ static bsk_status check_rays(const Rays &r, const std::string &w)
 }
 
 template <typename F>
-static bsk_status by_orders(const RaysCall &c, F &&f)
+static bsk_status by_orders(const Surface &s, F &&f)
 {
-    return with_range<2, RAYS_MAX_K>(c.K0, [&](auto k0) {
-        return with_range<2, RAYS_MAX_K>(c.K1, [&](auto k1) { return f(k0, k1); });
+    return with_range<2, RAYS_MAX_K>(s.K0, [&](auto k0) {
+        return with_range<2, RAYS_MAX_K>(s.K1, [&](auto k1) { return f(k0, k1); });
     });
 }
 
 template <bool DEVICE>
-static bsk_status boxes_of(const RaysCall &c, double *out, hipStream_t st)
+static bsk_status boxes_of(const Surface &c, double *out, hipStream_t st)
 {
     const std::string who = DEVICE ? "bsk_rays_boxes" : "bsk_rays_boxes_host";
-    bsk_status s = check_surface(c, who);
+    bsk_status s = bskpairs::check_surface(c, RAYS_MAX_K, who);
     if (s != BSK_OK) return s;
     if (!out) return fail(BSK_ERR_INVALID, who + ": NULL argument");
-    const long long lanes = c.s.nc0 * c.s.nc1;
+    const long long lanes = c.nc0 * c.nc1;
     s = by_orders(c, [&](auto k0, auto k1) {
         constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value;
-        if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_boxes<K0, K1>, lanes, st, c.s, out);
+        if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_boxes<K0, K1>, lanes, st, c, out);
         else {
-            for (long long cell = 0; cell < lanes; ++cell) boxes_lane<K0, K1>(c.s, cell, out);
+            for (long long cell = 0; cell < lanes; ++cell) boxes_lane<K0, K1>(c, cell, out);
             return BSK_OK;
         }
     });
@@ -66,28 +49,25 @@ static bsk_status boxes_of(const RaysCall &c, double *out, hipStream_t st)
 }
 
 template <bool DEVICE, bool EMIT>
-static bsk_status search(const RaysCall &c, const Rays &r, Search a, int prefilter, hipStream_t st)
+static bsk_status search(const Surface &c, const Rays &r, Search a, int prefilter, hipStream_t st)
 {
     const std::string who = std::string(EMIT ? "bsk_rays_emit" : "bsk_rays_count") + (DEVICE ? "" : "_host");
-    bsk_status s = check_surface(c, who);
+    bsk_status s = bskpairs::check_surface(c, RAYS_MAX_K, who);
     if (s != BSK_OK) return s;
     s = check_rays(r, who);
     if (s != BSK_OK) return s;
     if (!a.boxes || (EMIT ? (!a.offset || !a.pair_ray || !a.pair_cell) : (!a.partial || !a.skipped)))
         return fail(BSK_ERR_INVALID, who + ": NULL argument");
-    if (a.chunk < 1) return fail(BSK_ERR_INVALID, who + ": chunk must be >= 1");
-    if (EMIT && a.npairs < 1) return fail(BSK_ERR_INVALID, who + ": npairs must be >= 1 (no pairs: no call)");
-    const long long ncell = c.s.nc0 * c.s.nc1;
-    a.nchunks = (ncell + a.chunk - 1) / a.chunk;
-    if (a.nchunks > 65535) return fail(BSK_ERR_INVALID, who + ": more than 65535 chunks");
+    s = bskpairs::check_search(c, a.chunk, EMIT, a.npairs, a.nchunks, who);
+    if (s != BSK_OK) return s;
     s = by_orders(c, [&](auto k0, auto k1) {
         constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value;
         return with_bool(prefilter != 0, [&](auto pf) {
             constexpr bool PF = decltype(pf)::value;
-            if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_search<K0, K1, PF, EMIT>, r.nrays, a.nchunks, st, c.s, r, a);
+            if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_search<K0, K1, PF, EMIT>, r.nrays, a.nchunks, st, c, r, a);
             else {
                 for (long long ch = 0; ch < a.nchunks; ++ch)
-                    for (long long ray = 0; ray < r.nrays; ++ray) search_lane<K0, K1, PF, EMIT>(c.s, r, a, ch, ray);
+                    for (long long ray = 0; ray < r.nrays; ++ray) search_lane<K0, K1, PF, EMIT>(c, r, a, ch, ray);
                 return BSK_OK;
             }
         });
@@ -97,10 +77,10 @@ static bsk_status search(const RaysCall &c, const Rays &r, Search a, int prefilt
 }
 
 template <bool DEVICE>
-static bsk_status isolate(const RaysCall &c, const Rays &r, const Isolate &a, hipStream_t st)
+static bsk_status isolate(const Surface &c, const Rays &r, const Isolate &a, hipStream_t st)
 {
     const std::string who = DEVICE ? "bsk_rays_isolate" : "bsk_rays_isolate_host";
-    bsk_status s = check_surface(c, who);
+    bsk_status s = bskpairs::check_surface(c, RAYS_MAX_K, who);
     if (s != BSK_OK) return s;
     s = check_rays(r, who);
     if (s != BSK_OK) return s;
@@ -109,9 +89,9 @@ static bsk_status isolate(const RaysCall &c, const Rays &r, const Isolate &a, hi
     if (a.npairs < 1) return fail(BSK_ERR_INVALID, who + ": npairs must be >= 1 (no pairs: no call)");
     s = by_orders(c, [&](auto k0, auto k1) {
         constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value;
-        if constexpr (DEVICE) return launch_lanes<RAYS_ISOLATE_BLOCK>(ray_isolate<K0, K1>, a.npairs, st, c.s, r, a);
+        if constexpr (DEVICE) return launch_lanes<RAYS_ISOLATE_BLOCK>(ray_isolate<K0, K1>, a.npairs, st, c, r, a);
         else {
-            for (long long lane = 0; lane < a.npairs; ++lane) isolate_lane<K0, K1>(c.s, r, a, lane);
+            for (long long lane = 0; lane < a.npairs; ++lane) isolate_lane<K0, K1>(c, r, a, lane);
             return BSK_OK;
         }
     });
@@ -120,10 +100,10 @@ static bsk_status isolate(const RaysCall &c, const Rays &r, const Isolate &a, hi
 }
 
 template <bool DEVICE>
-static bsk_status reduce(const RaysCall &c, const Rays &r, const Reduce &a, int all, hipStream_t st)
+static bsk_status reduce(const Surface &c, const Rays &r, const Reduce &a, int all, hipStream_t st)
 {
     const std::string who = DEVICE ? "bsk_rays_reduce" : "bsk_rays_reduce_host";
-    bsk_status s = check_surface(c, who);
+    bsk_status s = bskpairs::check_surface(c, RAYS_MAX_K, who);
     if (s != BSK_OK) return s;
     s = check_rays(r, who);
     if (s != BSK_OK) return s;
@@ -136,9 +116,9 @@ static bsk_status reduce(const RaysCall &c, const Rays &r, const Reduce &a, int 
         constexpr int K0 = decltype(k0)::value, K1 = decltype(k1)::value;
         return with_bool(all != 0, [&](auto every) {
             constexpr bool ALL = decltype(every)::value;
-            if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_reduce<K0, K1, ALL>, r.nrays, st, c.s, r, a);
+            if constexpr (DEVICE) return launch_lanes<RAYS_BLOCK>(ray_reduce<K0, K1, ALL>, r.nrays, st, c, r, a);
             else {
-                for (long long ray = 0; ray < r.nrays; ++ray) reduce_lane<K0, K1, ALL>(c.s, r, a, ray);
+                for (long long ray = 0; ray < r.nrays; ++ray) reduce_lane<K0, K1, ALL>(c, r, a, ray);
                 return BSK_OK;
             }
         });
@@ -153,7 +133,7 @@ extern "C" bsk_status bsk_rays_boxes_host(int K0, int K1, const double *rows, in
                                           const int32_t *first0, const int32_t *first1,
                                           double *boxes)
 {
-    return boxes_of<false>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, boxes, nullptr);
+    return boxes_of<false>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, boxes, nullptr);
 }
 
 extern "C" bsk_status bsk_rays_boxes(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
@@ -161,7 +141,7 @@ extern "C" bsk_status bsk_rays_boxes(int K0, int K1, const double *rows, int64_t
                                      double *boxes,
                                      void *stream)
 {
-    return boxes_of<true>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, boxes, static_cast<hipStream_t>(stream));
+    return boxes_of<true>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, boxes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" bsk_status bsk_rays_count_host(int K0, int K1, const double *rows, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,
@@ -170,7 +150,7 @@ extern "C" bsk_status bsk_rays_count_host(int K0, int K1, const double *rows, in
                                           double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
                                           int32_t *partial, uint8_t *skipped)
 {
-    return search<false, false>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return search<false, false>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                                 Search{tmin, tmax, chunk, 0, boxes, partial, skipped, nullptr, nullptr, nullptr, 0}, prefilter, nullptr);
 }
 
@@ -181,7 +161,7 @@ extern "C" bsk_status bsk_rays_count(int K0, int K1, const double *rows, int64_t
                                      int32_t *partial, uint8_t *skipped,
                                      void *stream)
 {
-    return search<true, false>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return search<true, false>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                                Search{tmin, tmax, chunk, 0, boxes, partial, skipped, nullptr, nullptr, nullptr, 0}, prefilter, static_cast<hipStream_t>(stream));
 }
 
@@ -191,7 +171,7 @@ extern "C" bsk_status bsk_rays_emit_host(int K0, int K1, const double *rows, int
                                          double tmin, double tmax, int64_t chunk, int prefilter, const double *boxes,
                                          const int64_t *offset, int32_t *pair_ray, int32_t *pair_cell, int64_t npairs)
 {
-    return search<false, true>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return search<false, true>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                                Search{tmin, tmax, chunk, 0, boxes, nullptr, nullptr, offset, pair_ray, pair_cell, npairs}, prefilter, nullptr);
 }
 
@@ -202,7 +182,7 @@ extern "C" bsk_status bsk_rays_emit(int K0, int K1, const double *rows, int64_t 
                                     const int64_t *offset, int32_t *pair_ray, int32_t *pair_cell, int64_t npairs,
                                     void *stream)
 {
-    return search<true, true>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return search<true, true>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                               Search{tmin, tmax, chunk, 0, boxes, nullptr, nullptr, offset, pair_ray, pair_cell, npairs}, prefilter, static_cast<hipStream_t>(stream));
 }
 
@@ -213,7 +193,7 @@ extern "C" bsk_status bsk_rays_isolate_host(int K0, int K1, const double *rows, 
                                             const int32_t *pair_ray, const int32_t *pair_cell, int64_t npairs, double *roots, uint8_t *near,
                                             int32_t *count, uint8_t *status, int32_t *nodes)
 {
-    return isolate<false>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return isolate<false>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                           Isolate{breaks0, breaks1, pair_ray, pair_cell, npairs, roots, near, count, status, nodes}, nullptr);
 }
 
@@ -225,7 +205,7 @@ extern "C" bsk_status bsk_rays_isolate(int K0, int K1, const double *rows, int64
                                        int32_t *count, uint8_t *status, int32_t *nodes,
                                        void *stream)
 {
-    return isolate<true>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return isolate<true>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                          Isolate{breaks0, breaks1, pair_ray, pair_cell, npairs, roots, near, count, status, nodes}, static_cast<hipStream_t>(stream));
 }
 
@@ -238,7 +218,7 @@ extern "C" bsk_status bsk_rays_reduce_host(int K0, int K1, const double *rows, i
                                            const uint8_t *skipped, int all, const int64_t *hit_off, int64_t nhits, double *uv, double *t,
                                            int32_t *cell, int32_t *hits, uint8_t *status)
 {
-    return reduce<false>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return reduce<false>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                          Reduce{breaks0, breaks1, tmin, tmax, pstart, pair_cell, npairs, roots, near, count, pstatus, skipped, hit_off, nhits, uv, t, cell,
                                  hits, status}, all, nullptr);
 }
@@ -253,7 +233,7 @@ extern "C" bsk_status bsk_rays_reduce(int K0, int K1, const double *rows, int64_
                                       int32_t *cell, int32_t *hits, uint8_t *status,
                                       void *stream)
 {
-    return reduce<true>(RaysCall{K0, K1, Surface{rows, R0, R1, nc0, nc1, first0, first1}}, Rays{origins, dirs, cmax, nrays},
+    return reduce<true>(Surface{K0, K1, rows, R0, R1, nc0, nc1, first0, first1}, Rays{origins, dirs, cmax, nrays},
                         Reduce{breaks0, breaks1, tmin, tmax, pstart, pair_cell, npairs, roots, near, count, pstatus, skipped, hit_off, nhits, uv, t, cell,
                                  hits, status}, all, static_cast<hipStream_t>(stream));
 }

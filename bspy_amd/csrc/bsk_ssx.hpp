@@ -39,12 +39,15 @@
 #include <cstdint>
 
 #define BSK_ROOTS3_FUNCTIONS_ONLY
+#include "bsk_pairs.hpp"
 #include "bsk_roots3.hpp"
 
 #pragma clang fp contract(off)
 
 namespace bskssx {
 
+using bskpairs::Surface;                            // one surface with its orders (bsk_pairs.hpp)
+using bskpairs::window;
 using bskroots::lerp;
 using bskroots::ROOTS_EPS;
 using bskroots3::ROOTS3_SAME;
@@ -56,17 +59,9 @@ constexpr int SSX_WAVE = 64;                        // ssx_isolate: one wave a w
 constexpr int SSX_MAX_K = 4;
 constexpr unsigned STATUS_FLAT = 16;
 
-// rows: [3, R0, R1]; first0: [nc0]; first1: [nc1]
-struct Surf {
-    int K0, K1;
-    const double *rows;
-    long long R0, R1, nc0, nc1;
-    const int32_t *first0, *first1;
-};
-
 // one family: the lines of X with variable ax fixed, G per knot cell, against Y
 struct Side {
-    Surf X, Y;
+    Surface X, Y;
     int ax;
     long long G;
 };
@@ -119,18 +114,6 @@ BSK_HD bool line_ref(const Side &s, long long seg, LineRef &l, long long &e)
     l.sr = s.ax == 0 ? 1 : s.X.R1;
     l.KF = s.ax == 0 ? s.X.K0 : s.X.K1;
     l.x = (double)g / (double)s.G;
-    return true;
-}
-
-// the window of cell (p, q) of Y; false: it leaves the rows
-BSK_HD bool window(const Surf &y, long long cell, const double *&w, long long &p, long long &q)
-{
-    if (cell < 0 || cell >= y.nc0 * y.nc1) return false;
-    p = cell / y.nc1;
-    q = cell - p * y.nc1;
-    const long long f0 = y.first0[p], f1 = y.first1[q];
-    if (f0 < 0 || f0 + y.K0 > y.R0 || f1 < 0 || f1 + y.K1 > y.R1) return false;
-    w = y.rows + f0 * y.R1 + f1;
     return true;
 }
 
@@ -224,7 +207,7 @@ BSK_HD void search_lane(const Side &s, const Search &a, long long ch, long long 
             if (PREFILTER && !inbox) continue;
             const double *w;
             long long p, q;
-            if (!window(s.Y, cell, w, p, q)) continue;
+            if (!window(s.Y, s.Y.K0, s.Y.K1, cell, w, p, q)) continue;
             if (pair_kind(L, KR, w, s.Y.R0 * s.Y.R1, s.Y.R1, s.Y.K0, s.Y.K1, S, inbox) == 0) continue;
             if (EMIT && base + n >= 0 && base + n < a.npairs) {
                 a.pair_seg[base + n] = (int32_t)seg;
@@ -256,7 +239,7 @@ BSK_HD void isolate_wave(const W &wave, const Side &s, const Isolate &a, long lo
     double *out = a.roots + slot * 3 * R;
     PairCell pc;
     long long e = 0, p = 0, q = 0;
-    bool walk = line_ref(s, a.pair_seg[slot], pc.l, e) && window(s.Y, a.pair_cell[slot], pc.w, p, q);
+    bool walk = line_ref(s, a.pair_seg[slot], pc.l, e) && window(s.Y, s.Y.K0, s.Y.K1, a.pair_cell[slot], pc.w, p, q);
     unsigned status = 0;
     if (walk) {
         pc.sd = s.Y.R0 * s.Y.R1;

@@ -12,22 +12,11 @@ using namespace bskssx;
 
 static thread_local const char *g_ssx_kernel = "";
 
-static bsk_status check_surf(const Surf &s, const std::string &w)
-{
-    if (!s.rows || !s.first0 || !s.first1) return fail(BSK_ERR_INVALID, w + ": NULL argument");
-    if (s.K0 < 2 || s.K1 < 2) return fail(BSK_ERR_INVALID, w + ": orders must be >= 2");
-    if (s.K0 > SSX_MAX_K || s.K1 > SSX_MAX_K) return fail(BSK_ERR_UNSUPPORTED, w + ": order above " + std::to_string(SSX_MAX_K));
-    if (s.nc0 < 1 || s.nc1 < 1) return fail(BSK_ERR_INVALID, w + ": nc0 and nc1 must be >= 1");
-    if (s.R0 < s.K0 || s.R1 < s.K1) return fail(BSK_ERR_INVALID, w + ": the rows must hold one cell (R0 >= K0, R1 >= K1)");
-    if ((double)s.nc0 * (double)s.nc1 > 2.0e9 || 3.0 * (double)s.R0 * (double)s.R1 > 9.0e15) return fail(BSK_ERR_INVALID, w + ": array too large");
-    return BSK_OK;
-}
-
 static bsk_status check_side(const Side &s, const std::string &w)
 {
-    bsk_status st = check_surf(s.X, w);
+    bsk_status st = bskpairs::check_surface(s.X, SSX_MAX_K, w);
     if (st != BSK_OK) return st;
-    st = check_surf(s.Y, w);
+    st = bskpairs::check_surface(s.Y, SSX_MAX_K, w);
     if (st != BSK_OK) return st;
     if (s.ax != 0 && s.ax != 1) return fail(BSK_ERR_INVALID, w + ": ax must be 0 or 1");
     if (s.G < 1 || s.G > 64) return fail(BSK_ERR_INVALID, w + ": G must be in [1, 64]");
@@ -42,13 +31,10 @@ static bsk_status search(const Side &s, Search a, int prefilter, hipStream_t st)
     bsk_status r = check_side(s, who);
     if (r != BSK_OK) return r;
     if (!a.boxes || !a.scale || (EMIT ? (!a.offset || !a.pair_seg || !a.pair_cell) : !a.partial)) return fail(BSK_ERR_INVALID, who + ": NULL argument");
-    if (a.chunk < 1) return fail(BSK_ERR_INVALID, who + ": chunk must be >= 1");
     if (a.seg0 < 0 || a.nseg < 1 || a.seg0 + a.nseg > (ncfix(s) * s.G + 1) * ncrun(s))
         return fail(BSK_ERR_INVALID, who + ": the segments seg0 .. seg0 + nseg - 1 must be segments of the family");
-    if (EMIT && a.npairs < 1) return fail(BSK_ERR_INVALID, who + ": npairs must be >= 1 (no pairs: no call)");
-    const long long ncell = s.Y.nc0 * s.Y.nc1;
-    a.nchunks = (ncell + a.chunk - 1) / a.chunk;
-    if (a.nchunks > 65535) return fail(BSK_ERR_INVALID, who + ": more than 65535 chunks");
+    r = bskpairs::check_search(s.Y, a.chunk, EMIT, a.npairs, a.nchunks, who);
+    if (r != BSK_OK) return r;
     r = with_bool(prefilter != 0, [&](auto pf) {
         constexpr bool PF = decltype(pf)::value;
         if constexpr (DEVICE) return launch_lanes<SSX_SEARCH_BLOCK>(ssx_search<PF, EMIT>, a.nseg, a.nchunks, st, s, a);
@@ -115,7 +101,7 @@ static bsk_status merge(const Merge &m, hipStream_t st)
         const int32_t *firstX1, int KY0, int KY1, const double *rowsY, int64_t RY0, int64_t RY1, int64_t ncY0, int64_t ncY1,      \
         const int32_t *firstY0, const int32_t *firstY1, int ax, int64_t G
 #define SSX_SIDE                                                                                                                \
-    Side{Surf{KX0, KX1, rowsX, RX0, RX1, ncX0, ncX1, firstX0, firstX1}, Surf{KY0, KY1, rowsY, RY0, RY1, ncY0, ncY1, firstY0, firstY1}, ax, G}
+    Side{Surface{KX0, KX1, rowsX, RX0, RX1, ncX0, ncX1, firstX0, firstX1}, Surface{KY0, KY1, rowsY, RY0, RY1, ncY0, ncY1, firstY0, firstY1}, ax, G}
 #define SSX_SEARCH_ARGS int64_t seg0, int64_t nseg, int64_t chunk, int prefilter, const double *boxes, const double *scale
 #define SSX_ISOLATE_ARGS                                                                                                        \
     const double *breaks_run, const double *breaksY0, const double *breaksY1, const double *scale, const int32_t *pair_seg,      \

@@ -71,6 +71,7 @@ import numpy as np
 from . import _backend
 from . import _cells
 from . import _native as nv
+from . import _pairs as _search        # ``_pairs`` is a knob of cast_batch
 from . import refinement
 from . import roots2
 
@@ -101,6 +102,7 @@ STATUS_TEXT.update({STATUS_SKIPPED: "ray not finite or without direction", STATU
 SCOPE = "intersect_rays: surfaces (nInd 2, nDep 3) of orders 2 to 4"
 INF = float("inf")
 NAN = float("nan")
+box_of, pair_kind = _search.box_of, _search.pair_kind       # the statement's, shared with ``surfaces``
 
 
 # ------------------------------------------------------------------------------------------ the statement
@@ -137,15 +139,6 @@ def form_cell(window, fr):
                       for p, q, w0, w1 in fr.terms]
 
 
-def box_of(window):
-    """(lo0, hi0, lo1, hi1, lo2, hi2) of a window."""
-    out = []
-    for comp in window:
-        flat = [x for row in comp for x in row]
-        out += [min(flat), max(flat)]
-    return out
-
-
 def slab_test(fr, box, tmin, tmax):
     """False: the line on [tmin, tmax] misses the box."""
     enter, leave, hit = tmin, tmax, True
@@ -166,14 +159,6 @@ def slab_test(fr, box, tmin, tmax):
         enter = near if near > enter else enter
         leave = far if far < leave else leave
     return hit and not enter > leave
-
-
-def pair_kind(cell, S, inbox):
-    """0: no pair; 1: a candidate; 2: a flat pair."""
-    for comp, scale in zip(cell[1], S):
-        if all(abs(x) < scale * EPS for x in comp) or scale == 0.0:
-            return 2 if inbox else 0
-    return 0 if roots2.excluded(cell) else 1
 
 
 def reduce_ray(fr, pairs, windows, breaks0, breaks1, nc1, tmin, tmax):
@@ -269,21 +254,12 @@ def statement(rows, plan, cmax, origins, directions, tmin=0.0, tmax=INF, prefilt
 Plan = _cells.TensorPlan
 
 
-class Tables:
-    """What every pass of a call shares, the backend's arrays: the extracted rows (3, R0, R1), cmax (3), first and breaks per
-    axis and the boxes (ncell, 6) (``bsk_rays_boxes``)."""
-
-    def __init__(self, be, plan, rows, cmax):
-        self.be, self.plan, self.rows = be, plan, rows
-        (self.K0, self.K1), (self.nc0, self.nc1) = plan.order, plan.ncells
-        self.ncell = self.nc0 * self.nc1
-        with be:
-            self.cmax = be.put(cmax, np.float64)
-            self.first = [be.put(f, np.int32) for f in plan.first]
-            self.breaks = [be.put(b, np.float64) for b in plan.breaks]
-            self.boxes = be.empty((self.ncell, 6), np.float64)
-            self.surface = plan.order + (be.ptr(rows),) + tuple(plan.rowlen) + tuple(plan.ncells) + tuple(be.ptr(f) for f in self.first)
-            _run(be, "_boxes", *self.surface, be.ptr(self.boxes))
+def Tables(be, plan, rows, cmax):
+    """What every pass of a call shares: ``_pairs.Tables`` and ``dcmax``, cmax as the backend's array (the frames read it)."""
+    tab = _search.Tables(be, plan, rows, cmax, LAST_PATHS)
+    with be:
+        tab.dcmax = be.put(tab.cmax, np.float64)
+    return tab
 
 
 def _run(be, name, *args):
@@ -291,75 +267,70 @@ def _run(be, name, *args):
     LAST_PATHS.append(nv.lib().bsk_rays_last_kernel().decode())
 
 
-def run_pass(tab, origins, directions, tmin, tmax, chunk=CHUNK, prefilter=True, every=False, limit=None):
-    """One pass: origins, directions (3, n), the backend's contiguous float64 arrays.  -> a dict of the backend's arrays:
-    partial, skipped, npairs and, unless npairs is 0 or above ``limit``, pair_ray, pair_cell, roots, near, count, status,
-    nodes per pair, uv (2, n), t, cell, hits, rstatus per ray; every: also all_uv (M, 2), all_t, all_cell, all_off (n + 1)
-    in (ray, cell, slot) order."""
+def _finish(tab, out, search, origins, directions, tmin, tmax, every, offset, npairs):
+    """What follows the count of a pass of ``npairs`` pairs: emit, isolate, reduce (twice for ``every``); fills ``out``."""
     be, n = tab.be, int(origins.shape[1])
-    K0, K1 = tab.K0, tab.K1
-    R = roots2.slots(K0, K1)
-    nchunks = -(-tab.ncell // chunk)
-    with be:
-        rays = (be.ptr(tab.cmax), be.ptr(origins), be.ptr(directions), n)
-        search = tab.surface + rays + (tmin, tmax, chunk, int(bool(prefilter)), be.ptr(tab.boxes))
-        out = dict(partial=be.empty((n, nchunks), np.int32), skipped=be.empty(n, np.uint8))
-        _run(be, "_count", *search, be.ptr(out["partial"]), be.ptr(out["skipped"]))
-        ends = be.cumsum(out["partial"].reshape(-1))
-        npairs = out["npairs"] = int(ends[-1])
-        if limit is not None and npairs > limit:
-            return out
-        out["uv"], out["t"] = be.empty((2, n), np.float64), be.empty(n, np.float64)
-        out["cell"], out["hits"], out["rstatus"] = be.empty(n, np.int32), be.zeros(n, np.int32), out["skipped"]
-        out["all_off"] = be.zeros(n + 1, np.int64)
-        out["all_uv"], out["all_t"], out["all_cell"] = be.empty((0, 2), np.float64), be.empty(0, np.float64), be.empty(0, np.int32)
-        if npairs == 0:                                   # no ray has a candidate: nothing to emit, walk or reduce
-            out["uv"][...] = NAN
-            out["t"][...] = NAN
-            out["cell"][...] = -1
-            return out
-        offset = ends - out["partial"].reshape(-1)
-        pstart = be.empty(n + 1, np.int64)
-        pstart[:n] = offset.reshape(n, nchunks)[:, 0]
-        pstart[n] = npairs
-        out["pair_ray"], out["pair_cell"] = be.empty(npairs, np.int32), be.empty(npairs, np.int32)
-        _run(be, "_emit", *search, be.ptr(offset), be.ptr(out["pair_ray"]), be.ptr(out["pair_cell"]), npairs)
-        out.update(roots=be.empty((npairs, R, 2), np.float64), near=be.empty((npairs, R), np.uint8), count=be.empty(npairs, np.int32),
-                   status=be.empty(npairs, np.uint8), nodes=be.empty(npairs, np.int32), rstatus=be.empty(n, np.uint8))
-        head = tab.surface + tuple(be.ptr(b) for b in tab.breaks) + rays
-        _run(be, "_isolate", *head, be.ptr(out["pair_ray"]), be.ptr(out["pair_cell"]), npairs, be.ptr(out["roots"]), be.ptr(out["near"]),
-             be.ptr(out["count"]), be.ptr(out["status"]), be.ptr(out["nodes"]))
-        reduce = head + (tmin, tmax, be.ptr(pstart), be.ptr(out["pair_cell"]), npairs, be.ptr(out["roots"]), be.ptr(out["near"]),
-                         be.ptr(out["count"]), be.ptr(out["status"]), be.ptr(out["skipped"]))
-        _run(be, "_reduce", *reduce, 0, None, 0, be.ptr(out["uv"]), be.ptr(out["t"]), be.ptr(out["cell"]), be.ptr(out["hits"]),
-             be.ptr(out["rstatus"]))
-        if every:
-            stops = be.cumsum(out["hits"])
-            out["all_off"][1:] = stops
-            nhits = int(stops[-1])
-            if nhits:
-                out["all_uv"], out["all_t"] = be.empty((nhits, 2), np.float64), be.empty(nhits, np.float64)
-                out["all_cell"] = be.empty(nhits, np.int32)
-                _run(be, "_reduce", *reduce, 1, be.ptr(out["all_off"]), nhits, be.ptr(out["all_uv"]), be.ptr(out["all_t"]),
-                     be.ptr(out["all_cell"]), None, None)
+    rays = search[len(tab.surface):len(tab.surface) + 4]
+    R = roots2.slots(tab.K0, tab.K1)
+    out["npairs"] = npairs
+    out["uv"], out["t"] = be.empty((2, n), np.float64), be.empty(n, np.float64)
+    out["cell"], out["hits"], out["rstatus"] = be.empty(n, np.int32), be.zeros(n, np.int32), out["skipped"]
+    out["all_off"] = be.zeros(n + 1, np.int64)
+    out["all_uv"], out["all_t"], out["all_cell"] = be.empty((0, 2), np.float64), be.empty(0, np.float64), be.empty(0, np.int32)
+    if npairs == 0:                                       # no ray has a candidate: nothing to emit, walk or reduce
+        out["uv"][...] = NAN
+        out["t"][...] = NAN
+        out["cell"][...] = -1
+        return out
+    pstart = be.empty(n + 1, np.int64)
+    pstart[:n] = offset.reshape(n, -1)[:, 0]
+    pstart[n] = npairs
+    out["pair_ray"], out["pair_cell"] = be.empty(npairs, np.int32), be.empty(npairs, np.int32)
+    _run(be, "_emit", *search, be.ptr(offset), be.ptr(out["pair_ray"]), be.ptr(out["pair_cell"]), npairs)
+    out.update(_search.isolate_outputs(be, npairs, R, 2), rstatus=be.empty(n, np.uint8))
+    head = tab.surface + tuple(be.ptr(b) for b in tab.breaks) + rays
+    _run(be, "_isolate", *head, be.ptr(out["pair_ray"]), be.ptr(out["pair_cell"]), npairs, be.ptr(out["roots"]), be.ptr(out["near"]),
+         be.ptr(out["count"]), be.ptr(out["status"]), be.ptr(out["nodes"]))
+    reduce = head + (tmin, tmax, be.ptr(pstart), be.ptr(out["pair_cell"]), npairs, be.ptr(out["roots"]), be.ptr(out["near"]),
+                     be.ptr(out["count"]), be.ptr(out["status"]), be.ptr(out["skipped"]))
+    _run(be, "_reduce", *reduce, 0, None, 0, be.ptr(out["uv"]), be.ptr(out["t"]), be.ptr(out["cell"]), be.ptr(out["hits"]),
+         be.ptr(out["rstatus"]))
+    if every:
+        stops = be.cumsum(out["hits"])
+        out["all_off"][1:] = stops
+        nhits = int(stops[-1])
+        if nhits:
+            out["all_uv"], out["all_t"] = be.empty((nhits, 2), np.float64), be.empty(nhits, np.float64)
+            out["all_cell"] = be.empty(nhits, np.int32)
+            _run(be, "_reduce", *reduce, 1, be.ptr(out["all_off"]), nhits, be.ptr(out["all_uv"]), be.ptr(out["all_t"]),
+                 be.ptr(out["all_cell"]), None, None)
     return out
 
 
-def _passes(tab, origins, directions, tmin, tmax, chunk, rays_per_pass, prefilter, every, lo, hi, limit, done):
-    """The rays [lo, hi) in passes of at most ``rays_per_pass`` rays and ``limit`` pairs; ``done`` receives (lo, hi, result)."""
-    for begin in range(lo, hi, rays_per_pass):
-        end = min(begin + rays_per_pass, hi)
-        o, d = origins[:, begin:end], directions[:, begin:end]
-        if tab.be.__class__ is _cells.Host:
-            o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
-        else:
-            o, d = o.contiguous(), d.contiguous()
-        res = run_pass(tab, o, d, tmin, tmax, chunk, prefilter, every, limit if end - begin > 1 else None)
-        if "uv" not in res:                               # more pairs than a pass may hold: halve it
-            half = (end - begin + 1) // 2
-            _passes(tab, origins, directions, tmin, tmax, chunk, half, prefilter, every, begin, end, limit, done)
-        else:
-            done.append((begin, end, res))
+def _passes(tab, origins, directions, tmin, tmax, chunk, rays_per_pass, prefilter, every, limit):
+    """The rays of origins, directions (3, N), the backend's float64 arrays, in passes of at most ``rays_per_pass`` rays and
+    ``limit`` pairs (``_pairs.passes``) -> [(lo, hi, the pass's dict)].  A pass without a pair is kept: its rays are filled."""
+    be, nchunks = tab.be, _search.chunks(tab.ncell, chunk)
+
+    def count(lo, hi):                                    # -> partial and what ``_finish`` takes; o, d live as long as the pass
+        o, d = origins[:, lo:hi], directions[:, lo:hi]
+        o, d = (np.ascontiguousarray(o), np.ascontiguousarray(d)) if be.__class__ is _cells.Host else (o.contiguous(), d.contiguous())
+        search = tab.surface + (be.ptr(tab.dcmax), be.ptr(o), be.ptr(d), hi - lo, tmin, tmax, chunk, int(bool(prefilter)), be.ptr(tab.boxes))
+        out = dict(partial=be.empty((hi - lo, nchunks), np.int32), skipped=be.empty(hi - lo, np.uint8))
+        _run(be, "_count", *search, be.ptr(out["partial"]), be.ptr(out["skipped"]))
+        return out["partial"], (out, search, o, d)
+
+    with be:
+        return [(lo, hi, _finish(tab, *back, tmin, tmax, every, offset, npairs))
+                for lo, hi, back, offset, npairs in _search.passes(be, 0, int(origins.shape[1]), rays_per_pass, limit, count, empty=True)]
+
+
+def run_pass(tab, origins, directions, tmin, tmax, chunk=CHUNK, prefilter=True, every=False):
+    """One pass, whatever its pairs: origins, directions (3, n), the backend's contiguous float64 arrays.  -> a dict of the
+    backend's arrays: partial, skipped, npairs and, unless npairs is 0, pair_ray, pair_cell, roots, near, count, status,
+    nodes per pair, uv (2, n), t, cell, hits, rstatus per ray; every: also all_uv (M, 2), all_t, all_cell, all_off (n + 1)
+    in (ray, cell, slot) order."""
+    return _passes(tab, origins, directions, tmin, tmax, chunk, int(origins.shape[1]), prefilter, every, None)[0][2]
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -386,10 +357,7 @@ def _rays_arg(a, name, on_device):
 def host_tables(spline):
     """The host path's tables: (plan, rows (3, R0, R1), cmax (3)), NumPy float64."""
     plan = Plan(spline.order, spline.knots)
-    data = np.asarray(spline.coefs).astype(np.float64)                 # float32 is widened BEFORE the extraction
-    cmax = np.abs(data).max(axis=(1, 2))
-    rows = _cells.band_host(data, plan.steps, LAST_PATHS) if plan.steps else np.ascontiguousarray(data)
-    return plan, rows, cmax
+    return (plan,) + _search.surface_rows(_cells.Host(), spline, plan, LAST_PATHS)
 
 
 def cast_batch(spline, origins, directions, tmin=0.0, tmax=INF, hits="first", _path=None, _chunk=None, _pass=None, _prefilter=True,
@@ -428,8 +396,7 @@ def cast_batch(spline, origins, directions, tmin=0.0, tmax=INF, hits="first", _p
     N = int(origins.shape[1])
     plan = Plan(spline.order, spline.knots)
     nc0, nc1 = plan.ncells
-    if -(-nc0 * nc1 // chunk) > 65535:
-        raise ValueError("_chunk is too small: more than 65535 chunks")
+    _search.chunks(nc0 * nc1, chunk)
     kdtype = np.result_type(spline.knots[0].dtype, spline.knots[1].dtype)
     path = _backend.choose(path, refinement.steps_covered(plan.steps), N * nc0 * nc1 >= DEVICE_MIN_WORK,
                          "the device path covers the band steps of orders the band kernels take")
@@ -441,16 +408,10 @@ def cast_batch(spline, origins, directions, tmin=0.0, tmax=INF, hits="first", _p
         dev = o.device
         d = (directions if on_device else torch.from_numpy(np.ascontiguousarray(directions))).to(dev).double().contiguous()
         be = _cells.Device(dev)
-        rows = torch.from_numpy(np.ascontiguousarray(spline.coefs)).to(dev).double()       # widened BEFORE the extraction
-        cmax = rows.abs().amax(dim=(1, 2)).cpu().numpy()
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            LAST_PATHS.extend(ran)
-        rows = rows.contiguous()
     else:
         be = _cells.Host()
         o, d = origins.astype(np.float64), directions.astype(np.float64)
-        _, rows, cmax = host_tables(spline)
+    rows, cmax = _search.surface_rows(be, spline, plan, LAST_PATHS)
 
     def finish(*arrays):
         return arrays if on_device or path == "host" else tuple(be.get(a) for a in arrays)
@@ -462,8 +423,7 @@ def cast_batch(spline, origins, directions, tmin=0.0, tmax=INF, hits="first", _p
         return finish(*empty, be.empty(0, np.int32), be.empty(0, np.int32), be.empty(0, np.uint8))
 
     tab = Tables(be, plan, rows, cmax)
-    done = []
-    _passes(tab, o, d, tmin, tmax, chunk, per_pass, _prefilter, every, 0, N, limit, done)
+    done = _passes(tab, o, d, tmin, tmax, chunk, per_pass, _prefilter, every, limit)
     status = be.cat([res["rstatus"] for _, _, res in done])
     if not every:
         uv = be.cat([res["uv"].T for _, _, res in done]).T

@@ -81,6 +81,7 @@ import numpy as np
 from . import _backend
 from . import _cells
 from . import _native as nv
+from . import _pairs as _search        # ``_pairs`` is a knob of trace_pair
 from . import contours
 from . import refinement
 from . import roots
@@ -118,6 +119,7 @@ STATUS_TEXT = dict(roots3.STATUS_TEXT)
 STATUS_TEXT.update({STATUS_FLAT: "coincident (flat) pair of a line and a cell", STATUS_ODD: "a chain ends inside both domains",
                     STATUS_MANY: "more than two vertices in one product leaf"})
 SCOPE = "intersect_surface: two surfaces (nInd 2, nDep 3) of orders 2 to 4"
+box_of, pair_kind = _search.box_of, _search.pair_kind       # the statement's, shared with ``rays``
 
 
 # ------------------------------------------------------------------------------------------ the statement
@@ -157,24 +159,9 @@ def form_pair(L, ywindow):
     return (len(L), K1, K2), [[L[i][d] - ywindow[d][j][k] for i in range(len(L)) for j in range(K1) for k in range(K2)] for d in range(3)]
 
 
-def box_of(window):
-    out = []
-    for comp in window:
-        flat = [x for row in comp for x in row]
-        out += [min(flat), max(flat)]
-    return out
-
-
 def inbox_of(L, box):
     """False: the box of the points L and ``box`` are strictly disjoint in some component."""
     return all(not (max(p[d] for p in L) < box[2 * d] or min(p[d] for p in L) > box[2 * d + 1]) for d in range(3))
-
-
-def pair_kind(cell, S, inbox):
-    """0: no pair; 1: a candidate; 2: a flat pair."""
-    if any(all(abs(x) < S[d] * EPS for x in cell[1][d]) or S[d] == 0.0 for d in range(3)):
-        return 2 if inbox else 0
-    return 0 if roots3.excluded(cell) else 1
 
 
 def merge_keep(found, pairs, ncrun, ncy, brun, by0, by1):
@@ -341,34 +328,14 @@ def link(leaves):
 
 
 # ------------------------------------------------------------------------------------------ the launches
-class Plan(_cells.TensorPlan):
+class Plan(_cells.JumpFreePlan):
     """``_cells.TensorPlan`` that refuses a jump: an interior knot of multiplicity >= K."""
-
-    def __init__(self, order, knots):
-        for d in range(2):
-            k, t = int(order[d]), np.asarray(knots[d])
-            values, counts = np.unique(t, return_counts=True)
-            inside = (values > t[k - 1]) & (values < t[len(t) - k]) & (counts >= k)
-            if inside.any():
-                raise ValueError(f"intersect_surface: the knot {float(values[inside][0])} of variable {d} has multiplicity "
-                                 f"{int(counts[inside][0])} >= order {k} (a jump: no curve crosses it; trim the spline there)")
-        super().__init__(order, knots)
+    who, what = "intersect_surface", "curve"
 
 
-class Tables:
-    """One surface on a backend: the plan, the extracted rows (3, R0, R1), cmax (3, NumPy), first and breaks per axis and
-    the boxes (ncell, 6) (``bsk_rays_boxes``)."""
-
-    def __init__(self, be, plan, rows, cmax):
-        self.be, self.plan, self.rows, self.cmax = be, plan, rows, np.asarray(cmax, np.float64)
-        self.ncell = plan.ncells[0] * plan.ncells[1]
-        with be:
-            self.first = [be.put(f, np.int32) for f in plan.first]
-            self.breaks = [be.put(b, np.float64) for b in plan.breaks]
-            self.boxes = be.empty((self.ncell, 6), np.float64)
-            self.surface = plan.order + (be.ptr(rows),) + tuple(plan.rowlen) + tuple(plan.ncells) + tuple(be.ptr(f) for f in self.first)
-            be.call("bsk_rays_boxes", *self.surface, be.ptr(self.boxes))
-            LAST_PATHS.append(nv.lib().bsk_rays_last_kernel().decode())
+def Tables(be, plan, rows, cmax):
+    """One surface on a backend: ``_pairs.Tables``, logged here."""
+    return _search.Tables(be, plan, rows, cmax, LAST_PATHS)
 
 
 def _run(be, name, *args):
@@ -386,10 +353,7 @@ def chunk_of(nseg, ncell):
 def host_tables(spline):
     """The host path's tables of one surface: (plan, rows (3, R0, R1), cmax (3)), NumPy float64."""
     plan = Plan(spline.order, spline.knots)
-    data = np.asarray(spline.coefs).astype(np.float64)                 # float32 is widened BEFORE the extraction
-    cmax = np.abs(data).max(axis=(1, 2))
-    rows = _cells.band_host(data, plan.steps, LAST_PATHS) if plan.steps else np.ascontiguousarray(data)
-    return plan, rows, cmax
+    return (plan,) + _search.surface_rows(_cells.Host(), spline, plan, LAST_PATHS)
 
 
 def run_family(X, Y, ax, depth, scale, chunk=None, prefilter=True, limit=None):
@@ -400,41 +364,29 @@ def run_family(X, Y, ax, depth, scale, chunk=None, prefilter=True, limit=None):
     nseg = (ncfix * G + 1) * ncrun
     R = roots3.slots(X.plan.order[1 - ax], *Y.plan.order)
     chunk = chunk_of(nseg, Y.ncell) if chunk is None else int(chunk)
-    nchunks = -(-Y.ncell // chunk)
-    if nchunks > 65535:
-        raise ValueError("_chunk is too small: more than 65535 chunks")
+    nchunks = _search.chunks(Y.ncell, chunk)
     limit = PAIRS if limit is None else int(limit)
     side = X.surface + Y.surface + (ax, G)
     done = []
 
-    def passes(lo, hi):
+    def count(lo, hi):
         search = side + (lo, hi - lo, chunk, int(bool(prefilter)), be.ptr(Y.boxes), be.ptr(scale))
         partial = be.empty((hi - lo, nchunks), np.int32)
         _run(be, "_count", *search, be.ptr(partial))
-        ends = be.cumsum(partial.reshape(-1))
-        npairs = int(ends[-1])
-        if npairs > limit and hi - lo > 1:                    # more pairs than a pass may hold: halve it
-            mid = (lo + hi + 1) // 2
-            passes(lo, mid)
-            passes(mid, hi)
-            return
-        if npairs == 0:                                       # no pair: nothing to emit or walk
-            return
-        offset = ends - partial.reshape(-1)
-        res = dict(pair_seg=be.empty(npairs, np.int32), pair_cell=be.empty(npairs, np.int32))
-        _run(be, "_emit", *search, be.ptr(offset), be.ptr(res["pair_seg"]), be.ptr(res["pair_cell"]), npairs)
-        res.update(roots=be.empty((npairs, R, 3), np.float64), near=be.empty((npairs, R), np.uint8), count=be.empty(npairs, np.int32),
-                   status=be.empty(npairs, np.uint8), nodes=be.empty(npairs, np.int32))
-        _run(be, "_isolate", *side, be.ptr(X.breaks[1 - ax]), be.ptr(Y.breaks[0]), be.ptr(Y.breaks[1]), be.ptr(scale),
-             be.ptr(res["pair_seg"]), be.ptr(res["pair_cell"]), npairs, be.ptr(res["roots"]), be.ptr(res["near"]), be.ptr(res["count"]),
-             be.ptr(res["status"]), be.ptr(res["nodes"]))
-        done.append(res)
+        return partial, search
 
     with be:
-        passes(0, nseg)
-        shapes = dict(pair_seg=((0,), np.int32), pair_cell=((0,), np.int32), roots=((0, R, 3), np.float64), near=((0, R), np.uint8),
-                      count=((0,), np.int32), status=((0,), np.uint8), nodes=((0,), np.int32))
-        out = {key: (be.cat([res[key] for res in done]) if done else be.empty(*shape)) for key, shape in shapes.items()}
+        for _, _, search, offset, npairs in _search.passes(be, 0, nseg, nseg, limit, count):     # a pass without a pair is dropped
+            res = dict(pair_seg=be.empty(npairs, np.int32), pair_cell=be.empty(npairs, np.int32))
+            _run(be, "_emit", *search, be.ptr(offset), be.ptr(res["pair_seg"]), be.ptr(res["pair_cell"]), npairs)
+            res.update(_search.isolate_outputs(be, npairs, R, 3))
+            _run(be, "_isolate", *side, be.ptr(X.breaks[1 - ax]), be.ptr(Y.breaks[0]), be.ptr(Y.breaks[1]), be.ptr(scale),
+                 be.ptr(res["pair_seg"]), be.ptr(res["pair_cell"]), npairs, be.ptr(res["roots"]), be.ptr(res["near"]), be.ptr(res["count"]),
+                 be.ptr(res["status"]), be.ptr(res["nodes"]))
+            done.append(res)
+        if not done:
+            done.append(dict(pair_seg=be.empty(0, np.int32), pair_cell=be.empty(0, np.int32), **_search.isolate_outputs(be, 0, R, 3)))
+        out = {key: be.cat([res[key] for res in done]) for key in done[0]}
         out["keep"] = be.cast(~be.isnan(out["roots"][:, :, 0]), np.uint8)
         which = be.nonzero(out["near"])
         if len(which):
@@ -498,21 +450,8 @@ def trace_pair(a, b, depth=None, _path=None, _chunk=None, _pairs=None, _prefilte
     covered = all(refinement.steps_covered(plan.steps) for plan in plans)
     path = _backend.choose(path, covered, work >= DEVICE_MIN_WORK, "the device path covers the band steps of orders the band kernels take")
 
-    tabs = []
-    if path == "device":
-        import torch
-        be = _cells.Device.current()
-        for spline, plan in zip((a, b), plans):
-            rows = torch.from_numpy(np.ascontiguousarray(spline.coefs)).to(be.dev).double()     # widened BEFORE the extraction
-            cmax = rows.abs().amax(dim=(1, 2)).cpu().numpy()
-            if plan.steps:
-                rows, ran = refinement.run_device(rows, plan.steps)
-                LAST_PATHS.extend(ran)
-            tabs.append(Tables(be, plan, rows.contiguous(), cmax))
-    else:
-        be = _cells.Host()
-        for spline in (a, b):
-            tabs.append(Tables(be, *host_tables(spline)))
+    be = _cells.Device.current() if path == "device" else _cells.Host()
+    tabs = [Tables(be, plan, *_search.surface_rows(be, spline, plan, LAST_PATHS)) for spline, plan in zip((a, b), plans)]
     scale = be.put(tabs[0].cmax + tabs[1].cmax, np.float64)
 
     families = []
@@ -563,32 +502,11 @@ def _evaluate(spline, u, v):
 
 def fit_pair(points, xyz, tolerance=None, closed=False):
     """One polyline (n, 4) with its points in space (n, 3) -> (curve on a, curve on b): two Spline curves (nInd 1, nDep 2)
-    on [0, 1] fitted to the same normalised chord-length parameters, the chords measured in xyz.  Points that repeat their
-    predecessor in space are dropped; ``closed``: the last coefficient is set to the first one."""
-    from .spline import Spline
+    on [0, 1] fitted to the same normalised chord-length parameters, the chords measured in xyz (``contours.fit_chords``).
+    Points that repeat their predecessor in space are dropped; ``closed``: the last coefficient is set to the first one."""
     points, xyz = np.asarray(points, np.float64), np.asarray(xyz, np.float64)
     step = np.sqrt((np.diff(xyz, axis=0) ** 2).sum(axis=1)) if len(points) > 1 else np.zeros(0)
-    keep = np.concatenate(([True], step > 0.0))
-    points = points[keep]
-    if len(points) < 2:
-        points = np.repeat(points[:1], 2, axis=0)
-        t = np.array([0.0, 1.0])
-    else:
-        t = np.concatenate(([0.0], np.cumsum(step[step > 0.0])))
-        t /= t[-1]
-        t[-1] = 1.0
-        if np.any(np.diff(t) <= 0.0):                      # chords below the resolution of [0, 1]: index them instead
-            t = np.linspace(0.0, 1.0, len(points))
-    order = min(4, len(points))
-    curves = []
-    for cols in (points[:, :2], points[:, 2:]):
-        curve = Spline.least_squares(t, cols.T.copy(), order=[order], tolerance=tolerance)
-        if closed:
-            coefs = np.array(curve.coefs)
-            coefs[:, -1] = coefs[:, 0]
-            curve = Spline(1, 2, curve.order, curve.nCoef, curve.knots, coefs)
-        curves.append(curve)
-    return tuple(curves)
+    return tuple(contours.fit_chords(points, step, [slice(0, 2), slice(2, 4)], tolerance, closed))
 
 
 def intersect_surface(self, other, depth=None, tolerance=None, **kwargs):

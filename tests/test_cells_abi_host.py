@@ -1,11 +1,13 @@
 """
 The argument contract of the cell families' C entry points (no GPU): bsk_roots_*, bsk_roots2_*, bsk_roots3_*,
-bsk_project_* and bsk_contour_*, twelve ``x_host`` / ``x`` pairs.  Every entry gets one rejected call per failure branch
+bsk_project_*, bsk_contour_*, bsk_rays_* and bsk_ssx_*, twenty-one ``x_host`` / ``x`` pairs.  Every entry gets one rejected call per failure branch
 of its checks, held to the status AND to the exact text of ``bsk_last_error()``; every ``x_host`` entry gets one accepted
-call, held to ``bsk_<family>_last_kernel()``.  A device twin checks its arguments before it touches HIP, so its rejected
+call, held to ``bsk_<family>_last_kernel()`` and to what it wrote.  A device twin checks its arguments before it touches HIP, so its rejected
 calls need no device: they pass a null stream.
 
-The inputs are the smallest there are: one system, one cell, orders 2.  A rejected call reads none of its arrays, so the
+The inputs are the smallest there are: one system, one cell, orders 2 (rays: a 1 x 1 bilinear cell and one ray; ssx: two
+1 x 1 bilinear surfaces with G = 1).  Every rejected call differs from the valid one in one fault alone, so the order of
+the checks is not pinned.  A rejected call reads none of its arrays, so the
 extents that make it "too large" stand for no memory.
 
 Where the twins differ, the difference is pinned as it is: the device twins take fewer orders (roots 8 of 16, roots2 4
@@ -402,3 +404,244 @@ def test_contour_march(name, tail, device):
         assert a["counts"].tolist() == [2] and a["lane_status"].tolist() == [0]      # depth 1: the line crosses two leaves
         e.accepts(last, "host contour_march emit", **emit)
         assert a["xy"][:, [0, 2]].tolist() == [[0.5, 0.5]] * 2
+
+
+# ------------------------------------------------------------------------------------------------------------ the surface table
+SURFACE_KEYS = ("K0", "K1", "rows", "R0", "R1", "nc0", "nc1", "first0", "first1")
+
+
+def surface_checks(e, tag=""):
+    """The six checks of one surface table (bsk_rays_* has one, bsk_ssx_* two: ``tag`` X and Y)."""
+    e.null(*(key + tag for key in ("rows", "first0", "first1")))
+    for key in ("K0", "K1"):
+        e.rejects(INVALID, "orders must be >= 2", **{key + tag: 1})
+        e.rejects(UNSUPPORTED, "order above 4", **{key + tag: 5})
+    for key in ("nc0", "nc1"):
+        e.rejects(INVALID, "nc0 and nc1 must be >= 1", **{key + tag: 0})
+    for key in ("R0", "R1"):
+        e.rejects(INVALID, ONE_CELL2, **{key + tag: 1})
+    e.rejects(INVALID, LARGE, **{"nc0" + tag: 3 * 10 ** 9})
+    e.rejects(INVALID, LARGE, **{"R0" + tag: 10 ** 16})
+
+
+def same(a, want):
+    return np.array_equal(a, np.array(want, a.dtype), equal_nan=True)
+
+
+# ------------------------------------------------------------------------------------------------------------ rays
+NAN = float("nan")
+
+
+def rays_arrays():
+    """The cell (u, v, 0) on the unit square and the ray from (1/4, 1/2, 1) straight down: one hit, (1/4, 1/2) at t = 1.
+    The arrays an entry writes start from values it never writes; the ones a later entry reads hold what the earlier wrote."""
+    a = dict(rows=np.array([[[0.0, 0.0], [1.0, 1.0]], [[0.0, 1.0], [0.0, 1.0]], [[0.0, 0.0], [0.0, 0.0]]]), first0=np.zeros(1, np.int32),
+             first1=np.zeros(1, np.int32), breaks0=np.array([0.0, 1.0]), breaks1=np.array([0.0, 1.0]), cmax=np.array([1.0, 1.0, 0.0]),
+             origins=np.array([[0.25], [0.5], [1.0]]), dirs=np.array([[0.0], [0.0], [-1.0]]), boxes=np.array([[0.0, 1.0, 0.0, 1.0, 0.0, 0.0]]),
+             zero=np.zeros(1, np.int32), offset=np.zeros(1, np.int64), found=np.array([[[0.25, 0.5], [NAN, NAN]]]),
+             found_near=np.zeros((1, 2), np.uint8), found_count=np.ones(1, np.int32), found_status=np.zeros(1, np.uint8),
+             pstart=np.array([0, 1], np.int64), hit_off=np.array([0, 1], np.int64),
+             out_boxes=np.full((1, 6), -1.0), partial=np.full(1, -1, np.int32), skipped=np.full(1, 255, np.uint8),
+             pair_ray=np.full(1, -1, np.int32), pair_cell=np.full(1, -1, np.int32), roots=np.full((1, 2, 2), -1.0),
+             near=np.full((1, 2), 255, np.uint8), count=np.full(1, -1, np.int32), status=np.full(1, 255, np.uint8),
+             nodes=np.full(1, -1, np.int32), uv=np.full((2, 1), -1.0), t=np.full(1, -1.0), cell=np.full(1, -7, np.int32),
+             hits=np.full(1, -1, np.int32), rstatus=np.full(1, 255, np.uint8))
+    surface = dict(K0=2, K1=2, rows=ptr(a["rows"]), R0=2, R1=2, nc0=1, nc1=1, first0=ptr(a["first0"]), first1=ptr(a["first1"]))
+    rays = dict(cmax=ptr(a["cmax"]), origins=ptr(a["origins"]), dirs=ptr(a["dirs"]), nrays=1)
+    return a, surface, rays
+
+
+def rays_checks(e):
+    e.null("cmax", "origins", "dirs")
+    for nrays in (0, 2 * 10 ** 9 + 1):
+        e.rejects(INVALID, "nrays must be in [1, 2e9] (the driver walks the rays in passes)", nrays=nrays)
+
+
+def search_checks(e, nc0):
+    """The checks that the count and emit entries of bsk_rays_* and bsk_ssx_* share; ``nc0`` names the searched surface's."""
+    e.rejects(INVALID, "chunk must be >= 1", chunk=0)
+    e.rejects(INVALID, "more than 65535 chunks", **{nc0: 65536})
+    if "npairs" in e.args:
+        e.rejects(INVALID, "npairs must be >= 1 (no pairs: no call)", npairs=0)
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_rays_boxes"))
+def test_rays_boxes(name, tail, device):
+    a, surface, _ = rays_arrays()
+    e = Entry(name, tail, a, **surface, boxes=ptr(a["out_boxes"]))
+    surface_checks(e)
+    e.null("boxes")
+    if not device:
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_boxes")
+        assert same(a["out_boxes"], a["boxes"])
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_rays_count"))
+def test_rays_count(name, tail, device):
+    a, surface, rays = rays_arrays()
+    e = Entry(name, tail, a, **surface, **rays, tmin=0.0, tmax=float("inf"), chunk=1, prefilter=1, boxes=ptr(a["boxes"]),
+              partial=ptr(a["partial"]), skipped=ptr(a["skipped"]))
+    surface_checks(e)
+    rays_checks(e)
+    e.null("boxes", "partial", "skipped")
+    search_checks(e, "nc0")
+    if not device:
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_count")
+        assert same(a["partial"], [1]) and same(a["skipped"], [0])
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_count", prefilter=0)
+        assert same(a["partial"], [1]) and same(a["skipped"], [0])
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_rays_emit"))
+def test_rays_emit(name, tail, device):
+    a, surface, rays = rays_arrays()
+    e = Entry(name, tail, a, **surface, **rays, tmin=0.0, tmax=float("inf"), chunk=1, prefilter=1, boxes=ptr(a["boxes"]),
+              offset=ptr(a["offset"]), pair_ray=ptr(a["pair_ray"]), pair_cell=ptr(a["pair_cell"]), npairs=1)
+    surface_checks(e)
+    rays_checks(e)
+    e.null("boxes", "offset", "pair_ray", "pair_cell")
+    search_checks(e, "nc0")
+    if not device:
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_emit")
+        assert same(a["pair_ray"], [0]) and same(a["pair_cell"], [0])
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_rays_isolate"))
+def test_rays_isolate(name, tail, device):
+    a, surface, rays = rays_arrays()
+    e = Entry(name, tail, a, **surface, breaks0=ptr(a["breaks0"]), breaks1=ptr(a["breaks1"]), **rays, pair_ray=ptr(a["zero"]),
+              pair_cell=ptr(a["zero"]), npairs=1, roots=ptr(a["roots"]), near=ptr(a["near"]), count=ptr(a["count"]), status=ptr(a["status"]),
+              nodes=ptr(a["nodes"]))
+    surface_checks(e)
+    rays_checks(e)
+    e.null("breaks0", "breaks1", "pair_ray", "pair_cell", "roots", "near", "count", "status", "nodes")
+    e.rejects(INVALID, "npairs must be >= 1 (no pairs: no call)", npairs=0)
+    if not device:
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_isolate")
+        assert same(a["roots"], a["found"]) and same(a["near"], a["found_near"]) and same(a["count"], a["found_count"])
+        assert same(a["status"], a["found_status"]) and same(a["nodes"], [283])        # the nodes that rays.statement visits
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_rays_reduce"))
+def test_rays_reduce(name, tail, device):
+    a, surface, rays = rays_arrays()
+    e = Entry(name, tail, a, **surface, breaks0=ptr(a["breaks0"]), breaks1=ptr(a["breaks1"]), **rays, tmin=0.0, tmax=float("inf"),
+              pstart=ptr(a["pstart"]), pair_cell=ptr(a["zero"]), npairs=1, roots=ptr(a["found"]), near=ptr(a["found_near"]),
+              count=ptr(a["found_count"]), pstatus=ptr(a["found_status"]), skipped=ptr(a["found_status"]), all=0, hit_off=None, nhits=0,
+              uv=ptr(a["uv"]), t=ptr(a["t"]), cell=ptr(a["cell"]), hits=ptr(a["hits"]), status=ptr(a["rstatus"]))
+    every = dict(all=1, hit_off=ptr(a["hit_off"]), nhits=1, hits=None, status=None)
+    surface_checks(e)
+    rays_checks(e)
+    e.null("breaks0", "breaks1", "pstart", "pair_cell", "roots", "near", "count", "pstatus", "skipped", "uv", "t", "cell", "hits", "status")
+    e.rejects(INVALID, NULL, **dict(every, hit_off=None))
+    e.rejects(INVALID, "npairs must be >= 1 (no pairs: no call)", npairs=0)
+    e.rejects(INVALID, "nhits must be >= 1 (no hits: no call)", **dict(every, nhits=0))
+    if not device:
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_reduce")
+        assert same(a["uv"], [[0.25], [0.5]]) and same(a["t"], [1.0]) and same(a["cell"], [0]) and same(a["hits"], [1])
+        assert same(a["rstatus"], [0])
+        a["uv"][:], a["t"][:], a["cell"][:] = -1.0, -1.0, -7
+        e.accepts(nv.lib().bsk_rays_last_kernel, "host ray_reduce all", **every)            # uv is (nhits, 2) here
+        assert same(a["uv"].reshape(1, 2), [[0.25, 0.5]]) and same(a["t"], [1.0]) and same(a["cell"], [0])
+
+
+# ------------------------------------------------------------------------------------------------------------ ssx
+def ssx_arrays():
+    """X = (u, v, 0) and Y = (s - 1/4, 1/4 + s / 2, t - 3/4) on unit squares, G = 1, the lines of X with u fixed: the line
+    u = 0, segment 0, meets Y at (w, s, t) = (3/8, 1/4, 3/4); the line u = 1, segment 1, misses Y's box."""
+    a = dict(rowsX=np.array([[[0.0, 0.0], [1.0, 1.0]], [[0.0, 1.0], [0.0, 1.0]], [[0.0, 0.0], [0.0, 0.0]]]),
+             rowsY=np.array([[[-0.25, -0.25], [0.75, 0.75]], [[0.25, 0.25], [0.75, 0.75]], [[-0.75, 0.25], [-0.75, 0.25]]]),
+             first=np.zeros(1, np.int32), breaks=np.array([0.0, 1.0]), boxes=np.array([[-0.25, 0.75, 0.25, 0.75, -0.75, 0.25]]),
+             scale=np.array([1.75, 1.75, 0.75]), zero=np.zeros(1, np.int32), offset=np.array([0, 1], np.int64), key=np.zeros(1, np.int64),
+             which=np.zeros(1, np.int64), found=np.full((1, 6, 3), NAN),
+             partial=np.full((2, 1), -1, np.int32), pair_seg=np.full(1, -1, np.int32), pair_cell=np.full(1, -1, np.int32),
+             roots=np.full((1, 6, 3), -1.0), near=np.full((1, 6), 255, np.uint8), count=np.full(1, -1, np.int32),
+             status=np.full(1, 255, np.uint8), nodes=np.full(1, -1, np.int32), keep=np.full((1, 6), 7, np.uint8))
+    a["found"][0, 0] = [0.375, 0.25, 0.75]
+    side = {}
+    for tag in "XY":
+        side.update({"K0" + tag: 2, "K1" + tag: 2, "rows" + tag: ptr(a["rows" + tag]), "R0" + tag: 2, "R1" + tag: 2, "nc0" + tag: 1,
+                     "nc1" + tag: 1, "first0" + tag: ptr(a["first"]), "first1" + tag: ptr(a["first"])})
+    side.update(ax=0, G=1)
+    return a, side
+
+
+def side_checks(e):
+    surface_checks(e, "X")
+    surface_checks(e, "Y")
+    for ax in (-1, 2):
+        e.rejects(INVALID, "ax must be 0 or 1", ax=ax)
+    for G in (0, 65):
+        e.rejects(INVALID, "G must be in [1, 64]", G=G)
+    e.rejects(INVALID, "more than 2e9 line segments", nc0X=40000, nc1X=40000, G=2)         # 1.6e9 cells, 3.2e9 segments
+
+
+def ssx_search_checks(e):
+    e.null("boxes", "scale")
+    search_checks(e, "nc0Y")
+    for change in (dict(seg0=-1), dict(nseg=0), dict(nseg=3), dict(seg0=2)):
+        e.rejects(INVALID, "the segments seg0 .. seg0 + nseg - 1 must be segments of the family", **change)
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_ssx_count"))
+def test_ssx_count(name, tail, device):
+    a, side = ssx_arrays()
+    e = Entry(name, tail, a, **side, seg0=0, nseg=2, chunk=1, prefilter=1, boxes=ptr(a["boxes"]), scale=ptr(a["scale"]),
+              partial=ptr(a["partial"]))
+    side_checks(e)
+    ssx_search_checks(e)
+    e.null("partial")
+    if not device:
+        e.accepts(nv.lib().bsk_ssx_last_kernel, "host ssx_count")
+        assert same(a["partial"], [[1], [0]])
+        a["partial"][:] = -1
+        e.accepts(nv.lib().bsk_ssx_last_kernel, "host ssx_count", prefilter=0)
+        assert same(a["partial"], [[1], [0]])
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_ssx_emit"))
+def test_ssx_emit(name, tail, device):
+    a, side = ssx_arrays()
+    e = Entry(name, tail, a, **side, seg0=0, nseg=2, chunk=1, prefilter=1, boxes=ptr(a["boxes"]), scale=ptr(a["scale"]),
+              offset=ptr(a["offset"]), pair_seg=ptr(a["pair_seg"]), pair_cell=ptr(a["pair_cell"]), npairs=1)
+    side_checks(e)
+    ssx_search_checks(e)
+    e.null("offset", "pair_seg", "pair_cell")
+    if not device:
+        e.accepts(nv.lib().bsk_ssx_last_kernel, "host ssx_emit")
+        assert same(a["pair_seg"], [0]) and same(a["pair_cell"], [0])
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_ssx_isolate"))
+def test_ssx_isolate(name, tail, device):
+    a, side = ssx_arrays()
+    e = Entry(name, tail, a, **side, breaks_run=ptr(a["breaks"]), breaksY0=ptr(a["breaks"]), breaksY1=ptr(a["breaks"]), scale=ptr(a["scale"]),
+              pair_seg=ptr(a["zero"]), pair_cell=ptr(a["zero"]), npairs=1, roots=ptr(a["roots"]), near=ptr(a["near"]), count=ptr(a["count"]),
+              status=ptr(a["status"]), nodes=ptr(a["nodes"]))
+    side_checks(e)
+    e.null("breaks_run", "breaksY0", "breaksY1", "scale", "pair_seg", "pair_cell", "roots", "near", "count", "status", "nodes")
+    e.rejects(INVALID, "npairs must be >= 1 (no pairs: no call)", npairs=0)
+    e.rejects(INVALID, "more pairs than one launch takes (2^31 - 1)", npairs=2 ** 31)      # on both twins
+    if not device:
+        e.accepts(nv.lib().bsk_ssx_last_kernel, "host ssx_isolate")
+        assert same(a["roots"], a["found"]) and same(a["near"], np.zeros((1, 6))) and same(a["count"], [1]) and same(a["status"], [0])
+        assert same(a["nodes"], [402])                                                 # the nodes that surfaces.statement_family visits
+
+
+@pytest.mark.parametrize("name,tail,device", twins("bsk_ssx_merge"))
+def test_ssx_merge(name, tail, device):
+    a, _ = ssx_arrays()
+    e = Entry(name, tail, a, R=6, roots=ptr(a["found"]), ncrun=1, ncY0=1, ncY1=1, breaks_run=ptr(a["breaks"]), breaksY0=ptr(a["breaks"]),
+              breaksY1=ptr(a["breaks"]), pair_key=ptr(a["key"]), npairs=1, which=ptr(a["which"]), nnear=1, keep=ptr(a["keep"]))
+    e.null("roots", "breaks_run", "breaksY0", "breaksY1", "pair_key", "which", "keep")
+    for R in (5, 33):
+        e.rejects(INVALID, "R must be min(6 (KR - 1)(K1 - 1)(K2 - 1), 32) of covered orders", R=R)
+    for key in ("ncrun", "ncY0", "ncY1"):
+        e.rejects(INVALID, "ncrun, ncy0 and ncy1 must be >= 1", **{key: 0})
+    e.rejects(INVALID, LARGE, ncY0=3 * 10 ** 9)
+    e.rejects(INVALID, "npairs must be >= 1", npairs=0)
+    for nnear in (0, 7):
+        e.rejects(INVALID, "nnear must be in [1, npairs R] (no zero near a face: no call)", nnear=nnear)
+    if not device:
+        e.accepts(nv.lib().bsk_ssx_last_kernel, "host ssx_merge")
+        assert same(a["keep"], [[1, 7, 7, 7, 7, 7]])                                       # the lane of ``which`` alone writes

@@ -59,9 +59,9 @@ def kernel_rows(name, s, o, d, launches, repeats):
     R = roots2.slots(*plan.order)
     nchunks = -(-tab.ncell // rays.CHUNK)
     with be:
-        ray = (be.ptr(tab.cmax), be.ptr(d_o), be.ptr(d_d), N)
+        ray = (be.ptr(tab.dcmax), be.ptr(d_o), be.ptr(d_d), N)
         search = tab.surface + ray + (0.0, rays.INF, rays.CHUNK, 1, be.ptr(tab.boxes))
-        miss = tab.surface + (be.ptr(tab.cmax), be.ptr(away), be.ptr(d_d), N) + (0.0, rays.INF, rays.CHUNK, 1, be.ptr(tab.boxes))
+        miss = tab.surface + (be.ptr(tab.dcmax), be.ptr(away), be.ptr(d_d), N) + (0.0, rays.INF, rays.CHUNK, 1, be.ptr(tab.boxes))
         t_count = device_time(lambda: be.call("bsk_rays_count", *search, be.ptr(res["partial"]), be.ptr(res["skipped"])), launches, repeats)
         scratch = torch.empty_like(res["partial"])
         t_boxes = device_time(lambda: be.call("bsk_rays_count", *miss, be.ptr(scratch), be.ptr(res["skipped"])), launches, repeats)
