@@ -42,6 +42,9 @@ PRODUCT_SYMBOLS = (
     "bsk_rays_isolate_host", "bsk_rays_isolate", "bsk_rays_reduce_host", "bsk_rays_reduce", "bsk_rays_last_kernel",
     "bsk_ssx_count_host", "bsk_ssx_count", "bsk_ssx_emit_host", "bsk_ssx_emit", "bsk_ssx_isolate_host", "bsk_ssx_isolate",
     "bsk_ssx_merge_host", "bsk_ssx_merge", "bsk_ssx_last_kernel",
+    "bsk_scatter_key_host", "bsk_scatter_key", "bsk_scatter_gram_host", "bsk_scatter_gram", "bsk_scatter_cell_host", "bsk_scatter_cell",
+    "bsk_scatter_fold_host", "bsk_scatter_fold", "bsk_scatter_residual_host", "bsk_scatter_residual", "bsk_scatter_solve_host",
+    "bsk_scatter_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
 INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
@@ -243,6 +246,25 @@ def lib():
     L.bsk_ssx_merge.argtypes = merge_s + [_vp]
     L.bsk_ssx_last_kernel.argtypes = []
     L.bsk_ssx_last_kernel.restype = ctypes.c_char_p
+    shape_s = [ctypes.c_int] * 3 + [_i64, _i64, _vp, _vp, _i64, _i64, ctypes.c_int]
+    key_s = shape_s + [_vp, _vp, _vp, _i64, _vp, _vp]
+    gram_s = shape_s + [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+    cell_s = [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    fold_s = [ctypes.c_int] * 3 + [_i64, _i64, ctypes.c_int, _vp, _vp, _vp]
+    residual_s = shape_s + [_vp, _vp, _vp, _vp, _i64, _vp]
+    L.bsk_scatter_key_host.argtypes = key_s
+    L.bsk_scatter_key.argtypes = key_s + [_vp]
+    L.bsk_scatter_gram_host.argtypes = gram_s
+    L.bsk_scatter_gram.argtypes = gram_s + [_vp]
+    L.bsk_scatter_cell_host.argtypes = cell_s
+    L.bsk_scatter_cell.argtypes = cell_s + [_vp]
+    L.bsk_scatter_fold_host.argtypes = fold_s
+    L.bsk_scatter_fold.argtypes = fold_s + [_vp]
+    L.bsk_scatter_residual_host.argtypes = residual_s
+    L.bsk_scatter_residual.argtypes = residual_s + [_vp]
+    L.bsk_scatter_solve_host.argtypes = fold_s + [_i64p]
+    L.bsk_scatter_last_kernel.argtypes = []
+    L.bsk_scatter_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]
     L.bsk_last_kernel.restype = ctypes.c_char_p
     L.bsk_debug_probe.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -253,7 +275,7 @@ def lib():
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
                         "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_rays_last_kernel",
-                        "bsk_ssx_last_kernel"):
+                        "bsk_ssx_last_kernel", "bsk_scatter_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L

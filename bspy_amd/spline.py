@@ -251,6 +251,31 @@ class Spline:
         from . import fitting as _fitting
         return _fitting.least_squares(uValues, dataPoints, order, knots, compression, tolerance, fixEnds, metadata, **kwargs)
 
+    @staticmethod
+    def fit_points(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, **kwargs):
+        """Least-squares fit of a spline to scattered data (an extension beyond the reference's API; the gridded call is
+        ``least_squares``).  uvw: (nInd, N) parameters, or (N,) for a curve; points: (nDep, N); NumPy float32 / float64 or
+        torch CUDA tensors of those types (float32 is widened first).  order and knots are required.  weights: (N,), all
+        >= 0, or None.  Returns the Spline (float64) that minimises
+
+            sum_i w_i |S(u_i) - p_i|^2 + smoothing E_m(S),
+
+        E_m the energy of derivative order m = ``penalty`` (default min(2, min(order) - 1)): int |S'|^2 or int |S''|^2 for
+        a curve, membrane or thin plate for a surface.  ``correct=n`` runs n rounds of parameter correction (nDep 2 or 3):
+        uvw <- s.project(points, guess=uvw), then the fit again on the same knots.
+
+        The normal equations are assembled on the GPU without atomics (a key per point, a stable sort, per-cell Gram
+        slabs in a stated association, a gather) and solved by a banded Cholesky factorisation on the host; few points,
+        orders 5 and 6 and nDep > 4 are assembled on the host by the same functions.  Results are bitwise reproducible.
+        A point outside the domain, with a NaN or infinite value or a negative weight is excluded with one
+        RuntimeWarning (``scatter.fit_batch`` returns the status bits, residuals and objective values).  smoothing == 0
+        with a coefficient that has no data in its support raises ValueError, as does a matrix that is not positive
+        definite.  Curves and surfaces of orders 2 to 6; nInd 3 raises NotImplementedError (deliberate scope).
+        ``_path="device"`` / ``"host"`` pins the path (tests, measurements)."""
+        from . import scatter as _scatter
+        return _scatter.fit_points(uvw, points, order, knots, weights=weights, smoothing=smoothing, penalty=penalty, correct=correct,
+                                   metadata=metadata, **kwargs)
+
     # ------------------------------------------------------------------ spline to spline (bspy_amd/refinement.py)
     def insert_knots(self, newKnots, **kwargs):
         """Insert knots: newKnots holds per independent variable an iterable of knots or (knot, multiplicity) pairs

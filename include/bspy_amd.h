@@ -764,6 +764,69 @@ bsk_status bsk_contour_march(int K0, int K1, const double *rows, int64_t nrows, 
 const char *bsk_contour_last_kernel(void);
 
 /*
+ * Scattered least squares (Spline.fit_points; the statement of the key, the units, the Gram slabs, the trees, the fold
+ * and the solve is in bspy_amd/scatter.py and DESIGN.md section 24).  The family keeps no handle.  Variable d has order
+ * K_d, n_d coefficients and the n_d + K_d knots knots_d (doubles); a curve has nind = 1, K1 = n1 = 1, knots1 = {0, 1} and
+ * top1 = 0.  Knot cell (c0, c1), c_d in 0 .. n_d - K_d, is the span c_d + K_d - 1; its flat index is c0 nc1 + c1,
+ * nc_d = n_d - K_d + 1.  top_d is the last span of positive width.  uvw[nind][npts], points[ndep][npts], weights[npts]
+ * or NULL (doubles).
+ *   key      : key_out[npts] (int64) = the flat cell of the point, the last span whose left knot is <= u per variable
+ *              (the right domain end belongs to span top); -1 and status[npts] (bytes) != 0 for an excluded point:
+ *              1 a parameter outside the domain, 2 a parameter, coordinate or weight that is NaN or infinite,
+ *              4 a negative weight.
+ *   gram     : order[npts] (int64) is the stable sort of the points by key, offsets[ncells + 1] where the cells start in
+ *              it.  A cell's points are cut into units of 256 points: unit_cell[nunits], unit_start[ncells] (the first
+ *              unit of a cell).  slabs[nunits][K][K + ndep], K = K0 K1: row a = a0 K1 + a1 holds sum w B_a B_b, b < K,
+ *              then sum w B_a p_d, summed as scatter.gram_unit states it.
+ *   cell     : one level of the adjacent-pairs tree over the nodes of a cell, 16 to a node: out[nnodes][entries], node g
+ *              of cell node_cell[g] is its node g - out_start[cell] and sums the inputs in_start[cell] + 16 k ..., at
+ *              most in_count[cell] in all; no inputs: zeros.
+ *   fold     : cells[ncells][K][K + ndep] -> stencil[n0 n1][2 K0 - 1][2 K1 - 1] (entry (i, j), j - i = (d0, d1) at
+ *              [i][d0 + K0 - 1][d1 + K1 - 1]; 0 where j is no coefficient) and rhs[n0 n1][ndep]: per entry the cells that
+ *              hold both coefficients, in increasing flat index; entry (a, b) of a slab is read with a <= b.
+ *   residual : residual_out[npts] = |S(u) - p| for coefs[ndep][n0][n1], NaN where key_in is -1.
+ *   solve    : host only.  The stencil of a symmetric positive definite matrix goes to upper band storage of half
+ *              bandwidth (K0 - 1) n1 + K1 - 1 (at most 2^27 doubles) and is solved by a banded Cholesky factorisation:
+ *              coefs[ndep][n0 n1].  A pivot that is not positive: *bad_row = its row, BSK_ERR_INVALID.
+ *   The kernels cover K0, K1 in 2 .. 4 and ndep 1 .. 4 (gram) and K0, K1 in 2 .. 4 (residual), the host twins orders
+ *   2 .. 6 and any ndep; anything else is BSK_ERR_UNSUPPORTED.  The device entry points take device buffers on the
+ *   current device and enqueue on `stream`.  No atomics, no waiting; the host drivers and the kernels give the same bits.
+ *   The name of the last call: "scatter_key", "scatter_gram", "scatter_cell", "scatter_fold", "scatter_residual" or the
+ *   same behind "host ", or "host scatter_solve".
+ */
+bsk_status bsk_scatter_key_host(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                                int64_t top0, int64_t top1, int ndep, const double *uvw, const double *points,
+                                const double *weights, int64_t npts, int64_t *key_out, uint8_t *status);
+bsk_status bsk_scatter_key(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                           int64_t top0, int64_t top1, int ndep, const double *uvw, const double *points, const double *weights,
+                           int64_t npts, int64_t *key_out, uint8_t *status, void *stream);
+bsk_status bsk_scatter_gram_host(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                                 int64_t top0, int64_t top1, int ndep, const double *uvw, const double *points,
+                                 const double *weights, int64_t npts, const int64_t *order, const int64_t *offsets,
+                                 const int64_t *unit_cell, const int64_t *unit_start, int64_t nunits, double *slabs);
+bsk_status bsk_scatter_gram(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                            int64_t top0, int64_t top1, int ndep, const double *uvw, const double *points, const double *weights,
+                            int64_t npts, const int64_t *order, const int64_t *offsets, const int64_t *unit_cell,
+                            const int64_t *unit_start, int64_t nunits, double *slabs, void *stream);
+bsk_status bsk_scatter_cell_host(int64_t entries, const double *in, const int64_t *in_start, const int64_t *in_count,
+                                 const int64_t *node_cell, const int64_t *out_start, int64_t nnodes, double *out);
+bsk_status bsk_scatter_cell(int64_t entries, const double *in, const int64_t *in_start, const int64_t *in_count,
+                            const int64_t *node_cell, const int64_t *out_start, int64_t nnodes, double *out, void *stream);
+bsk_status bsk_scatter_fold_host(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *cells, double *stencil,
+                                 double *rhs);
+bsk_status bsk_scatter_fold(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *cells, double *stencil,
+                            double *rhs, void *stream);
+bsk_status bsk_scatter_residual_host(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                                     int64_t top0, int64_t top1, int ndep, const double *coefs, const double *uvw,
+                                     const double *points, const int64_t *key_in, int64_t npts, double *residual_out);
+bsk_status bsk_scatter_residual(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
+                                int64_t top0, int64_t top1, int ndep, const double *coefs, const double *uvw, const double *points,
+                                const int64_t *key_in, int64_t npts, double *residual_out, void *stream);
+bsk_status bsk_scatter_solve_host(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil,
+                                  const double *rhs, double *coefs, int64_t *bad_row);
+const char *bsk_scatter_last_kernel(void);
+
+/*
  * Synchronise `stream` and report whether any BSK_DEVICE call on this handle since the
  * last bsk_domain_status() met an out-of-domain parameter (*first_bad = smallest such
  * index, else -1).  Resets the record.

@@ -1,0 +1,278 @@
+"""
+The exact oracle of ``Spline.fit_points`` in ``fractions.Fraction``: no library, no GPU, no reference code.
+
+    basis(K, t, mu, u)            the K basis functions on span mu at u by rational Cox-de Boor
+    span(K, t, u)                 the cell rule of the statement: the last span of positive width whose left knot is <= u
+    normal(case)                  the exact N = A^T W A + lambda E (dense, n x n), Nbar = A^T W A + lambda |E|, r = A^T W p and
+                                  A^T W |p|; E by exact integration of the piecewise polynomials (``gram_exact``)
+    solve(N, R)                   the exact solution by rational elimination (Gauss-Jordan), N^-1 with R = I
+    record(case)                  the exact coefficients rounded once and the per-coefficient bar
+                                      bar_j = c eps (|N^-1| (Nbar |c| + A^T W |p|))_j,       c = ``roundings(case)``
+
+``roundings`` COUNTS the roundings on the longest chain of the statement (bspy_amd/scatter.py); it is not fitted:
+    basis      5 per level and variable (temp: a difference and a quotient; b[r]: a difference, a product, a sum), K_d - 1 levels:
+               5 (K0 - 1) + 5 (K1 - 1), and 1 for Bu Bv; an entry w B_a B_b carries two basis values and two products:
+               2 (5 (K0 - 1) + 5 (K1 - 1) + 1) + 2
+    strand     at most ceil(SEG / Q) sums, Q = strands(K0 K1)
+    trees      log2(Q) levels over the strands, ceil(log2(units)) levels over the units of the fullest cell
+    fold       at most K0 K1 cells per entry
+    penalty    per 1-D Gram entry: 3 m for the differences of the coefficients, 5 (K - 1) for the basis, K for the dot product,
+               twice (two factors), 2 for the weight and the product, K nodes, K spans; 2 + m for the Kronecker sum,
+               2 for smoothing E and its sum with the data term: 2 (3 m + 6 K) + 2 K + 6 + m, K = max(order); 0 without smoothing
+    solve      3 (half bandwidth + 1) for the banded factorisation and the two substitutions
+"""
+import math
+from fractions import Fraction as F
+
+import numpy as np
+
+SEG = 256
+EPS = 2.0 ** -52
+
+
+def strands(K):
+    q = 1
+    while 2 * q * K <= 64:
+        q *= 2
+    return q
+
+
+def frac(a):
+    return [F(float(x)) for x in a]
+
+
+def top_span(K, t):
+    n = len(t) - K
+    mu = n - 1
+    while mu > K - 1 and not t[mu] < t[n]:
+        mu -= 1
+    return mu
+
+
+def span(K, t, u):
+    mu = top_span(K, t)
+    while mu > K - 1 and not t[mu] <= u:
+        mu -= 1
+    return mu
+
+
+def basis(K, t, mu, u):
+    b = [F(1)]
+    for j in range(1, K):
+        saved = F(0)
+        for r in range(j):
+            tr, tl = t[mu + 1 + r], t[mu + 1 + r - j]
+            temp = b[r] / (tr - tl)
+            b[r] = saved + (tr - u) * temp
+            saved = (u - tl) * temp
+        b.append(saved)
+    return b
+
+
+# ------------------------------------------------------------------------------------------ polynomials, lowest power first
+def p_add(a, b):
+    n = max(len(a), len(b))
+    return [(a[i] if i < len(a) else 0) + (b[i] if i < len(b) else 0) for i in range(n)]
+
+
+def p_mul(a, b):
+    out = [F(0)] * (len(a) + len(b) - 1)
+    for i, x in enumerate(a):
+        for j, y in enumerate(b):
+            out[i + j] += x * y
+    return out
+
+
+def p_diff(a):
+    return [i * a[i] for i in range(1, len(a))] or [F(0)]
+
+
+def p_int(a, lo, hi):
+    return sum(c * (hi ** (i + 1) - lo ** (i + 1)) / (i + 1) for i, c in enumerate(a))
+
+
+def span_polys(K, t, mu):
+    """The K basis functions on span mu as polynomials in x."""
+    polys = {mu: [F(1)]}                                                  # order 1
+    for k in range(2, K + 1):
+        new = {}
+        for i in range(mu - k + 1, mu + 1):
+            total = [F(0)]
+            if i in polys and t[i + k - 1] > t[i]:
+                d = t[i + k - 1] - t[i]
+                total = p_add(total, p_mul([-t[i] / d, 1 / d], polys[i]))
+            if i + 1 in polys and t[i + k] > t[i + 1]:
+                d = t[i + k] - t[i + 1]
+                total = p_add(total, p_mul([t[i + k] / d, -1 / d], polys[i + 1]))
+            new[i] = total
+        polys = new
+    return [polys[i] for i in range(mu - K + 1, mu + 1)]
+
+
+def gram_exact(K, t, r):
+    """n x n: int B_i^(r) B_j^(r), exactly."""
+    n = len(t) - K
+    G = [[F(0)] * n for _ in range(n)]
+    for mu in range(K - 1, n):
+        if not t[mu] < t[mu + 1]:
+            continue
+        polys = span_polys(K, t, mu)
+        for _ in range(r):
+            polys = [p_diff(p) for p in polys]
+        for a in range(K):
+            for b in range(a, K):
+                v = p_int(p_mul(polys[a], polys[b]), t[mu], t[mu + 1])
+                G[mu - K + 1 + a][mu - K + 1 + b] += v
+                if b > a:
+                    G[mu - K + 1 + b][mu - K + 1 + a] += v
+    return G
+
+
+def penalty_exact(order, knots, m):
+    """Dense n x n E_m, row index i0 n1 + i1."""
+    if len(order) == 1:
+        return gram_exact(order[0], knots[0], m)
+    n0, n1 = (len(t) - k for t, k in zip(knots, order))
+    E = [[F(0)] * (n0 * n1) for _ in range(n0 * n1)]
+    for a0 in range(m + 1):
+        G0, G1 = gram_exact(order[0], knots[0], a0), gram_exact(order[1], knots[1], m - a0)
+        f = math.comb(m, a0)
+        for i0 in range(n0):
+            for j0 in range(n0):
+                if G0[i0][j0]:
+                    for i1 in range(n1):
+                        for j1 in range(n1):
+                            if G1[i1][j1]:
+                                E[i0 * n1 + i1][j0 * n1 + j1] += f * G0[i0][j0] * G1[i1][j1]
+    return E
+
+
+# ------------------------------------------------------------------------------------------ the normal equations
+def included(case):
+    """bool (N,): the points the statement keeps."""
+    order, knots = case["order"], case["knots"]
+    uvw, pts, w = np.asarray(case["uvw"], np.float64).reshape(len(order), -1), np.asarray(case["points"], np.float64), case.get("weights")
+    ok = np.isfinite(uvw).all(axis=0) & np.isfinite(pts).all(axis=0)
+    if w is not None:
+        ok &= np.isfinite(np.asarray(w, np.float64)) & (np.asarray(w, np.float64) >= 0)
+    for d, (k, t) in enumerate(zip(order, knots)):
+        ok &= (uvw[d] >= t[k - 1]) & (uvw[d] <= t[len(t) - k])
+    return ok
+
+
+def normal(case):
+    """-> (N, Nbar, R, Rabs, counts): dense Fractions, R and Rabs n x nDep, counts the points per flat cell."""
+    order = [int(k) for k in case["order"]]
+    knots = [frac(t) for t in case["knots"]]
+    uvw = np.asarray(case["uvw"], np.float64).reshape(len(order), -1)
+    pts = np.asarray(case["points"], np.float64)
+    w = case.get("weights")
+    ncoef = [len(t) - k for t, k in zip(knots, order)]
+    n1 = ncoef[1] if len(order) == 2 else 1
+    n, nDep = int(np.prod(ncoef)), pts.shape[0]
+    nc = [m - k + 1 for m, k in zip(ncoef, order)]
+    counts = np.zeros(int(np.prod(nc)), np.int64)
+    N = [[F(0)] * n for _ in range(n)]
+    R = [[F(0)] * nDep for _ in range(n)]
+    Rabs = [[F(0)] * nDep for _ in range(n)]
+    ok = included(case)
+    for i in np.flatnonzero(ok):
+        u = [F(float(x)) for x in uvw[:, i]]
+        mus = [span(k, t, x) for k, t, x in zip(order, knots, u)]
+        B = basis(order[0], knots[0], mus[0], u[0])
+        index = [mus[0] - order[0] + 1 + a for a in range(order[0])]
+        cell = mus[0] - order[0] + 1
+        if len(order) == 2:
+            Bv = basis(order[1], knots[1], mus[1], u[1])
+            B = [x * y for x in B for y in Bv]
+            index = [i0 * n1 + mus[1] - order[1] + 1 + a for i0 in index for a in range(order[1])]
+            cell = cell * nc[1] + mus[1] - order[1] + 1
+        counts[cell] += 1
+        wi = F(1) if w is None else F(float(w[i]))
+        p = [F(float(x)) for x in pts[:, i]]
+        for a, ia in enumerate(index):
+            t = wi * B[a]
+            for b, ib in enumerate(index):
+                N[ia][ib] += t * B[b]
+            for d in range(nDep):
+                R[ia][d] += t * p[d]
+                Rabs[ia][d] += t * abs(p[d])
+    Nbar = [row[:] for row in N]
+    lam = F(float(case.get("smoothing", 0.0)))
+    if lam:
+        E = penalty_exact(order, knots, int(case["penalty"]))
+        for i in range(n):
+            for j in range(n):
+                if E[i][j]:
+                    N[i][j] += lam * E[i][j]
+                    Nbar[i][j] += lam * abs(E[i][j])
+    return N, Nbar, R, Rabs, counts
+
+
+def solve(N, R):
+    """N^-1 R by Gauss-Jordan elimination in Fractions (N symmetric positive definite: no pivoting needed)."""
+    n, m = len(N), len(R[0])
+    M = [N[i][:] + R[i][:] for i in range(n)]
+    for k in range(n):
+        piv = M[k][k]
+        if piv <= 0:
+            raise ValueError(f"the pivot of row {k} is not positive")
+        row = M[k] = [x / piv for x in M[k]]
+        for i in range(n):
+            f = M[i][k]
+            if i != k and f:
+                Mi = M[i]
+                for j in range(k, n + m):
+                    if row[j]:
+                        Mi[j] -= f * row[j]
+    return [M[i][n:] for i in range(n)]
+
+
+def roundings(case, counts):
+    order = [int(k) for k in case["order"]]
+    K0, K1 = (order + [1])[:2]
+    n1 = (len(case["knots"][1]) - K1) if len(order) == 2 else 1
+    K, Q = K0 * K1, strands(K0 * K1)
+    units = max(1, -(-int(counts.max()) // SEG))
+    c = 2 * (5 * (K0 - 1) + 5 * (K1 - 1) + 1) + 2
+    c += -(-SEG // Q)
+    c += int(math.log2(Q)) + (units - 1).bit_length()
+    c += K
+    if float(case.get("smoothing", 0.0)) > 0.0:
+        m, top = int(case["penalty"]), max(order)
+        c += 2 * (3 * m + 6 * top) + 2 * top + 6 + m
+    c += 3 * ((K0 - 1) * n1 + K1 - 1 + 1)
+    return c
+
+
+def record(case):
+    """-> (coefs (nDep, n) float64: the exact ones rounded once, bar (nDep, n), c)."""
+    N, Nbar, R, Rabs, counts = normal(case)
+    n, nDep = len(N), len(R[0])
+    eye = [[F(int(i == j)) for j in range(n)] for i in range(n)]
+    X = solve(N, [R[i] + eye[i] for i in range(n)])
+    C = [[X[i][d] for d in range(nDep)] for i in range(n)]
+    inv = [[abs(x) for x in X[i][nDep:]] for i in range(n)]
+    c = roundings(case, counts)
+    bar = np.empty((nDep, n))
+    for d in range(nDep):
+        g = [sum(Nbar[i][j] * abs(C[j][d]) for j in range(n) if Nbar[i][j]) + Rabs[i][d] for i in range(n)]
+        for j in range(n):
+            bar[d, j] = c * EPS * float(sum(inv[j][i] * g[i] for i in range(n)))
+    return np.array([[float(C[i][d]) for i in range(n)] for d in range(nDep)]), bar, c
+
+
+def load(path):
+    """The recorded cases of tests/golden/scatter.npz: name -> dict(order, knots, uvw, points, weights, smoothing, penalty,
+    coefs, bar, c)."""
+    z = np.load(path)
+    out = {}
+    for name in z["names"]:
+        name = str(name)
+        order = tuple(int(k) for k in z[f"{name}.order"])
+        smoothing = float(z[f"{name}.smoothing"])
+        out[name] = dict(order=order, knots=[z[f"{name}.knots{d}"] for d in range(len(order))], uvw=z[f"{name}.uvw"],
+                         points=z[f"{name}.points"], weights=z[f"{name}.weights"] if f"{name}.weights" in z else None,
+                         smoothing=smoothing, penalty=int(z[f"{name}.penalty"]) if smoothing > 0.0 else None,
+                         coefs=z[f"{name}.coefs"], bar=z[f"{name}.bar"], c=int(z[f"{name}.c"]))
+    return out
