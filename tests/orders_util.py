@@ -36,7 +36,18 @@ def dispatched(family):
         return span(rays.MIN_K, rays.MAX_K, 2)
     if family == "surfaces":
         return span(surfaces.MIN_K, surfaces.MAX_K, 3)
+    if family == "scatter":
+        from bspy_amd import scatter
+        return span(2, scatter.DEVICE_MAX_K, 1) + span(2, scatter.DEVICE_MAX_K, 2)
     raise KeyError(family)
+
+
+def scatter_triples():
+    """The (K0, K1, nDep) scatter_gram is built for: K1 = 1 is a curve.  ("scatter" is not one of FAMILIES: its fixture
+    orders_scatter.npz has the layout of scatter.npz and its tests are tests/test_scatter_orders_host.py and
+    tests/test_gpu_scatter_orders.py.)"""
+    from bspy_amd import scatter
+    return [((tuple(order) + (1,))[:2]) + (d,) for order in dispatched("scatter") for d in range(1, scatter.DEVICE_MAX_NDEP + 1)]
 
 
 def triples_of(oa, ob):

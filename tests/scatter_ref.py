@@ -20,6 +20,14 @@ The exact oracle of ``Spline.fit_points`` in ``fractions.Fraction``: no library,
                twice (two factors), 2 for the weight and the product, K nodes, K spans; 2 + m for the Kronecker sum,
                2 for smoothing E and its sum with the data term: 2 (3 m + 6 K) + 2 K + 6 + m, K = max(order); 0 without smoothing
     solve      3 (half bandwidth + 1) for the banded factorisation and the two substitutions
+
+The assembly alone (no penalty, no solve) has a bar of its own, counted from the same terms:
+    assembly_roundings(case, counts)   c_asm = basis + strand + trees + fold: 31 for a line, 60 for a cubic curve and 148 for a
+                                       bicubic whose fullest cell holds 2 SEG + 5 points
+    assembly_check(case, stencil, rhs) the worst of |stencil - N_ij| / (c_asm eps N_ij) over the entries where j is a coefficient
+                                       (N_ij is a sum of non-negative terms: its own absolute sum) and the worst of
+                                       |rhs - R_id| / (c_asm eps (A^T W |p|)_id); an entry that is exactly zero must be 0.0 in the
+                                       result, or the ratio is inf.  No elimination: every instantiation is affordable.
 """
 import math
 from fractions import Fraction as F
@@ -245,6 +253,47 @@ def roundings(case, counts):
     return c
 
 
+def assembly_roundings(case, counts):
+    """The terms of ``roundings`` without the penalty and the solve."""
+    order = [int(k) for k in case["order"]]
+    K0, K1 = (order + [1])[:2]
+    Q = strands(K0 * K1)
+    units = max(1, -(-int(np.max(counts)) // SEG))
+    return 2 * (5 * (K0 - 1) + 5 * (K1 - 1) + 1) + 2 + -(-SEG // Q) + int(math.log2(Q)) + (units - 1).bit_length() + K0 * K1
+
+
+def assembly_check(case, stencil, rhs, exact=None):
+    """-> (worst stencil ratio, worst right-hand-side ratio, c_asm) of a stencil (n, S0 S1) and a right-hand side (n, nDep)
+    against ``normal(case)`` without smoothing; ``exact`` takes the result of ``normal`` where it is shared (of a case with
+    at least as many channels: the first nDep columns are used)."""
+    order = [int(k) for k in case["order"]]
+    K0, K1 = (order + [1])[:2]
+    n0, n1 = ([len(t) - k for t, k in zip(case["knots"], order)] + [1])[:2]
+    N, _, R, Rabs, counts = exact if exact is not None else normal(dict(case, smoothing=0.0))
+    c = assembly_roundings(case, counts)
+    stencil = np.asarray(stencil, np.float64).reshape(n0, n1, 2 * K0 - 1, 2 * K1 - 1)
+    rhs = np.asarray(rhs, np.float64).reshape(n0 * n1, -1)
+
+    def ratio(have, want, scale):
+        if not scale:
+            return 0.0 if float(have) == 0.0 and not want else float("inf")
+        return float(abs(F(float(have)) - want) / (c * F(EPS) * scale))
+
+    worst_s = worst_r = 0.0
+    for i0 in range(n0):
+        for i1 in range(n1):
+            i = i0 * n1 + i1
+            for e0 in range(2 * K0 - 1):
+                for e1 in range(2 * K1 - 1):
+                    j0, j1 = i0 + e0 - (K0 - 1), i1 + e1 - (K1 - 1)
+                    inside = 0 <= j0 < n0 and 0 <= j1 < n1
+                    want = N[i][j0 * n1 + j1] if inside else F(0)
+                    worst_s = max(worst_s, ratio(stencil[i0, i1, e0, e1], want, want))
+            for d in range(rhs.shape[1]):
+                worst_r = max(worst_r, ratio(rhs[i, d], R[i][d], Rabs[i][d]))
+    return worst_s, worst_r, c
+
+
 def record(case):
     """-> (coefs (nDep, n) float64: the exact ones rounded once, bar (nDep, n), c)."""
     N, Nbar, R, Rabs, counts = normal(case)
@@ -263,8 +312,8 @@ def record(case):
 
 
 def load(path):
-    """The recorded cases of tests/golden/scatter.npz: name -> dict(order, knots, uvw, points, weights, smoothing, penalty,
-    coefs, bar, c)."""
+    """The recorded cases of tests/golden/scatter.npz (or orders_scatter.npz): name -> dict(order, knots, uvw, points, weights,
+    smoothing, penalty, coefs, bar, c[, counts: the prescribed points per cell])."""
     z = np.load(path)
     out = {}
     for name in z["names"]:
@@ -275,4 +324,6 @@ def load(path):
                          points=z[f"{name}.points"], weights=z[f"{name}.weights"] if f"{name}.weights" in z else None,
                          smoothing=smoothing, penalty=int(z[f"{name}.penalty"]) if smoothing > 0.0 else None,
                          coefs=z[f"{name}.coefs"], bar=z[f"{name}.bar"], c=int(z[f"{name}.c"]))
+        if f"{name}.counts" in z:
+            out[name]["counts"] = z[f"{name}.counts"]
     return out

@@ -5,6 +5,8 @@
 stencil, right-hand side, coefficients, residuals): there is no tolerance.  The same with CUDA tensors in, with the input
 permuted so that every cell keeps its internal order, and twice in a row.  One property case of 2 x 10^5 points on 20 x 20
 bicubic coefficients (cells of several units, two levels of the tree).  Gridded data against ``Spline.least_squares``.
+Excluded points on the device (NaN and infinite parameters, coordinates and weights, points outside the domain, a negative
+weight; a weight of -0.0 and the domain ends are kept), and a call in which every point but one cell's is excluded.
 The host results are computed once per case and shared.
 """
 import functools
@@ -119,6 +121,116 @@ def test_cuda_tensors_permutations_and_repeats(name):
     # twice: the same bytes
     again, _ = fit(case, "device")
     assert bits(again.coefs) == bits(coefs)
+
+
+def excluded_inputs():
+    """The inputs of test_scatter_host.test_excluded_points_change_nothing (the same six points at the same positions), and
+    behind them a NaN weight, a weight of -0.0 (not negative: the point is kept) and a parameter exactly at each domain end
+    (kept: the right end belongs to the last cell)."""
+    case = CASES["weights"]
+    uvw, pts, w = case["uvw"].copy(), case["points"].copy(), case["weights"].copy()
+    extra_u = np.array([[-0.5, 0.5, np.nan, 0.5, 0.5, 0.25], [0.5, 1.5, 0.5, np.inf, 0.5, 0.75]])
+    extra_p = np.ones((3, 6))
+    extra_p[1, 4] = np.nan
+    extra_w = np.array([1.0, 1.0, 1.0, 1.0, 1.0, np.inf])
+    at = [0, 50, 51, 200, 399, 400]
+    uvw, pts, w = (np.insert(a, at, b, axis=-1) for a, b in ((uvw, extra_u), (pts, extra_p), (w, extra_w)))
+    more_u = np.array([[0.5, 0.5, 0.0, 1.0, 0.0, 1.0, 0.375], [0.5, 0.25, 0.375, 1.0, 0.0, 0.625, 1.0]])
+    more_w = np.array([np.nan, -0.0, 1.0, 0.5, 2.0, 1.0, 0.25])
+    more_at = [406] * 7                                                          # behind: the six keep their positions
+    uvw, pts, w = (np.insert(a, more_at, b, axis=-1) for a, b in ((uvw, more_u), (pts, 0.5 * np.ones((3, 7))), (w, more_w)))
+    # the status by the rule of the statement, in NumPy: comparisons with NaN are false
+    outside = ((uvw < 0.0) | (uvw > 1.0)).any(axis=0)
+    nonfinite = ~(np.isfinite(uvw).all(axis=0) & np.isfinite(pts).all(axis=0) & np.isfinite(w))
+    flagged = (1 * outside + 2 * nonfinite + 4 * (w < 0.0)).astype(np.uint8)
+    return case, uvw, pts, w, flagged
+
+
+def both_ways(uvw, pts, order, knots, w, **more):
+    """(coefs, info with NumPy status and residual, key) of the host path, of _path="device" and of CUDA tensors in."""
+    import torch
+    sh = scatter.Shape(order, knots)
+    out = {}
+    for how in ("host", "device", "cuda"):
+        if how == "cuda":
+            t = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (uvw, pts, w)]
+            s, info = scatter.fit_batch(t[0], t[1], order, knots, weights=t[2], **more)
+            info = dict(info, status=info["status"].cpu().numpy(), residual=info["residual"].cpu().numpy())
+        else:
+            s, info = scatter.fit_batch(uvw, pts, order, knots, weights=w, _path=how, **more)
+        assert info["paths"] == (KERNELS if how != "host" else ["host " + k.replace("host ", "") for k in KERNELS])
+        if how == "host":
+            res = scatter.assemble(scatter.Host(), sh, *(np.ascontiguousarray(a, np.float64) for a in (uvw, pts, w)))
+        else:
+            res = device_tables(dict(order=order, knots=knots, uvw=uvw, points=pts, weights=w))
+        out[how] = (s.coefs.copy(), info, np.asarray(res["key"]), res)
+    return out
+
+
+def same_as_host(runs):
+    coefs, hinfo, hkey, hres = runs["host"]
+    for how in ("device", "cuda"):
+        c, info, key, res = runs[how]
+        assert bits(info["status"]) == bits(hinfo["status"]) and bits(key) == bits(hkey), how
+        assert (key[info["status"] != 0] == -1).all() and (key[info["status"] == 0] >= 0).all()
+        bad = info["status"] != 0
+        assert np.isnan(info["residual"][bad]).all() and not np.isnan(info["residual"][~bad]).any()
+        assert bits(info["residual"][~bad]) == bits(hinfo["residual"][~bad]), how
+        assert bits(c) == bits(coefs), how
+        assert info["rms"] == hinfo["rms"] and info["max"] == hinfo["max"] and info["objective"] == hinfo["objective"], how
+        for what in ("counts", "stencil", "rhs"):
+            assert bits(np.asarray(res[what]).reshape(-1)) == bits(np.asarray(hres[what]).reshape(-1)), (how, what)
+
+
+def test_excluded_points_on_the_device():
+    """The device twin of test_scatter_host.test_excluded_points_change_nothing: NaN and inf go through is_finite compiled
+    for the GPU, the keys of -1 through the stable torch.argsort, and offsets[0] > 0 into unit_range."""
+    import torch
+    case, uvw, pts, w, flagged = excluded_inputs()
+    runs = both_ways(uvw, pts, case["order"], case["knots"], w)
+    status = runs["host"][1]["status"]
+    assert bits(status) == bits(flagged) and np.flatnonzero(status).tolist() == [0, 51, 53, 203, 403, 405, 406]
+    assert status[np.flatnonzero(status)].tolist() == [1, 1, 2, 3, 2, 2, 2]
+    assert status.shape == (413,) and int(np.asarray(runs["host"][3]["counts"]).sum()) == 406
+    same_as_host(runs)
+    # the six points of the host test alone change nothing; the kept ones (a weight of -0.0, the domain ends) are data
+    messages = []
+    for how in ("host", "device", "cuda"):
+        args = (uvw, pts, w) if how != "cuda" else tuple(torch.from_numpy(a).cuda() for a in (uvw, pts, w))
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            s = Spline.fit_points(args[0], args[1], case["order"], case["knots"], weights=args[2], _path=None if how == "cuda" else how)
+        assert len(caught) == 1 and issubclass(caught[0].category, RuntimeWarning)
+        messages.append(str(caught[0].message))
+        assert bits(s.coefs) == bits(runs["host"][0])
+    assert messages[0] == messages[1] == messages[2] and "7 of 413" in messages[0] and "flat index 0" in messages[0]
+    # a negative weight
+    neg = case["weights"].copy()
+    neg[3] = -1.0
+    _, info = scatter.fit_batch(case["uvw"], case["points"], case["order"], case["knots"], weights=neg, _path="device")
+    assert info["paths"] == KERNELS and info["status"][3] == scatter.STATUS_WEIGHT and np.count_nonzero(info["status"]) == 1
+    assert np.isnan(info["residual"][3])
+
+
+def test_all_points_but_one_cell_excluded_on_the_device():
+    """Every point excluded, in every way, except the points of one cell: offsets[0] is nearly N and every other cell has no
+    unit.  smoothing > 0, so it solves."""
+    case = CASES["weights"]
+    uvw, pts, w = (a.copy() for a in arrays(case))
+    key = host("weights")[2]["key"]
+    cell = int(np.argmax(np.bincount(key)))
+    out = np.flatnonzero(key != cell)
+    uvw[0, out[0::4]] = np.nan
+    uvw[1, out[1::4]] = 2.0
+    pts[2, out[2::4]] = -np.inf
+    w[out[3::4]] = -0.25
+    runs = both_ways(uvw, pts, case["order"], case["knots"], w, smoothing=2.0 ** -10, penalty=2)
+    _, hinfo, hkey, hres = runs["host"]
+    assert (hkey[out] == -1).all() and (hkey[key == cell] == cell).all() and np.count_nonzero(hinfo["status"]) == len(out)
+    assert set(hinfo["status"][out].tolist()) == {1, 2, 4}
+    counts = np.asarray(hres["counts"])
+    assert counts[cell] == np.count_nonzero(key == cell) > 0 and counts.sum() == counts[cell]
+    same_as_host(runs)
 
 
 def test_two_hundred_thousand_points_device_equals_host():

@@ -2,7 +2,8 @@
 Spline.intersect_surface and surfaces.trace_pair on the GPU (ray_boxes, ssx_count, ssx_emit, ssx_isolate, ssx_merge, the
 band kernels for the extraction): every golden of tests/golden/surfaces.npz through ``_path="device"`` with the kernels that
 ran asserted from ``surfaces.LAST_PATHS`` and ``bsk_ssx_last_kernel``, bit-equal to the host path (which
-tests/test_surfaces_host.py holds to the exact oracle) and on a second run; the layouts of the launches; the fused family
+tests/test_surfaces_host.py holds to the exact oracle) and on a second run; both surfaces x 2^+-40 with the same bytes; the
+layouts of the launches; the fused family
 against the parent's only alternative, ``roots3.zeros3_batch`` on the materialised systems of every line, byte for byte;
 and the fitted curves of ``Spline.intersect_surface`` (``Spline.least_squares`` needs the device).  No kernel of the family
 uses LDS (the resource log shows 0 bytes for all 32), so there is no stale-LDS test to go with it.
@@ -56,6 +57,27 @@ def test_golden_device(name):
         assert "ssx_merge" in ran
     if name == "disjoint":                                  # no candidates: emit, isolate and merge are skipped
         assert ran[2:] == ["ssx_count"] * 4
+
+
+@pytest.mark.parametrize("name", ["plane_d1", "loop"])
+@pytest.mark.parametrize("k", [-40, 40])
+def test_scaling_both_surfaces_by_a_power_of_two_changes_no_byte_on_the_device(name, k):
+    """The device twin of the test of its name in tests/test_surfaces_host.py: the walk's thresholds are relative and a power
+    of two commutes with every rounding, so both surfaces x 2^k give the bytes of the unscaled device run and of the host
+    run, from the ssx_* kernels."""
+    c = load_case(name)
+    a, b = make(c)
+    host = surfaces.trace_pair(a, b, depth=c["depth"], _path="host")
+    host_ran = list(surfaces.LAST_PATHS)
+    dev = surfaces.trace_pair(a, b, depth=c["depth"], _path="device")
+    ran = launches(surfaces.LAST_PATHS)
+    a2, b2 = make(c, 2.0 ** k)
+    scaled = surfaces.trace_pair(a2, b2, depth=c["depth"], _path="device")
+    ran2 = launches(surfaces.LAST_PATHS)
+    assert ran2 == ran == expected(host_ran) and {"ssx_count", "ssx_emit", "ssx_isolate"} <= set(ran2)
+    assert nv.lib().bsk_ssx_last_kernel().decode() == [p for p in ran2 if p.startswith("ssx_")][-1]
+    assert same_result(dev, scaled) and same_result(host, scaled)
+    assert same_result(scaled, surfaces.trace_pair(a2, b2, depth=c["depth"], _path="host"))
 
 
 def test_layouts_against_the_host_drivers():
