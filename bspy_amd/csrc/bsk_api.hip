@@ -804,7 +804,7 @@ static bsk_status launch_jac_rowrot(bsk_spline s, const PointShape &ps, const Pa
         if (ps.uni) {
             // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
             const UniDesc<T> &ud = uni_of<T>(s);
-            const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
+            const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);   // + jac_uni's rank counters
             auto go = [&](auto nd) {
                 return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {
                     return launch(s, "jac_uni", jac_uni<T, O, NORMAL, decltype(nd)::value>, rr_grid(s, m, lds_u), dim3(TILE),
@@ -847,6 +847,8 @@ static bsk_status launch_eval_lds(bsk_spline s, const PointShape &ps, const Para
                 if (ps.uni) {
                     // equally spaced knots: table-free front end on the unclamped image (bsk_uniform.hpp)
                     const UniDesc<T> &ud = uni_of<T>(s);
+                    // one launch geometry for eval_uni and jac_uni (tests/golden/point_launches.txt pins it): the tail holds
+                    // jac_uni's rank counters, eval_uni ranks by ballots and does not touch it
                     const size_t lds_u = (size_t)ud.img_bytes + TILE * sizeof(unsigned);
                     return with_int<1, 2, 3, 0>(s->nDep, [&](auto nd) {     // 0 = run-time loop
                         return for_rr_chunks<T>(s, prm, n, [&](const Params<T> &cp, long long m, long long n0) {

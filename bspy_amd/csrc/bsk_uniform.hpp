@@ -23,7 +23,7 @@
 //   [domain knots of variable 0: ns0 + 1][variable 1: ns1 + 1] pad16
 //   [coefficients: control-point major [i0][i1][dep] when nDep <= 3 (every window read of every dependent
 //    variable is then one of O row addresses plus a compile-time offset), else [dep][i0][i1];
-//    row stride = 32 / O (mod 32) elements] pad1024 [rank counters: not in the global image]
+//    row stride = 32 / O (mod 32) elements] pad16 [rank counters, not in the global image: used by jac_uni only]
 // Row rotation (bsk_rowrot.hpp) on this stride: stepping to the next window row moves 32 / O banks, so
 // the lanes whose windows start in classes equal mod 32 / O share O banks; each lane starts at the row
 // that puts it (rank among those lanes) banks into that set - a conflict-free schedule whenever such a
@@ -37,6 +37,7 @@
 // in flight during the multiply-adds), image staged by LDS-DMA.
 #pragma once
 #include "bsk_rowrot.hpp"
+#include "bsk_rank.hpp"
 
 namespace bsk {
 
@@ -233,22 +234,28 @@ __host__ __device__ inline int uni_row_stride(int nc1, int nDep, int O)
     return r;
 }
 
-// Rank of the lane among the lanes of its half-wave whose windows share banks (classes equal mod
-// 32 / O), requested before the basis is computed and consumed after it (one LDS atomic on a per-wave
-// counter row), and the O row addresses in rotated order.
-// The counters are never reset: lanes that hit one counter in one instruction get CONSECUTIVE values whatever
-// it held, and only the value mod O is used.
+// Rank of the lane among the active lanes of its half-wave whose windows share banks (classes equal mod
+// 32 / O); only the value mod O is used, and the O row addresses come in rotated order.
+// eval_uni, LDS-bound: one wave ballot per class bit (bsk_rank.hpp), ranks 0, 1, 2, ... in lane order, no LDS traffic.
 template <int O>
-__device__ __forceinline__ int uni_rank_request(int base, unsigned *s_rc, int lane)
+__device__ __forceinline__ int uni_rank_ballot(int base, int lane)
+{
+    static_assert(O == 2 || O == 4, "32 / O classes: 4 or 3 ballots");
+    return ballot_rank<(O == 4 ? 3 : 4)>((unsigned)base & (unsigned)(32 / O - 1), lane);
+}
+// jac_uni, bound by the vector ALU (measured no faster with the ballots): one LDS atomic on a
+// per-wave counter row behind the image, requested before the basis is computed and consumed after it.  The counters
+// are never reset: lanes that hit one counter in one instruction get CONSECUTIVE values whatever it held.
+template <int O>
+__device__ __forceinline__ int uni_rank_atomic(int base, unsigned *s_rc, int lane)
 {
     return (int)atomicAdd(&s_rc[(lane & 32) + (base & (32 / O - 1))], 1u);
 }
 template <typename T, int O>
 __device__ __forceinline__ int uni_rows(unsigned coef_a, int base, int rank, unsigned rstride, unsigned (&ra)[O])
 {
-    asm volatile("" : "+v"(rank));   // first use of the atomic's result: hipcc puts its wait here
     // bank inside the shared set at step a = (class / (32 / O) + a + rho) mod O: make it (rank + a) mod O
-    const int rho = (rank - base / (32 / O)) & (O - 1);
+    const int rho = (rank - (int)((unsigned)base / (unsigned)(32 / O))) & (O - 1);   // base >= 0
     const unsigned a0 = coef_a + (unsigned)base * (unsigned)sizeof(T);
 #pragma unroll
     for (int a = 0; a < O; ++a) ra[a] = a0 + __umul24((unsigned)((a + rho) & (O - 1)), rstride);
@@ -279,7 +286,6 @@ __global__ __launch_bounds__(TILE) void eval_uni(const UniDesc<T> ud, const void
     if (n < N) { un[0] = rr_load(p0, n * (unsigned)sizeof(T)); un[1] = rr_load(p1, n * (unsigned)sizeof(T)); }
     stage_linear(smem, gimg, ud.img_bytes);
     __syncthreads();
-    unsigned *s_rc = reinterpret_cast<unsigned *>(smem + ud.img_bytes) + (threadIdx.x & ~63);
     asm volatile("" : "+v"(un[0]), "+v"(un[1]));   // see eval_rowrot: no load pending at the loop header
     const int nDep = ND > 0 ? ND : ud.nDep;
 
@@ -297,7 +303,7 @@ __global__ __launch_bounds__(TILE) void eval_uni(const UniDesc<T> ud, const void
         T z[2];
         uni_spans2<T, DERIV>(kn_a, ud, u, m, z);
         const int base = (int)__umul24((unsigned)m[0], (unsigned)rs) + m[1] * CS;
-        const int rank = uni_rank_request<O>(base, s_rc, lane);
+        const int rank = uni_rank_ballot<O>(base, lane);
         T b[2][O];
         if constexpr (!DERIV) {
             uni_basis_closed<T, O>(z[0], b[0]);
@@ -390,11 +396,12 @@ __global__ __launch_bounds__(TILE) void jac_uni(const UniDesc<T> ud, const void 
         T z[2];
         uni_spans2<T, true>(kn_a, ud, u, m, z);
         const int base = (int)__umul24((unsigned)m[0], (unsigned)rs) + m[1] * CS;
-        const int rank = uni_rank_request<O>(base, s_rc, lane);
+        int rank = uni_rank_atomic<O>(base, s_rc, lane);
         T b[2][O], db[2][O];
         uni_basis_d1<T, O>(z[0], ud.inv_h[0], b[0], db[0]);
         uni_basis_d1<T, O>(z[1], ud.inv_h[1], b[1], db[1]);
         unsigned ra[O];
+        asm volatile("" : "+v"(rank));   // first use of the atomic's result: hipcc puts its wait here
         const int rho = uni_rows<T, O>(coef_a, base, rank, rstride, ra);
         T b0r[O], db0r[O];
         rotate_basis_values<T, O>(b[0], rho, b0r);
