@@ -12,6 +12,8 @@ import numpy as np
 import oracle
 from bspy_amd import integral as _iq
 
+ORACLE_NDEP = 64            # ORC_MAX_NDEP of oracle/bspline_oracle.c
+
 
 def node_grid(nind):
     """(nInd, 15^nInd) axis indices of the tensor nodes, first variable slowest (the kernel's order)."""
@@ -49,8 +51,10 @@ def region_sums(spline, lo_hi, span, integrand=None, chunk=8192):
     mid = 0.5 * (lo_hi[:, :, 0] + lo_hi[:, :, 1])
     half = 0.5 * (lo_hi[:, :, 1] - lo_hi[:, :, 0])
     pts = [(mid[:, i, None] + half[:, i, None] * _iq.GK_X[j[i]][None, :]).ravel() for i in range(nind)]
-    jac, bad = oracle.c_jacobian(spline.order, spline.nCoef, spline.knots, spline.coefs, pts)
-    assert bad == -1
+    parts = [oracle.c_jacobian(spline.order, spline.nCoef, spline.knots, spline.coefs[d:d + ORACLE_NDEP], pts)
+             for d in range(0, spline.nDep, ORACLE_NDEP)]            # the C oracle holds ORC_MAX_NDEP dependents per call
+    assert all(bad == -1 for _, bad in parts)
+    jac = np.concatenate([p[0] for p in parts])
     mu = measure(np.asarray(jac, np.float64)).reshape(nreg, -1)
     if integrand is not None:
         x, _ = oracle.c_evaluate(spline.order, spline.nCoef, spline.knots, spline.coefs, [0] * nind, pts)
