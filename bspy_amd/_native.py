@@ -44,10 +44,10 @@ PRODUCT_SYMBOLS = (
     "bsk_ssx_merge_host", "bsk_ssx_merge", "bsk_ssx_last_kernel",
     "bsk_scatter_key_host", "bsk_scatter_key", "bsk_scatter_gram_host", "bsk_scatter_gram", "bsk_scatter_cell_host", "bsk_scatter_cell",
     "bsk_scatter_fold_host", "bsk_scatter_fold", "bsk_scatter_residual_host", "bsk_scatter_residual", "bsk_scatter_solve_host",
-    "bsk_scatter_last_kernel",
+    "bsk_scatter_solve_work", "bsk_scatter_solve", "bsk_scatter_reweight_host", "bsk_scatter_reweight", "bsk_scatter_last_kernel",
 )
 # ... and the measurement hooks of its BSK_INTERNAL section (bench.py, tools/: not used by the product path)
-INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds")
+INTERNAL_SYMBOLS = ("bsk_debug_probe", "bsk_debug_stage_times", "bsk_debug_fill_lds", "bsk_debug_scatter_solve")
 SYMBOLS = PRODUCT_SYMBOLS + INTERNAL_SYMBOLS
 # ... and the family of Spline.zeros2, also product ABI.  Listed apart because of the digit in the names: the header scan of
 # tests/test_host_logic.py reads names of [a-z_] only and compares them with the tuples above; tests/test_roots2_host.py
@@ -263,6 +263,12 @@ def lib():
     L.bsk_scatter_residual_host.argtypes = residual_s
     L.bsk_scatter_residual.argtypes = residual_s + [_vp]
     L.bsk_scatter_solve_host.argtypes = fold_s + [_i64p]
+    reweight_s = [ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _i64, _vp]
+    L.bsk_scatter_solve_work.argtypes = [ctypes.c_int] * 3 + [_i64, _i64, ctypes.c_int, _i64p]
+    L.bsk_scatter_solve.argtypes = fold_s + [_vp, _i64, _vp, _vp]
+    L.bsk_debug_scatter_solve.argtypes = fold_s + [_vp, _i64, _vp, ctypes.c_int, _vp]
+    L.bsk_scatter_reweight_host.argtypes = reweight_s
+    L.bsk_scatter_reweight.argtypes = reweight_s + [_vp]
     L.bsk_scatter_last_kernel.argtypes = []
     L.bsk_scatter_last_kernel.restype = ctypes.c_char_p
     L.bsk_last_kernel.argtypes = [_vp]

@@ -325,8 +325,251 @@ BSK_HD void residual_lane(const Grid &g, int ndep, const double *coefs, const do
     residual[lane] = sqrt(d2);
 }
 
+// ------------------------------------------------------------------------------------------ reweight
+// The robust weight of one point: residual r >= 0, the caller's weight w0, the threshold s = c sigma > 0.  Huber (loss 0)
+// and Tukey (loss 1); an excluded point (key < 0) keeps w0.  Every operation rounded on its own.
+BSK_HD double reweight_value(int loss, double r, double w0, long long key, double s)
+{
+    if (key < 0) return w0;
+    if (loss == 0) return r <= s ? w0 : w0 * (s / r);
+    if (r < s) {
+        const double t = r / s;
+        const double q = 1.0 - t * t;
+        return w0 * (q * q);
+    }
+    return 0.0;
+}
+
+BSK_HD void reweight_lane(int loss, double s, const double *residual, const double *weights, const int64_t *key, long long lane,
+                          double *out)
+{
+    out[lane] = reweight_value(loss, residual[lane], weights ? weights[lane] : 1.0, key[lane], s);
+}
+
+// ------------------------------------------------------------------------------------------ solve
+// The device twin of bsk_scatter_solve_host: U^T D U = N in band storage, the host's operations on the host's operands
+// in the host's order, reached from the right.  Once row k is final (v_kj = D_k U_kj), every entry (i, j), k < i <= j <=
+// k + hb, subtracts U_ki v_kj; an entry takes its updates in increasing k, the product rounded, then the difference, so
+// it ends with the host's bits (the host's column j sums the same products over k = low .. i - 1, low = max(0, j - hb)).
+// Rows outside low .. are never touched: a product with a stored zero inside the band is formed, one outside is not.
+//
+// Storage is by rows: entry (i, i + d), d in 0 .. hb, at [i ld + d], ld = hb + 1.  Two arrays of n ld doubles: A holds
+// the running entries and, behind the sweep, v; Ub holds U and D on d = 0.  z: [ndep][n].
+//
+//   scatter_band      lane = one stored entry: the stencil's entry of (i, i + d) or 0.0, by the host loop's index rule.
+//   scatter_panel     SOLVE_NB rows k0 .. : wave 0 of every workgroup factors the panel's diagonal triangle in registers,
+//                     lane = column, one row after the other, the finished row handed round by lane exchanges; the
+//                     triangle's U and D go to LDS.  Then lane = one column k0 + NB .. k0 + NB - 1 + hb: the column's
+//                     NB entries in registers take the panel's rows in increasing k.  Workgroup 0 stores the triangle.
+//   scatter_trail     lane = one entry of the window behind the panel, rows and columns k0 + NB .. k0 + NB - 1 + hb:
+//                     the panel's NB rows in increasing k.
+//   scatter_forward   one workgroup per right-hand side, panel by panel: U^T z = b as a column sweep (z_k final: every
+//                     later row subtracts U_kj z_k), wave 0 the triangle, lane = one row of the window; then z / D.
+//   scatter_backward  one wave per right-hand side: row i sums k = i + 1 .. top in increasing k, a serial chain (its
+//                     first term finished last, so no two rows overlap); the lanes form 64 products at a time and put
+//                     them in LDS, every lane runs the chain on them.  x lives in an LDS ring of SOLVE_RING doubles.
+constexpr int SOLVE_NB = 32;                        // rows of a panel: a launch shape, no bit depends on it
+constexpr int SOLVE_BLOCK = 256;                    // scatter_band, scatter_panel, scatter_trail, scatter_forward
+constexpr int SOLVE_RING = 4096;                    // scatter_backward's window of x: half bandwidths up to SOLVE_RING - 1
+
+struct Band {
+    int K0, K1;
+    long long n1, n, hb, ld;
+};
+
+// entry (i, i + d) of the normal matrix in the stencil [n][2 K0 - 1][2 K1 - 1], 0.0 where the stencil has none
+BSK_HD double band_entry(const Band &B, const double *stencil, long long i, long long d)
+{
+    const long long j = i + d;
+    if (j >= B.n) return 0.0;
+    const long long i0 = i / B.n1, i1 = i - i0 * B.n1, j0 = j / B.n1, j1 = j - j0 * B.n1;
+    const long long d0 = j0 - i0, d1 = j1 - i1;
+    if (d0 >= B.K0 || d1 <= -B.K1 || d1 >= B.K1) return 0.0;
+    const int S1 = 2 * B.K1 - 1;
+    return stencil[i * ((2 * B.K0 - 1) * S1) + (d0 + B.K0 - 1) * S1 + d1 + B.K1 - 1];
+}
+
 // ------------------------------------------------------------------------------------------ kernels
 #ifdef __HIPCC__
+__global__ __launch_bounds__(SCATTER_BLOCK) void scatter_reweight(int loss, double s, const double *__restrict__ residual,
+                                                                 const double *__restrict__ weights, const int64_t *__restrict__ key,
+                                                                 long long npts, double *__restrict__ out)
+{
+    const long long gid = (long long)blockIdx.x * SCATTER_BLOCK + threadIdx.x;
+    if (gid >= npts) return;
+    reweight_lane(loss, s, residual, weights, key, gid, out);
+}
+
+__global__ __launch_bounds__(SOLVE_BLOCK) void scatter_band(Band B, const double *__restrict__ stencil, double *__restrict__ A,
+                                                           int64_t *__restrict__ bad_row)
+{
+    const long long gid = (long long)blockIdx.x * SOLVE_BLOCK + threadIdx.x;
+    if (gid == 0) *bad_row = -1;
+    if (gid >= B.n * B.ld) return;
+    const long long i = gid / B.ld;
+    A[gid] = band_entry(B, stencil, i, gid - i * B.ld);
+}
+
+__global__ __launch_bounds__(SOLVE_BLOCK) void scatter_panel(Band B, long long k0, double *A, double *__restrict__ Ub, int64_t *bad_row)
+{
+    constexpr int NB = SOLVE_NB;
+    __shared__ double tri[NB][NB + 1];              // tri[r][i] = U of (k0 + r, k0 + i), r < i; tri[r][r] = D
+    const int tid = threadIdx.x;
+    const long long n = B.n, hb = B.hb, ld = B.ld;
+    if (tid < 64) {
+        const int t = tid;                          // column k0 + t of the triangle
+        const bool col = t < NB && k0 + t < n;
+        double a[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) a[i] = col && i <= t && t - i <= hb ? A[(k0 + i) * ld + (t - i)] : 1.0;
+        long long bad = -1;
+#pragma unroll
+        for (int r = 0; r < NB; ++r) {
+            const double D = __shfl(a[r], r, 64);   // lane r holds the pivot of row k0 + r
+            if (k0 + r < n && bad < 0 && !(D > 0.0)) bad = k0 + r;
+            const bool live = col && t > r && t - r <= hb;
+            const double u = a[r] / D;
+            if (col && t >= r && t - r <= hb) {
+                const double keep = t == r ? D : u;
+                tri[r][t] = keep;
+                if (blockIdx.x == 0) Ub[(k0 + r) * ld + (t - r)] = keep;
+            }
+#pragma unroll
+            for (int i = r + 1; i < NB; ++i) {
+                const double ui = __shfl(u, i, 64);
+                if (live && i <= t) a[i] = a[i] - ui * a[r];
+            }
+        }
+        if (blockIdx.x == 0 && t == 0 && bad >= 0 && *bad_row < 0) *bad_row = bad;
+    }
+    __syncthreads();
+    const long long c = NB + (long long)blockIdx.x * SOLVE_BLOCK + tid, j = k0 + c;
+    if (c >= hb + NB || j >= n) return;
+    double a[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) a[i] = c - i <= hb ? A[(k0 + i) * ld + (c - i)] : 0.0;
+#pragma unroll
+    for (int r = 0; r < NB; ++r)
+        if (c - r <= hb) {
+#pragma unroll
+            for (int i = r + 1; i < NB; ++i) a[i] = a[i] - tri[r][i] * a[r];
+        }
+#pragma unroll
+    for (int r = 0; r < NB; ++r)
+        if (c - r <= hb) {
+            A[(k0 + r) * ld + (c - r)] = a[r];
+            Ub[(k0 + r) * ld + (c - r)] = a[r] / tri[r][r];
+        }
+}
+
+__global__ __launch_bounds__(SOLVE_BLOCK) void scatter_trail(Band B, long long k0, double *A, const double *__restrict__ Ub)
+{
+    constexpr int NB = SOLVE_NB;
+    const long long n = B.n, hb = B.hb, ld = B.ld;
+    const long long i = k0 + NB + blockIdx.y, d = (long long)blockIdx.x * SOLVE_BLOCK + threadIdx.x, j = i + d;
+    const long long top = k0 + NB - 1 + hb < n - 1 ? k0 + NB - 1 + hb : n - 1;
+    if (i > top || j > top) return;
+    double acc = A[i * ld + d];
+#pragma unroll 8
+    for (int r = 0; r < NB; ++r) {
+        const long long k = k0 + r;
+        if (j - k <= hb) acc = acc - Ub[k * ld + (i - k)] * A[k * ld + (j - k)];
+    }
+    A[i * ld + d] = acc;
+}
+
+__global__ __launch_bounds__(SOLVE_BLOCK) void scatter_forward(Band B, int ndep, const double *__restrict__ Ub,
+                                                              const double *__restrict__ rhs, double *z)
+{
+    constexpr int NB = SOLVE_NB;
+    __shared__ double zs[NB];
+    const int tid = threadIdx.x;
+    const long long n = B.n, hb = B.hb, ld = B.ld;
+    const int dep = blockIdx.x;
+    double *zd = z + dep * n;
+    for (long long j = tid; j < n; j += SOLVE_BLOCK) zd[j] = rhs[j * ndep + dep];
+    __syncthreads();
+    for (long long k0 = 0; k0 < n; k0 += NB) {
+        if (tid < 64) {
+            const int t = tid;
+            const bool col = t < NB && k0 + t < n;
+            double zt = col ? zd[k0 + t] : 0.0;
+            double u[NB];
+#pragma unroll
+            for (int r = 0; r < NB; ++r) u[r] = col && r < t && t - r <= hb ? Ub[(k0 + r) * ld + (t - r)] : 0.0;
+#pragma unroll
+            for (int r = 0; r < NB; ++r) {
+                const double zr = __shfl(zt, r, 64);
+                if (col && r < t && t - r <= hb) zt = zt - u[r] * zr;
+            }
+            if (col) {
+                zs[t] = zt;
+                zd[k0 + t] = zt;
+            }
+        }
+        __syncthreads();
+        const long long top = k0 + NB - 1 + hb < n - 1 ? k0 + NB - 1 + hb : n - 1;
+        for (long long j = k0 + NB + tid; j <= top; j += SOLVE_BLOCK) {
+            double acc = zd[j];
+#pragma unroll 8
+            for (int r = 0; r < NB; ++r) {
+                const long long k = k0 + r;
+                if (j - k <= hb) acc = acc - Ub[k * ld + (j - k)] * zs[r];
+            }
+            zd[j] = acc;
+        }
+        __syncthreads();
+    }
+    for (long long j = tid; j < n; j += SOLVE_BLOCK) zd[j] = zd[j] / Ub[j * ld];
+}
+
+__global__ __launch_bounds__(SCATTER_WAVE) __attribute__((amdgpu_waves_per_eu(1, 1))) void scatter_backward(Band B, const double *__restrict__ Ub, const double *__restrict__ z,
+                                                                double *__restrict__ coefs)
+{
+    __shared__ double ring[SOLVE_RING], prod[SCATTER_WAVE];
+    const int lane = threadIdx.x;
+    const long long n = B.n, hb = B.hb, ld = B.ld;
+    const double *y = z + blockIdx.x * n;
+    double *x = coefs + blockIdx.x * n;
+    // U of row ii at the offsets base .. base + 63, one per lane: loaded one step ahead of its use
+    auto load = [&](long long ii, long long base) {
+        const long long kk = base + lane, mm = hb < n - 1 - ii ? hb : n - 1 - ii;
+        return ii >= 0 && kk <= mm ? Ub[ii * ld + kk] : 0.0;
+    };
+    double unext = load(n - 1, 1), ynext = y[n - 1];
+    for (long long i = n - 1; i >= 0; --i) {
+        const long long m = hb < n - 1 - i ? hb : n - 1 - i;      // the terms k = i + 1 .. i + m
+        double sum = ynext;
+        if (i > 0) ynext = y[i - 1];
+        long long base = 1;
+        do {
+            const double u = unext;
+            unext = base + 64 <= m ? load(i, base + 64) : load(i - 1, 1);
+            const long long kk = base + lane;
+            const double p = kk <= m ? u * ring[(i + kk) & (SOLVE_RING - 1)] : 0.0;
+            const long long cnt = m - base + 1;
+            __builtin_amdgcn_wave_barrier();        // one wave: its LDS accesses complete in program order
+            prod[lane] = p;
+            __builtin_amdgcn_wave_barrier();
+            if (cnt >= 64) {
+                double q[SCATTER_WAVE];                // all 64 reads in flight, then the chain
+#pragma unroll
+                for (int l = 0; l < 64; ++l) q[l] = prod[l];
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int l = 0; l < 64; ++l) sum = sum - q[l];
+            } else {
+                for (int l = 0; l < (int)cnt; ++l) sum = sum - prod[l];
+            }
+            base += 64;
+        } while (base <= m);
+        __builtin_amdgcn_wave_barrier();
+        ring[i & (SOLVE_RING - 1)] = sum;           // every lane writes the same value
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) x[i] = sum;
+    }
+}
+
 __global__ __launch_bounds__(SCATTER_BLOCK) void scatter_key(int nind, int K0, int K1, Grid g, int ndep,
                                                             const double *__restrict__ uvw, const double *__restrict__ points,
                                                             const double *__restrict__ weights, long long npts,

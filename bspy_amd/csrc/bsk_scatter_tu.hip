@@ -1,6 +1,8 @@
 // Scattered least squares (bsk_scatter.hpp): the bsk_scatter_* entry points.  Like bsk_project_tu.hip the family keeps
 // no handle, and each x_host / x pair is one function of DEVICE: the checks, the dispatch, then the host loop over the
-// lanes or the launch.  bsk_scatter_solve_host, the banded Cholesky solve, has no device twin.
+// lanes or the launch.  bsk_scatter_solve_host, the banded Cholesky solve, is a loop of its own; bsk_scatter_solve is its
+// device twin, a sequence of launches (scatter_band, scatter_panel and scatter_trail per panel, scatter_forward,
+// scatter_backward) on the caller's workspace.
 // Instantiations: scatter_gram for curves of order 2 .. 4 and surfaces of orders 2 .. 4, ndep 1 .. 4; scatter_residual for
 // the same orders; the host drivers for orders 2 .. 6 and any ndep.
 #include <cstdint>
@@ -177,6 +179,84 @@ static bsk_status residual(const Shape &s, int ndep, const double *coefs, const 
     return r;
 }
 
+// ------------------------------------------------------------------------------------------ reweight
+template <bool DEVICE>
+static bsk_status reweight(int loss, double s, const double *residual, const double *weights, const int64_t *keys, long long npts,
+                           double *out, hipStream_t st)
+{
+    const std::string w = DEVICE ? "bsk_scatter_reweight" : "bsk_scatter_reweight_host";
+    if (loss != 0 && loss != 1) return fail(BSK_ERR_INVALID, w + ": loss must be 0 (Huber) or 1 (Tukey)");
+    if (!(s > 0.0) || !is_finite(s)) return fail(BSK_ERR_INVALID, w + ": the threshold must be finite and > 0");
+    if (!residual || !keys || !out) return fail(BSK_ERR_INVALID, w + ": NULL argument");
+    if (npts < 1) return fail(BSK_ERR_INVALID, w + ": npts must be >= 1");
+    if (DEVICE && too_many(npts, SCATTER_BLOCK)) return fail(BSK_ERR_INVALID, w + ": too many points for one launch");
+    if constexpr (DEVICE) {
+        bsk_status r = launch_lanes<SCATTER_BLOCK>(scatter_reweight, npts, st, loss, s, residual, weights, keys, npts, out);
+        if (r != BSK_OK) return r;
+    } else {
+        for (long long lane = 0; lane < npts; ++lane) reweight_lane(loss, s, residual, weights, keys, lane, out);
+    }
+    g_scatter_kernel = DEVICE ? "scatter_reweight" : "host scatter_reweight";
+    return BSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------ solve (device)
+constexpr int STAGE_BAND = 1, STAGE_FACTOR = 2, STAGE_FORWARD = 4, STAGE_BACKWARD = 8;
+
+// the checks of bsk_scatter_solve and the band it works on; *doubles: the workspace (A, Ub: n ld each; z: ndep n)
+static bsk_status solve_plan(const Shape &s, int ndep, const std::string &w, Band &B, long long &doubles)
+{
+    bsk_status r = check_shape(s, false, w, false);
+    if (r != BSK_OK) return r;
+    if (ndep < 1 || ndep > SCATTER_DEVICE_MAX_NDEP) return fail(BSK_ERR_UNSUPPORTED, w + ": ndep 1 to 4");
+    const long long n = s.n0 * s.n1, full = (long long)(s.K0 - 1) * s.n1 + s.K1 - 1, hb = full < n - 1 ? full : n - 1;
+    if ((double)n * (double)(full + 1) > SCATTER_MAX_BAND) return fail(BSK_ERR_INVALID, w + ": the band storage n (half bandwidth + 1) exceeds 2^27 doubles");
+    if (hb > SOLVE_RING - 1) return fail(BSK_ERR_UNSUPPORTED, w + ": half bandwidths up to " + std::to_string(SOLVE_RING - 1));
+    B = Band{s.K0, s.K1, s.n1, n, hb, hb + 1};
+    doubles = 2 * n * (hb + 1) + (long long)ndep * n;
+    return BSK_OK;
+}
+
+static bsk_status solve_device(const Shape &s, int ndep, const double *stencil, const double *rhs, double *coefs, double *work,
+                               long long work_doubles, int64_t *bad_row, int stages, hipStream_t st)
+{
+    const std::string w = "bsk_scatter_solve";
+    Band B;
+    long long need = 0;
+    bsk_status r = solve_plan(s, ndep, w, B, need);
+    if (r != BSK_OK) return r;
+    if (!stencil || !rhs || !coefs || !work || !bad_row) return fail(BSK_ERR_INVALID, w + ": NULL argument");
+    if (work_doubles < need) return fail(BSK_ERR_INVALID, w + ": the workspace holds fewer than " + std::to_string(need) + " doubles");
+    const long long n = B.n, hb = B.hb;
+    double *A = work, *Ub = work + n * B.ld, *z = work + 2 * n * B.ld;
+    if (stages & STAGE_BAND) {
+        r = launch_lanes<SOLVE_BLOCK>(scatter_band, n * B.ld, st, B, stencil, A, bad_row);
+        if (r != BSK_OK) return r;
+    }
+    if (stages & STAGE_FACTOR)
+        for (long long k0 = 0; k0 < n; k0 += SOLVE_NB) {
+            const long long behind = n - k0 - SOLVE_NB, cols = behind < hb ? behind : hb;     // columns and rows behind the panel
+            hipLaunchKernelGGL(scatter_panel, dim3((unsigned)(cols > 0 ? (cols + SOLVE_BLOCK - 1) / SOLVE_BLOCK : 1)), dim3(SOLVE_BLOCK), 0, st,
+                               B, k0, A, Ub, bad_row);
+            HIPCHK(hipGetLastError());
+            if (cols > 0) {
+                hipLaunchKernelGGL(scatter_trail, dim3((unsigned)((cols + SOLVE_BLOCK - 1) / SOLVE_BLOCK), (unsigned)cols), dim3(SOLVE_BLOCK), 0, st,
+                                   B, k0, A, Ub);
+                HIPCHK(hipGetLastError());
+            }
+        }
+    if (stages & STAGE_FORWARD) {
+        hipLaunchKernelGGL(scatter_forward, dim3((unsigned)ndep), dim3(SOLVE_BLOCK), 0, st, B, ndep, Ub, rhs, z);
+        HIPCHK(hipGetLastError());
+    }
+    if (stages & STAGE_BACKWARD) {
+        hipLaunchKernelGGL(scatter_backward, dim3((unsigned)ndep), dim3(SCATTER_WAVE), 0, st, B, Ub, z, coefs);
+        HIPCHK(hipGetLastError());
+    }
+    g_scatter_kernel = "scatter_solve";
+    return BSK_OK;
+}
+
 // ------------------------------------------------------------------------------------------ the C ABI
 extern "C" const char *bsk_scatter_last_kernel(void) { return g_scatter_kernel; }
 
@@ -250,6 +330,45 @@ extern "C" bsk_status bsk_scatter_residual(int nind, int K0, int K1, int64_t n0,
                                            const double *points, const int64_t *key_in, int64_t npts, double *residual_out, void *stream)
 {
     return residual<true>(SHAPE, ndep, coefs, uvw, points, key_in, npts, residual_out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" bsk_status bsk_scatter_reweight_host(int loss, double threshold, const double *residual, const double *weights,
+                                                const int64_t *key_in, int64_t npts, double *weights_out)
+{
+    return reweight<false>(loss, threshold, residual, weights, key_in, npts, weights_out, nullptr);
+}
+
+extern "C" bsk_status bsk_scatter_reweight(int loss, double threshold, const double *residual, const double *weights,
+                                           const int64_t *key_in, int64_t npts, double *weights_out, void *stream)
+{
+    return reweight<true>(loss, threshold, residual, weights, key_in, npts, weights_out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" bsk_status bsk_scatter_solve_work(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, int64_t *doubles)
+{
+    if (!doubles) return fail(BSK_ERR_INVALID, "bsk_scatter_solve_work: NULL argument");
+    Band B;
+    long long need = 0;
+    bsk_status r = solve_plan(Shape{nind, K0, K1, n0, n1, nullptr, nullptr, n0 - 1, n1 - 1}, ndep, "bsk_scatter_solve_work", B, need);
+    if (r == BSK_OK) *doubles = need;
+    return r;
+}
+
+extern "C" bsk_status bsk_scatter_solve(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil,
+                                        const double *rhs, double *coefs, double *work, int64_t work_doubles, int64_t *bad_row,
+                                        void *stream)
+{
+    return solve_device(Shape{nind, K0, K1, n0, n1, nullptr, nullptr, n0 - 1, n1 - 1}, ndep, stencil, rhs, coefs, work, work_doubles,
+                        bad_row, STAGE_BAND | STAGE_FACTOR | STAGE_FORWARD | STAGE_BACKWARD, static_cast<hipStream_t>(stream));
+}
+
+// measurement hook (tools/scatter_time.py): the stages of bsk_scatter_solve one by one, 1 band, 2 factor, 4 forward, 8 backward
+extern "C" bsk_status bsk_debug_scatter_solve(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil,
+                                              const double *rhs, double *coefs, double *work, int64_t work_doubles,
+                                              int64_t *bad_row, int stages, void *stream)
+{
+    return solve_device(Shape{nind, K0, K1, n0, n1, nullptr, nullptr, n0 - 1, n1 - 1}, ndep, stencil, rhs, coefs, work, work_doubles,
+                        bad_row, stages, static_cast<hipStream_t>(stream));
 }
 
 // The stencil [n][2 K0 - 1][2 K1 - 1] of a symmetric positive definite matrix goes to upper band storage, column j at

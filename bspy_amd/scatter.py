@@ -6,7 +6,9 @@ and ``intersect_rays``).  N points (u_i, p_i) without any grid structure, fixed 
 
     device path   ``bsk_scatter_key``, a stable sort by key (``be.lexsort``), ``bsk_scatter_gram`` (one wave per unit),
                   ``bsk_scatter_cell`` (one launch per level of the tree), ``bsk_scatter_fold``; the stencil comes to the
-                  host, ``bsk_scatter_solve_host``; ``bsk_scatter_residual`` on the device
+                  host, ``bsk_scatter_solve_host``, or stays on the device, ``bsk_scatter_solve`` (``solve=``: a robust fit
+                  of a large enough system takes it, a plain fit the host solve); ``bsk_scatter_residual`` and
+                  ``bsk_scatter_reweight`` on the device
     host path     the ``*_host`` twins: the same functions of bsk_scatter.hpp on the CPU, for few points and for orders
                   5 and 6 or more than 4 dependent variables, which the kernels do not cover
 
@@ -41,6 +43,14 @@ the dtypes, float32 is widened first, every product and sum rounded on its own):
   * solve: stencil + smoothing E (the product and the sum rounded on their own), expanded to upper band storage of half
     bandwidth (K0 - 1) n1 + K1 - 1 and factored as U^T D U without square roots on the host (``bsk_scatter_solve_host``,
     one code path): both paths give the same coefficients once their stencils agree, and weights x 2^k give the same bits.
+    ``bsk_scatter_solve`` is the same solve on the device: the host's operations on the host's operands in the host's
+    order (DESIGN.md section 24), so its coefficients and its first bad pivot are the host's, bit for bit;
+  * robust (``robust=``, ``reweight``, ``lower_median``): round 0 is the fit with the caller's weights w0 (1.0 without).  Each
+    of the ``iterations`` rounds takes the residuals r_i = |S(u_i) - p_i| of the last fit, sigma = 1.4826 x the lower median
+    (rank (M - 1) // 2 in sorted order) of r_i over the M points with status 0 and w0_i > 0, s = c sigma, and the weights
+    Huber: r_i <= s ? w0_i : w0_i (s / r_i); Tukey: r_i < s ? w0_i (q q), q = 1.0 - (r_i / s)(r_i / s) : 0.0 (every operation
+    rounded on its own; an excluded point keeps w0_i), then assembles and solves again.  sigma == 0.0 (an exact fit) ends
+    the rounds; there is no convergence test, so the result is a function of the inputs alone.
 No atomics, no waiting: two runs give the same bytes, and no launch shape enters the result.
 
 ``_path="device" | "host"`` (or ``scatter.FORCE_PATH``) pins the path; ``scatter.LAST_PATHS`` lists what the last call ran.
@@ -60,6 +70,16 @@ from ._backend import Device, Host, choose, is_torch, pick_path
 DEVICE_MIN_WORK = 10 ** 4
 FORCE_PATH = None          # None, "device" or "host"
 LAST_PATHS = []
+# n hb^2 (coefficients x half bandwidth squared) from which a robust fit on the device path solves on the device
+# (``solve=None``).  Read off the table of ``tools/scatter_time.py --solves`` on an MI355X: the smallest
+# measured n hb^2 at which the device solve's slowest run beats the host's fastest is the 64 x 64 bicubic (n = 4096, hb = 195),
+# 14.9 against 20.8 ms; the 128 x 128 bicubic wins 4.9 times.  The next smaller row, orders (3, 4) on 48 x 48 (2.3 x 10^7),
+# loses, 8.76 against 3.00 ms, and nothing was measured between: the crossover is not bracketed from below.
+SOLVE_MIN_WORK = 4096 * 195 * 195
+FORCE_SOLVE = None         # None, "device" or "host"
+SOLVE_MAX_HALF = 4095      # half bandwidths bsk_scatter_solve covers
+LOSSES = {"huber": (0, 1.345), "tukey": (1, 4.685)}
+SIGMA = 1.4826             # sigma of a normal distribution = SIGMA x its median absolute value
 
 SEG = 256                  # points per unit: a constant of the statement
 FAN = 16                   # inputs per node and level of bsk_scatter_cell: any power of two gives the same tree
@@ -144,6 +164,76 @@ def pair_tree(x):
     while len(x) > 1:
         x = [x[i] + x[i + 1] if i + 1 < len(x) else x[i] for i in range(0, len(x), 2)]
     return x[0]
+
+
+def reweight(loss, r, w0, key, s):
+    """The robust weight of one point in plain floats: loss "huber" or "tukey", residual r, the caller's weight w0 (1.0
+    without weights), the point's key and the threshold s = c sigma."""
+    if key < 0:
+        return w0
+    if loss == "huber":
+        return w0 if r <= s else w0 * (s / r)
+    if r < s:
+        t = r / s
+        q = 1.0 - t * t
+        return w0 * (q * q)
+    return 0.0
+
+
+def lower_median(values):
+    """The element of rank (M - 1) // 2 of the M values in sorted order."""
+    values = sorted(values)
+    return values[(len(values) - 1) // 2]
+
+
+def solve_statement(order, ncoef, stencil, rhs):
+    """The U^T D U solve in plain floats, operation by operation what ``bsk_scatter_solve_host`` and ``bsk_scatter_solve``
+    compute: stencil [n][S0 S1] and rhs [n][nDep] as lists.  -> (coefs [nDep][n], bad_row)."""
+    K0, K1 = (tuple(order) + (1,))[:2]
+    n0, n1 = (tuple(ncoef) + (1,))[:2]
+    n, S1 = n0 * n1, 2 * K1 - 1
+    hb = min((K0 - 1) * n1 + K1 - 1, n - 1)
+    N = {}
+    for i0 in range(n0):
+        for i1 in range(n1):
+            for d0 in range(K0):
+                for d1 in range(-(K1 - 1), K1):
+                    j0, j1 = i0 + d0, i1 + d1
+                    i, j = i0 * n1 + i1, j0 * n1 + j1
+                    if j0 < n0 and 0 <= j1 < n1 and j >= i:
+                        N[i, j] = float(stencil[i][(d0 + K0 - 1) * S1 + d1 + K1 - 1])
+    U, D = {}, [0.0] * n
+    for j in range(n):
+        low = max(0, j - hb)
+        v = {}
+        for i in range(low, j):
+            acc = N.get((i, j), 0.0)
+            for k in range(low, i):
+                acc = acc - U[k, i] * v[k]
+            v[i] = acc
+        pivot = N.get((j, j), 0.0)
+        for i in range(low, j):
+            U[i, j] = v[i] / D[i]
+            pivot = pivot - U[i, j] * v[i]
+        if not pivot > 0.0:
+            return None, j
+        D[j] = pivot
+    coefs = []
+    for d in range(len(rhs[0])):
+        y = [0.0] * n
+        for j in range(n):
+            acc = float(rhs[j][d])
+            for k in range(max(0, j - hb), j):
+                acc = acc - U[k, j] * y[k]
+            y[j] = acc
+        y = [y[j] / D[j] for j in range(n)]
+        for i in range(n - 1, -1, -1):
+            acc = y[i]
+            for k in range(i + 1, min(i + hb, n - 1) + 1):
+                acc = acc - U[i, k] * y[k]
+            y[i] = acc
+        coefs.append(y)
+    return coefs, -1
 
 
 def gram_unit(order, knots, cell, pts):
@@ -379,26 +469,110 @@ def residuals(be, sh, coefs, uvw, points, key):
     return out
 
 
-def solve(sh, stencil, rhs):
-    """The coefficients (nDep, n) of the stencil (n, S0 S1) and rhs (n, nDep), NumPy: the banded U^T D U solve on the host."""
-    stencil, rhs = np.ascontiguousarray(stencil, np.float64), np.ascontiguousarray(rhs, np.float64)
+def _not_definite(sh, bad):
+    row = tuple(int(x) for x in np.unravel_index(int(bad), sh.ncoef))
+    return ValueError(f"fit_points: the normal matrix is not positive definite: the pivot of row {int(bad)} (coefficient {row}) "
+                      "is not positive; more data or smoothing > 0 makes it so")
+
+
+def half_bandwidth(sh):
+    return min((sh.K01[0] - 1) * sh.n01[1] + sh.K01[1] - 1, sh.n - 1)
+
+
+def device_solve_scope(sh, nDep):
+    """None when ``bsk_scatter_solve`` covers the system, else the reason."""
+    if nDep > DEVICE_MAX_NDEP:
+        return f"the device solve covers nDep 1 to {DEVICE_MAX_NDEP}"
+    if half_bandwidth(sh) > SOLVE_MAX_HALF:
+        return f"the device solve covers half bandwidths up to {SOLVE_MAX_HALF}"
+    return None
+
+
+def solve(sh, stencil, rhs, where=None):
+    """The coefficients (nDep, n), NumPy, of the stencil (n, S0 S1) and rhs (n, nDep): the banded U^T D U solve.  NumPy
+    arrays are solved on the host (``where`` None or "host") or sent to the device ("device"); torch CUDA tensors are
+    solved on the device (None or "device") or fetched ("host").  Both solves give the same bytes."""
+    on_device = is_torch(stencil)
+    if where not in (None, "host", "device"):
+        raise ValueError("where must be None, 'device' or 'host'")
+    where = where or ("device" if on_device else "host")
     nDep = rhs.shape[1]
     half = (sh.K01[0] - 1) * sh.n01[1] + sh.K01[1] - 1
     if sh.n * (half + 1) > MAX_BAND:
         raise ValueError(f"fit_points: {sh.n} coefficients with the half bandwidth {half} need more than 2^27 doubles of band storage; "
                          "the solve runs on the host (a device solve is not built)")
+    L = nv.lib()
+    if where == "device":
+        why = device_solve_scope(sh, nDep)
+        if why is not None:
+            raise ValueError(why)
+        import torch
+        if on_device:
+            be = Device(stencil.device)
+            stencil, rhs = stencil.double().contiguous(), rhs.double().contiguous()
+        else:
+            be = Device.current()
+            stencil, rhs = be.put(stencil, np.float64), be.put(rhs, np.float64)
+        need = np.zeros(1, np.int64)
+        nv.check(L.bsk_scatter_solve_work(sh.nind, *sh.K01, *sh.n01, nDep, need.ctypes.data_as(nv._i64p)))
+        with be:
+            work = be.empty(int(need[0]), np.float64)
+            coefs, bad = be.empty((nDep, sh.n), np.float64), be.empty(1, np.int64)
+            be.call("bsk_scatter_solve", sh.nind, *sh.K01, *sh.n01, nDep, be.ptr(stencil), be.ptr(rhs), be.ptr(coefs), be.ptr(work),
+                    int(need[0]), be.ptr(bad))
+            name = _last()
+            bad = int(bad.cpu()[0])
+            if bad >= 0:
+                raise _not_definite(sh, bad)
+            coefs = be.get(coefs)
+        LAST_PATHS.append(name)
+        return coefs
+    if on_device:
+        stencil, rhs = stencil.cpu().numpy(), rhs.cpu().numpy()
+    stencil, rhs = np.ascontiguousarray(stencil, np.float64), np.ascontiguousarray(rhs, np.float64)
     coefs = np.empty((nDep, sh.n))
     bad = np.zeros(1, np.int64)
-    L = nv.lib()
     st = L.bsk_scatter_solve_host(sh.nind, *sh.K01, *sh.n01, nDep, stencil.ctypes.data, rhs.ctypes.data, coefs.ctypes.data,
                                   bad.ctypes.data_as(nv._i64p))
     if st != nv.BSK_OK and bad[0] >= 0:
-        row = tuple(int(x) for x in np.unravel_index(int(bad[0]), sh.ncoef))
-        raise ValueError(f"fit_points: the normal matrix is not positive definite: the pivot of row {int(bad[0])} (coefficient {row}) "
-                         "is not positive; more data or smoothing > 0 makes it so")
+        raise _not_definite(sh, bad[0])
     nv.check(st)
     LAST_PATHS.append(_last())
     return coefs
+
+
+_solve = solve             # fit_batch has a keyword of that name
+
+
+def sigma(values):
+    """SIGMA x the lower median of the values (NumPy, (M,)); 0.0 for none.  Selection is exact: ``lower_median`` in NumPy."""
+    if not len(values):
+        return 0.0
+    rank = (len(values) - 1) // 2
+    return SIGMA * float(np.partition(values, rank)[rank])
+
+
+def reweights(be, loss, s, residual, weights, key):
+    """The robust weights (N,) of a round, the backend's: ``bsk_scatter_reweight``."""
+    N = residual.shape[0]
+    with be:
+        out = be.empty(N, np.float64)
+        be.call("bsk_scatter_reweight", LOSSES[loss][0], float(s), be.ptr(residual), be.ptr(weights), be.ptr(key), N, be.ptr(out))
+        LAST_PATHS.append(_last())
+    return out
+
+
+def _robust(robust):
+    """(loss, c) of ``robust=``, or None."""
+    if robust is None:
+        return None
+    name, c = (robust, None) if isinstance(robust, str) else tuple(robust)
+    if name not in LOSSES:
+        raise ValueError(f"robust must be None, 'huber', 'tukey' or (name, c), not {name!r}")
+    c = LOSSES[name][1] if c is None else float(c)
+    if not (c > 0.0 and c < INF):
+        raise ValueError("robust: the tuning constant c must be finite and > 0")
+    return name, c
 
 
 # ------------------------------------------------------------------------------------------ public
@@ -435,12 +609,22 @@ def _empty_support(sh, counts):
     return None if not len(at) else tuple(int(x) for x in at[0])
 
 
-def fit_batch(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, _path=None):
+def fit_batch(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, robust=None,
+              iterations=8, solve=None, _path=None):
     """``Spline.fit_points`` and what happened: (spline, info).  info: ``status`` (N,) uint8 (1 a parameter outside the
     domain, 2 something not finite, 4 a negative weight: the point is excluded), ``residual`` (N,) |S(u_i) - p_i| (NaN for
     an excluded point), ``rms`` and ``max`` over the points that count, ``empty`` the knot cells of positive width without a
-    point, ``objective`` the objective of every fit, ``uvw`` the parameters of the last fit, ``paths``.  CUDA tensors in
-    give CUDA ``status`` and ``residual`` out."""
+    point, ``objective`` the objective of every solve, ``uvw`` the parameters of the last fit, ``paths``.  CUDA tensors in
+    give CUDA ``status`` and ``residual`` out.
+
+    ``robust`` ("huber", "tukey" or (name, c); c defaults to 1.345 and 4.685) runs exactly ``iterations`` reweighted rounds
+    behind the plain fit (fewer only when sigma == 0.0) and adds ``weights`` (the weights of the last solve, CUDA for CUDA
+    in), ``scale`` (sigma per round) and ``rounds`` to info; ``residual``, ``rms`` and ``max`` are the last fit's.  Tukey can
+    take all weight from under a coefficient: that is the ValueError of the pivot ("not positive definite ... smoothing > 0
+    makes it so").  With ``correct`` every fit of the correction loop is the whole robust loop, started from ``weights``.
+    ``solve`` ("host", "device" or None, else ``scatter.FORCE_SOLVE``) pins the solve: None is the host solve for a plain
+    fit and, for a robust fit on the device path, the device solve when it covers the system and n hb^2 reaches
+    ``SOLVE_MIN_WORK``."""
     from . import project as _project
     from .spline import Spline
     del LAST_PATHS[:]
@@ -481,6 +665,13 @@ def fit_batch(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=No
     correct = int(correct)
     if correct and nDep not in (2, 3):
         raise ValueError("correct > 0 takes nDep 2 or 3 (Spline.project)")
+    robust = _robust(robust)
+    iterations = int(iterations)
+    if robust is not None and iterations < 1:
+        raise ValueError("robust takes iterations >= 1")
+    where = solve if solve is not None else FORCE_SOLVE
+    if where not in (None, "host", "device"):
+        raise ValueError("solve must be None, 'device' or 'host'")
     covered = max(order) <= DEVICE_MAX_K and nDep <= DEVICE_MAX_NDEP
     if on_device:
         if path == "host":
@@ -499,29 +690,57 @@ def fit_batch(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=No
         up = (lambda a: a.contiguous()) if on_device else (lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev))
     else:
         be, up = Host(), np.ascontiguousarray
+    if where == "device":
+        why = "the device solve belongs to the device path" if path != "device" else device_solve_scope(sh, nDep)
+        if why is not None:
+            raise ValueError(f"solve='device': {why}")
+    elif where is None:
+        hb = half_bandwidth(sh)
+        large = robust is not None and path == "device" and device_solve_scope(sh, nDep) is None and sh.n * hb * hb >= SOLVE_MIN_WORK
+        where = "device" if large else "host"
     uvw, points, weights = up(uvw), up(points), None if weights is None else up(weights)
     E = penalty_stencil(order, knots, m) if smoothing > 0.0 else None
+    E_there = be.put(E, np.float64) if E is not None and where == "device" else None
 
-    objective = []
-    for round_ in range(correct + 1):
-        res = assemble(be, sh, uvw, points, weights)
+    def one_fit(current):
+        """Assemble with the weights ``current``, solve, residuals, the objective's value."""
+        res = assemble(be, sh, uvw, points, current)
         counts = be.get(res["counts"])
         if smoothing == 0.0:
             at = _empty_support(sh, counts)
             if at is not None:
                 raise ValueError(f"fit_points: no point lies in the support of the coefficient {at}: the fit is not determined there; "
                                  "smoothing > 0 fills it in")
-        stencil, rhs = be.get(res["stencil"]), be.get(res["rhs"])
-        total = stencil if E is None else stencil + smoothing * E
-        coefs = solve(sh, total, rhs)
+        if where == "device":                                               # the product and the sum rounded on their own
+            total = res["stencil"] if E is None else res["stencil"] + E_there * smoothing
+            coefs = _solve(sh, total, res["rhs"], "device")
+        else:
+            stencil, rhs = be.get(res["stencil"]), be.get(res["rhs"])
+            total = stencil if E is None else stencil + smoothing * E
+            coefs = _solve(sh, total, rhs)
         residual = residuals(be, sh, coefs, uvw, points, res["key"])
         r = be.get(residual)
         ok = be.get(res["status"]) == 0
-        w = np.ones(int(ok.sum())) if weights is None else be.get(weights)[ok]
+        w = np.ones(int(ok.sum())) if current is None else be.get(current)[ok]
         value = float(np.sum(w * r[ok] * r[ok]))
         if E is not None:
             value += smoothing * float(np.sum(coefs.T * stencil_apply(order, sh.ncoef, E, coefs.T)))
         objective.append(value)
+        return res, counts, coefs, residual, r, ok
+
+    objective, scale, rounds, last = [], [], 0, weights
+    for round_ in range(correct + 1):
+        res, counts, coefs, residual, r, ok = one_fit(weights)
+        last = weights
+        if robust is not None:
+            counted = ok if weights is None else ok & (be.get(weights) > 0.0)
+            for _ in range(iterations):
+                scale.append(sigma(r[counted]))
+                if scale[-1] == 0.0:
+                    break
+                last = reweights(be, robust[0], robust[1] * scale[-1], residual, weights, res["key"])
+                res, counts, coefs, residual, r, ok = one_fit(last)
+                rounds += 1
         spline = Spline(nInd, nDep, order, sh.ncoef, knots, coefs.reshape((nDep,) + sh.ncoef), metadata)
         if round_ < correct:
             moved, _ = spline.project(points if on_device else be.get(points), guess=uvw if on_device else be.get(uvw),
@@ -533,8 +752,14 @@ def fit_batch(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=No
                 max=float(r[ok].max()) if ok.any() else float("nan"),
                 empty=int(np.count_nonzero((np.asarray(counts).reshape(sh.nc) == 0) & _positive(sh))), objective=objective,
                 uvw=uvw, paths=list(LAST_PATHS))
+    if robust is not None:
+        if last is None:
+            last = be.put(np.ones(N), np.float64)
+        info.update(weights=last, scale=scale, rounds=rounds)
     if not on_device and path == "device":
         info.update(status=be.get(status), residual=r, uvw=be.get(uvw))
+        if robust is not None:
+            info.update(weights=be.get(last))
     return spline, info
 
 
@@ -544,10 +769,11 @@ def _positive(sh):
     return wide[0] if sh.nind == 1 else wide[0][:, None] & wide[1][None, :]
 
 
-def fit_points(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, _path=None):
+def fit_points(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, robust=None,
+               iterations=8, solve=None, _path=None):
     """``Spline.fit_points``: the spline; one RuntimeWarning when points were excluded."""
     spline, info = fit_batch(uvw, points, order, knots, weights=weights, smoothing=smoothing, penalty=penalty, correct=correct,
-                             metadata=metadata, _path=_path)
+                             metadata=metadata, robust=robust, iterations=iterations, solve=solve, _path=_path)
     flagged = info["status"] != 0
     count = int(flagged.sum())
     if count:

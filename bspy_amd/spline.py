@@ -252,7 +252,8 @@ class Spline:
         return _fitting.least_squares(uValues, dataPoints, order, knots, compression, tolerance, fixEnds, metadata, **kwargs)
 
     @staticmethod
-    def fit_points(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, **kwargs):
+    def fit_points(uvw, points, order, knots, weights=None, smoothing=0.0, penalty=None, correct=0, metadata={}, robust=None,
+                   iterations=8, solve=None, **kwargs):
         """Least-squares fit of a spline to scattered data (an extension beyond the reference's API; the gridded call is
         ``least_squares``).  uvw: (nInd, N) parameters, or (N,) for a curve; points: (nDep, N); NumPy float32 / float64 or
         torch CUDA tensors of those types (float32 is widened first).  order and knots are required.  weights: (N,), all
@@ -271,10 +272,19 @@ class Spline:
         RuntimeWarning (``scatter.fit_batch`` returns the status bits, residuals and objective values).  smoothing == 0
         with a coefficient that has no data in its support raises ValueError, as does a matrix that is not positive
         definite.  Curves and surfaces of orders 2 to 6; nInd 3 raises NotImplementedError (deliberate scope).
+
+        ``robust="huber"`` / ``"tukey"`` / ``(name, c)`` makes the fit robust against gross outliers: behind the plain fit
+        run exactly ``iterations`` reweighted rounds (residuals, sigma = 1.4826 x their lower median, the loss's weights
+        times ``weights``, assemble, solve; fewer rounds only when sigma == 0.0; no convergence test, so the result is a
+        function of the inputs alone).  c defaults to 1.345 (Huber) and 4.685 (Tukey).  Tukey gives a point beyond
+        c sigma the weight 0.0 and can so take all weight from under a coefficient: that raises the ValueError of a matrix
+        that is not positive definite.  ``solve="host"`` / ``"device"`` pins the banded solve; None is the host solve for a
+        plain fit and, for a robust fit on the device path, the device solve (``bsk_scatter_solve``: the host's bytes) once
+        the system is large enough for it (``scatter.SOLVE_MIN_WORK``).
         ``_path="device"`` / ``"host"`` pins the path (tests, measurements)."""
         from . import scatter as _scatter
         return _scatter.fit_points(uvw, points, order, knots, weights=weights, smoothing=smoothing, penalty=penalty, correct=correct,
-                                   metadata=metadata, **kwargs)
+                                   metadata=metadata, robust=robust, iterations=iterations, solve=solve, **kwargs)
 
     # ------------------------------------------------------------------ spline to spline (bspy_amd/refinement.py)
     def insert_knots(self, newKnots, **kwargs):

@@ -791,8 +791,17 @@ const char *bsk_contour_last_kernel(void);
  *   The kernels cover K0, K1 in 2 .. 4 and ndep 1 .. 4 (gram) and K0, K1 in 2 .. 4 (residual), the host twins orders
  *   2 .. 6 and any ndep; anything else is BSK_ERR_UNSUPPORTED.  The device entry points take device buffers on the
  *   current device and enqueue on `stream`.  No atomics, no waiting; the host drivers and the kernels give the same bits.
- *   The name of the last call: "scatter_key", "scatter_gram", "scatter_cell", "scatter_fold", "scatter_residual" or the
- *   same behind "host ", or "host scatter_solve".
+ *   solve (device) : the twin of solve_host for ndep 1 .. 4 and half bandwidths hb = min((K0 - 1) n1 + K1 - 1, n - 1) up to
+ *              4095 (anything else is BSK_ERR_UNSUPPORTED and stays with solve_host): stencil, rhs, coefs[ndep][n], work
+ *              and the one int64 bad_row are device buffers; work holds at least the doubles that bsk_scatter_solve_work
+ *              reports (2 n (hb + 1) + ndep n) and needs no contents.  The call enqueues launches and returns; coefs are
+ *              the bytes of solve_host, and *bad_row is -1 or the first row whose pivot is not > 0 (coefs then hold
+ *              nothing of use).
+ *   reweight : the robust weights of a reweighted fit.  loss 0 (Huber): r <= s ? w0 : w0 (s / r); loss 1 (Tukey):
+ *              r < s ? w0 (q q), q = 1 - (r / s)(r / s) : 0; r = residual[i], w0 = weights[i] (1.0 for NULL), s =
+ *              threshold > 0; a point with key_in[i] < 0 keeps w0.
+ *   The name of the last call: "scatter_key", "scatter_gram", "scatter_cell", "scatter_fold", "scatter_residual",
+ *   "scatter_reweight" or the same behind "host ", or "host scatter_solve", or "scatter_solve".
  */
 bsk_status bsk_scatter_key_host(int nind, int K0, int K1, int64_t n0, int64_t n1, const double *knots0, const double *knots1,
                                 int64_t top0, int64_t top1, int ndep, const double *uvw, const double *points,
@@ -824,6 +833,18 @@ bsk_status bsk_scatter_residual(int nind, int K0, int K1, int64_t n0, int64_t n1
                                 const int64_t *key_in, int64_t npts, double *residual_out, void *stream);
 bsk_status bsk_scatter_solve_host(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil,
                                   const double *rhs, double *coefs, int64_t *bad_row);
+/* the device solve and the robust weights (the parameter lists start on a line of their own) */
+bsk_status bsk_scatter_solve_work(
+    int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, int64_t *doubles);
+bsk_status bsk_scatter_solve(
+    int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil, const double *rhs, double *coefs,
+    double *work, int64_t work_doubles, int64_t *bad_row, void *stream);
+bsk_status bsk_scatter_reweight_host(
+    int loss, double threshold, const double *residual, const double *weights, const int64_t *key_in, int64_t npts,
+    double *weights_out);
+bsk_status bsk_scatter_reweight(
+    int loss, double threshold, const double *residual, const double *weights, const int64_t *key_in, int64_t npts,
+    double *weights_out, void *stream);
 const char *bsk_scatter_last_kernel(void);
 
 /*
@@ -905,12 +926,17 @@ const char *bsk_last_kernel(bsk_spline s);
  *                           LDS of a CU.  mode 0 writes `pattern` over it; mode 1 (positive control) reads it without
  *                           writing it and adds the words that differ from `pattern` to *mismatches.  Synchronises
  *                           `stream` before it returns.
+ *   bsk_debug_scatter_solve : bsk_scatter_solve stage by stage for tools/scatter_time.py: `stages` is a sum of 1 (the band
+ *                           expansion), 2 (the factorisation), 4 (the forward substitution), 8 (the backward one).
  */
 #ifdef BSK_INTERNAL
 bsk_status bsk_debug_probe(bsk_spline s, int mode, int blocks_per_cu, int threads, int64_t lds_bytes,
                            const void *u, const void *v, int64_t n, void *out, void *stream);
 bsk_status bsk_debug_stage_times(bsk_spline s, int enable, float *ms, const char **names, int cap, int *count);
 bsk_status bsk_debug_fill_lds(bsk_spline s, uint32_t pattern, int mode, int64_t *mismatches, void *stream);
+bsk_status bsk_debug_scatter_solve(int nind, int K0, int K1, int64_t n0, int64_t n1, int ndep, const double *stencil,
+                                   const double *rhs, double *coefs, double *work, int64_t work_doubles, int64_t *bad_row,
+                                   int stages, void *stream);
 #endif
 
 #ifdef __cplusplus

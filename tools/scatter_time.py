@@ -1,7 +1,7 @@
 """
 Timings of Spline.fit_points / scatter.fit_batch.
 
-    python tools/scatter_time.py [--quick] [--out scatter_time.json]
+    python tools/scatter_time.py [--quick] [--solves] [--out scatter_time.json]
 
   calls      ``fit_batch`` on both paths, NumPy in, for 10^4 .. 10^7 points on the bench surface's shape (cfg2: 64 x 64
              bicubic, nDep 3) and on a cubic curve of 64 coefficients, nDep 3: the host / device table behind
@@ -12,6 +12,12 @@ Timings of Spline.fit_points / scatter.fit_batch.
   yardstick  the same stencil and right-hand side formed by ``torch.index_add_`` on the device from the same basis values
              (float atomics: not reproducible, the sums differ in the last bits); the largest difference from the kernels'
              stencil relative to its largest entry is printed, not asserted.
+  solves     (``--solves``: this table alone) the banded solve of 16^2, 32^2, 64^2 and 128^2 bicubic coefficients, a 48 x 48
+             surface of orders (3, 4) and cubic curves of 64 and 4096 coefficients, nDep 3, from 10^5 points:
+             ``bsk_scatter_solve`` stage by stage between HIP events (``bsk_debug_scatter_solve``: the band expansion, the
+             factorisation, the forward and the backward substitution) and whole, ``bsk_scatter_solve_host`` in the same run,
+             and a robust call (Huber, 8 rounds, NumPy in, device path) with each solve.  The table behind
+             scatter.SOLVE_MIN_WORK.
 Every figure is the range over `--repeats` runs.
 """
 import argparse
@@ -28,6 +34,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cases  # noqa: E402
+from bspy_amd import _native as nv  # noqa: E402
 from bspy_amd import scatter  # noqa: E402
 from refine_time import wall  # noqa: E402
 
@@ -111,14 +118,79 @@ def spread(rows):
     return {k: [min(r[k] for r in rows), max(r[k] for r in rows)] for k in rows[0]}
 
 
+def clamped(order, ncoef):
+    return [np.concatenate(((k - 1) * [0.0], np.linspace(0, 1, n - k + 2), (k - 1) * [1.0])) for k, n in zip(order, ncoef)]
+
+
+def solves(repeats, out):
+    """The table of the solves: one JSON line per shape."""
+    import ctypes
+    rng = np.random.default_rng(1)
+    L = nv.lib()
+    shapes = [(f"bicubic {m} x {m}", (4, 4), (m, m)) for m in (16, 32, 64, 128)]
+    shapes += [("orders (3, 4), 48 x 48", (3, 4), (48, 48)), ("cubic curve, 64", (4,), (64,)), ("cubic curve, 4096", (4,), (4096,))]
+    results = []
+    for name, order, ncoef in shapes:
+        knots = clamped(order, ncoef)
+        sh = scatter.Shape(order, knots)
+        n, nDep = 10 ** 5, 3
+        uvw, pts = rng.random((len(order), n)), rng.standard_normal((nDep, n))
+        be = scatter.Device.current()
+        res = scatter.assemble(be, sh, *[torch.from_numpy(x).cuda() for x in (uvw, pts)], None)
+        E = scatter.penalty_stencil(order, knots, 1)
+        stencil = (res["stencil"] + torch.from_numpy(E).cuda() * 1e-6).contiguous()
+        rhs = res["rhs"]
+        hb = scatter.half_bandwidth(sh)
+        row = dict(case=name, n=sh.n, hb=hb, work=sh.n * hb * hb)
+        need = np.zeros(1, np.int64)
+        nv.check(L.bsk_scatter_solve_work(sh.nind, *sh.K01, *sh.n01, nDep, need.ctypes.data_as(nv._i64p)))
+        work = torch.empty(int(need[0]), dtype=torch.float64, device="cuda")
+        coefs, bad = torch.empty((nDep, sh.n), dtype=torch.float64, device="cuda"), torch.zeros(1, dtype=torch.int64, device="cuda")
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def stage(mask):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            nv.check(L.bsk_debug_scatter_solve(sh.nind, *sh.K01, *sh.n01, nDep, stencil.data_ptr(), rhs.data_ptr(), coefs.data_ptr(),
+                                               work.data_ptr(), int(need[0]), bad.data_ptr(), mask, stream))
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b) * 1e-3
+
+        stage(15)
+        runs = [dict(band=stage(1), factor=stage(2), forward=stage(4), backward=stage(8), device_solve=stage(15)) for _ in range(repeats)]
+        assert int(bad.cpu()[0]) == -1
+        row.update(spread(runs))
+        hs, hr = stencil.cpu().numpy(), rhs.cpu().numpy()
+        host = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            want = scatter.solve(sh, hs, hr)
+            host.append(time.perf_counter() - t0)
+        row["host_solve"] = [min(host), max(host)]
+        row["same_bytes"] = bool(np.array_equal(want.view(np.int64), coefs.cpu().numpy().view(np.int64)))
+        pts[:, ::10] += 50.0
+        for where in ("device", "host"):
+            row[f"robust_{where}_solve"] = wall(lambda: scatter.fit_batch(uvw, pts, order, knots, smoothing=1e-6, penalty=1, robust="huber",
+                                                                         solve=where, _path="device"), repeats)
+        results.append(row)
+        print(json.dumps(row), flush=True)
+        if out:
+            with open(out, "w") as f:
+                json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--solves", action="store_true")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     torch.zeros(1 << 24, device="cuda").sum().item()                 # clocks up
+    if a.solves:
+        return solves(a.repeats, a.out)
     _, _, order2, ncoef2, knots2, _, _ = cases.bench_spline(2)
     curve_knots = [np.concatenate((4 * [0.0], np.linspace(0, 1, 62)[1:-1], 4 * [1.0]))]
     shapes = [("bench surface cfg2 (bicubic 64 x 64, nDep 3)", tuple(order2), [np.asarray(k, np.float64) for k in knots2]),
