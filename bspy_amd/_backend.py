@@ -136,6 +136,13 @@ class Host:
     def arange(self, n):
         return np.arange(n, dtype=np.int64)
 
+    def sort(self, a):
+        return np.sort(a)
+
+    def unique(self, a):
+        values, inverse = np.unique(a, return_inverse=True)
+        return values, inverse.reshape(-1).astype(np.int64)
+
     def cat(self, arrays):
         return np.concatenate(arrays)
 
@@ -218,6 +225,13 @@ class Device:
 
     def arange(self, n):
         return self.torch.arange(n, dtype=self.torch.int64, device=self.dev)
+
+    def sort(self, a):
+        return self.torch.sort(a).values.contiguous()
+
+    def unique(self, a):
+        values, inverse = self.torch.unique(a, sorted=True, return_inverse=True)      # ascending, as np.unique
+        return values.contiguous(), inverse.reshape(-1)
 
     def cat(self, arrays):
         return self.torch.cat(list(arrays))

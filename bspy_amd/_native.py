@@ -38,6 +38,8 @@ PRODUCT_SYMBOLS = (
     "bsk_roots_extract_host", "bsk_roots_flag_host", "bsk_roots_flag", "bsk_roots_isolate_host", "bsk_roots_isolate", "bsk_roots_last_kernel",
     "bsk_project_seed_host", "bsk_project_seed", "bsk_project_newton_host", "bsk_project_newton", "bsk_project_last_kernel",
     "bsk_contour_flag_host", "bsk_contour_flag", "bsk_contour_march_host", "bsk_contour_march", "bsk_contour_last_kernel",
+    "bsk_iso_flag_host", "bsk_iso_flag", "bsk_iso_walk_host", "bsk_iso_walk", "bsk_iso_leaf_host", "bsk_iso_leaf", "bsk_iso_vertex_host",
+    "bsk_iso_vertex", "bsk_iso_last_kernel",
     "bsk_rays_boxes_host", "bsk_rays_boxes", "bsk_rays_count_host", "bsk_rays_count", "bsk_rays_emit_host", "bsk_rays_emit",
     "bsk_rays_isolate_host", "bsk_rays_isolate", "bsk_rays_reduce_host", "bsk_rays_reduce", "bsk_rays_last_kernel",
     "bsk_ssx_count_host", "bsk_ssx_count", "bsk_ssx_emit_host", "bsk_ssx_emit", "bsk_ssx_isolate_host", "bsk_ssx_isolate",
@@ -214,6 +216,20 @@ def lib():
     L.bsk_contour_march.argtypes = march_c + [_vp]
     L.bsk_contour_last_kernel.argtypes = []
     L.bsk_contour_last_kernel.restype = ctypes.c_char_p
+    grid_i = [ctypes.c_int] * 3 + [_vp] + [_i64] * 7 + [_vp, _vp, _vp, _vp, _i64, _vp]
+    walk_i = grid_i + [_vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, _vp, _vp]
+    leaf_i = grid_i + [_vp, _i64, ctypes.c_int, ctypes.c_int, _vp, _i64, _vp, _vp, _vp]
+    vertex_i = grid_i + [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, _vp]
+    L.bsk_iso_flag_host.argtypes = grid_i + [_vp, _vp]
+    L.bsk_iso_flag.argtypes = grid_i + [_vp, _vp, _vp]
+    L.bsk_iso_walk_host.argtypes = walk_i
+    L.bsk_iso_walk.argtypes = walk_i + [_vp]
+    L.bsk_iso_leaf_host.argtypes = leaf_i
+    L.bsk_iso_leaf.argtypes = leaf_i + [_vp]
+    L.bsk_iso_vertex_host.argtypes = vertex_i
+    L.bsk_iso_vertex.argtypes = vertex_i + [_vp]
+    L.bsk_iso_last_kernel.argtypes = []
+    L.bsk_iso_last_kernel.restype = ctypes.c_char_p
     surface = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]
     rays = [_vp, _vp, _vp, _i64]
     search = surface + rays + [ctypes.c_double, ctypes.c_double, _i64, ctypes.c_int, _vp]
@@ -280,7 +296,7 @@ def lib():
     for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_rays_last_kernel",
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_iso_last_kernel", "bsk_rays_last_kernel",
                         "bsk_ssx_last_kernel", "bsk_scatter_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L

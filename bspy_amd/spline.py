@@ -555,6 +555,20 @@ class Spline:
         from . import contours as _contours
         return _contours.contours(self, tolerance=tolerance, depth=depth, **kwargs)
 
+    def isosurface(self, level=0.0, tolerance=None, depth=None, normals=False, **kwargs):
+        """The level surface {f = level} of a scalar spline in three variables (nInd == 3, nDep == 1, orders 2 .. 4; the
+        reference has nothing for it): (vertices (n, 3) float64, triangles (m, 3) int64), the vertices parameter values
+        (u, v, w), every triangle's right-hand normal pointing into f >= level; with ``normals=True`` a third array (n, 3),
+        the normalised gradient at every vertex (from ``jacobian``; NaN where it vanishes).  Every knot cell carries a
+        lattice of 2^depth leaves per axis (depth 0 .. 6; default 3, or chosen from ``tolerance``), every leaf is cut into
+        six tetrahedra, and the surface is decided on that lattice: features smaller than a leaf are missed without a flag
+        and nothing is certified; what is computed is stated in bspy_amd/isosurface.py.  Where no lattice node value is
+        exactly zero the mesh is a consistently oriented 2-manifold, closed but for the domain boundary and zero cells.
+        Results are bitwise reproducible and the same on both paths.  ``_path="device"`` / ``"host"`` pins the path.
+        ``bspy_amd.isosurface.extract_batch`` extracts many fields or many levels of one field in one launch sequence."""
+        from . import isosurface as _isosurface
+        return _isosurface.isosurface(self, level=level, tolerance=tolerance, depth=depth, normals=normals, **kwargs)
+
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
 

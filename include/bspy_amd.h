@@ -764,6 +764,57 @@ bsk_status bsk_contour_march(int K0, int K1, const double *rows, int64_t nrows, 
 const char *bsk_contour_last_kernel(void);
 
 /*
+ * Level surfaces {f = 0} of scalar splines in three variables (Spline.isosurface; the statement of the lattice, the
+ * tetrahedra, the vertices and the arithmetic is in bspy_amd/isosurface.py and DESIGN.md section 25).  The family keeps no
+ * handle.  The caller brings the three variables to Bezier form with the band operator: rows[nrows][R0][R1][R2] (doubles),
+ * cell (i, j, k) is the K0 x K1 x K2 window at first0[i], first1[j], first2[k] and covers [breaks0[i], breaks0[i + 1]] x
+ * [breaks1[j], breaks1[j + 1]] x [breaks2[k], breaks2[k + 1]]; no knot is a jump, so adjacent cells share their end plane.
+ * There are nfields fields: field b is rows[b] (levels NULL, nrows == nfields) or rows[0] - levels[b] (nrows == 1);
+ * scale[nfields] = max |coefficient| of the field.  A cell's flat index is ((field * nc0 + i) * nc1 + j) * nc2 + k; every
+ * cell carries 2^depth leaves per axis, depth in 0 .. 6, and a leaf's flat index is ((field * NL0 + I) * NL1 + J) * NL2 + K
+ * with NL = nc << depth.  A window that leaves the rows, or an index that is no cell, leaf or lattice edge, gives nothing
+ * (a vertex: NaN) instead of a read out of bounds.
+ *   bsk_iso_flag(_host)   : zero[nfields][nc0][nc1][nc2] (bytes) = 1 where every coefficient of the cell is below scale eps;
+ *                           cand (same shape) = 1 unless the cell is a zero cell or its coefficients are all above tau or
+ *                           all below -tau, tau = 32 (K0 + K1 + K2) eps scale.
+ *   bsk_iso_walk(_host)   : cand[ncand] (int64, flat indices of the flagged cells, ncand >= 1); wave = candidate * 8^split +
+ *                           top box, split in 0 .. depth.  emit == 0: counts[waves] (int32) = the leaves of the wave's box
+ *                           that the sign test keeps.  emit != 0: offsets[waves] (int64, the exclusive sum of counts),
+ *                           total = the sum (>= 1), leaves[total] (int64) = their flat indices in the order of the walk.
+ *   bsk_iso_leaf(_host)   : leaves[nleaves] (int64, ascending).  emit == 0: counts[nleaves] (int32) = the triangles of the
+ *                           leaf, and status[nfields][nc0][nc1][nc2] (bytes, zeroed by the caller) = 2 on the cell of a
+ *                           leaf with a node value of exactly 0.0.  emit != 0: offsets[nleaves], total (>= 1) and
+ *                           tris[total][3] (int64) = the lattice-edge keys of the triangles' vertices, the right-hand
+ *                           normal into f >= 0.  Pointers of the other pass may be NULL.
+ *   bsk_iso_vertex(_host) : keys[n], fields[n] (int64) -> xyz[n][3] = (u, v, w) of the crossed lattice edge.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1, K2 in 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above).  No atomics, no waiting, every loop has a compile-time bound; the host drivers and the
+ *   kernels give the same bits, and the triangles do not depend on split.
+ *   bsk_iso_last_kernel   : "iso_flag", "iso_walk count", "iso_walk emit", "iso_leaf count", "iso_leaf emit", "iso_vertex"
+ *                           or the same behind "host ".
+ */
+#define BSK_ISO_GRID                                                                                                          \
+    int K0, int K1, int K2, const double *rows, int64_t nrows, int64_t R0, int64_t R1, int64_t R2, int64_t nc0, int64_t nc1,   \
+        int64_t nc2, const int32_t *first0, const int32_t *first1, const int32_t *first2, const double *levels,               \
+        int64_t nfields, const double *scale
+bsk_status bsk_iso_flag_host(BSK_ISO_GRID, uint8_t *cand, uint8_t *zero);
+bsk_status bsk_iso_flag(BSK_ISO_GRID, uint8_t *cand, uint8_t *zero, void *stream);
+bsk_status bsk_iso_walk_host(BSK_ISO_GRID, const int64_t *cand, int64_t ncand, int depth, int split, int emit,
+                             const int64_t *offsets, int64_t total, int32_t *counts, int64_t *leaves);
+bsk_status bsk_iso_walk(BSK_ISO_GRID, const int64_t *cand, int64_t ncand, int depth, int split, int emit, const int64_t *offsets,
+                        int64_t total, int32_t *counts, int64_t *leaves, void *stream);
+bsk_status bsk_iso_leaf_host(BSK_ISO_GRID, const int64_t *leaves, int64_t nleaves, int depth, int emit, const int64_t *offsets,
+                             int64_t total, int32_t *counts, uint8_t *status, int64_t *tris);
+bsk_status bsk_iso_leaf(BSK_ISO_GRID, const int64_t *leaves, int64_t nleaves, int depth, int emit, const int64_t *offsets,
+                        int64_t total, int32_t *counts, uint8_t *status, int64_t *tris, void *stream);
+bsk_status bsk_iso_vertex_host(BSK_ISO_GRID, const double *breaks0, const double *breaks1, const double *breaks2,
+                               const int64_t *keys, const int64_t *fields, int64_t n, int depth, double *xyz);
+bsk_status bsk_iso_vertex(BSK_ISO_GRID, const double *breaks0, const double *breaks1, const double *breaks2, const int64_t *keys,
+                          const int64_t *fields, int64_t n, int depth, double *xyz, void *stream);
+#undef BSK_ISO_GRID
+const char *bsk_iso_last_kernel(void);
+
+/*
  * Scattered least squares (Spline.fit_points; the statement of the key, the units, the Gram slabs, the trees, the fold
  * and the solve is in bspy_amd/scatter.py and DESIGN.md section 24).  The family keeps no handle.  Variable d has order
  * K_d, n_d coefficients and the n_d + K_d knots knots_d (doubles); a curve has nind = 1, K1 = n1 = 1, knots1 = {0, 1} and
