@@ -1,6 +1,6 @@
 """
-What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``, ``isosurface``, ``rays``, ``surfaces``) share, written
-once: the host band loop, the per-axis Bezier plan (``JumpFreePlan``: the one of ``contours``, ``isosurface`` and ``surfaces``, which refuses
+What the cell families (``roots``, ``roots2``, ``roots3``, ``project``, ``contours``, ``isosurface``, ``mesh``, ``rays``, ``surfaces``) share, written
+once: the host band loop, the per-axis Bezier plan (``JumpFreePlan``: the one of ``contours``, ``isosurface``, ``mesh`` and ``surfaces``, which refuses
 a jump), the zero-cell table, and ``zeros2_batch`` / ``zeros3_batch`` whole, on the two backends of bspy_amd/_backend.py
 (``Host``, ``Device``, the path switch: passed on under their names here).  The layer that ``rays`` and ``surfaces`` put on
 top, one surface's tables and the passes of the pair search, is written once in bspy_amd/_pairs.py.
@@ -91,7 +91,7 @@ class TensorPlan:
 
 class JumpFreePlan(TensorPlan):
     """``TensorPlan`` that refuses a jump: an interior knot of multiplicity >= K.  A subclass sets ``who``,
-    the caller's name, and ``what``, the thing that cannot cross the knot (``contours``: a contour; ``surfaces``: a curve; ``isosurface``: a surface)."""
+    the caller's name, and ``what``, the thing that cannot cross the knot (``contours``: a contour; ``surfaces``: a curve; ``isosurface``: a surface; ``mesh``: a mesh)."""
     who = what = None
 
     def __init__(self, order, knots):

@@ -40,6 +40,8 @@ PRODUCT_SYMBOLS = (
     "bsk_contour_flag_host", "bsk_contour_flag", "bsk_contour_march_host", "bsk_contour_march", "bsk_contour_last_kernel",
     "bsk_iso_flag_host", "bsk_iso_flag", "bsk_iso_walk_host", "bsk_iso_walk", "bsk_iso_leaf_host", "bsk_iso_leaf", "bsk_iso_vertex_host",
     "bsk_iso_vertex", "bsk_iso_last_kernel",
+    "bsk_mesh_bound_host", "bsk_mesh_bound", "bsk_mesh_count_host", "bsk_mesh_count", "bsk_mesh_emit_host", "bsk_mesh_emit",
+    "bsk_mesh_vertex_host", "bsk_mesh_vertex", "bsk_mesh_last_kernel",
     "bsk_rays_boxes_host", "bsk_rays_boxes", "bsk_rays_count_host", "bsk_rays_count", "bsk_rays_emit_host", "bsk_rays_emit",
     "bsk_rays_isolate_host", "bsk_rays_isolate", "bsk_rays_reduce_host", "bsk_rays_reduce", "bsk_rays_last_kernel",
     "bsk_ssx_count_host", "bsk_ssx_count", "bsk_ssx_emit_host", "bsk_ssx_emit", "bsk_ssx_isolate_host", "bsk_ssx_isolate",
@@ -230,6 +232,18 @@ def lib():
     L.bsk_iso_vertex.argtypes = vertex_i + [_vp]
     L.bsk_iso_last_kernel.argtypes = []
     L.bsk_iso_last_kernel.restype = ctypes.c_char_p
+    net_m = [ctypes.c_int, ctypes.c_int, _vp, _i64, ctypes.c_int] + [_i64] * 4 + [_vp, _vp]
+    quad_m = [_vp, _i64, _i64, _i64, _vp, ctypes.c_int, ctypes.c_int, _i64, _i64, _i64]
+    L.bsk_mesh_bound_host.argtypes = net_m + [ctypes.c_double, ctypes.c_int, _vp, _vp, _vp]
+    L.bsk_mesh_bound.argtypes = net_m + [ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]
+    L.bsk_mesh_count_host.argtypes = quad_m + [_vp]
+    L.bsk_mesh_count.argtypes = quad_m + [_vp, _vp]
+    L.bsk_mesh_emit_host.argtypes = quad_m + [_vp, _i64, _vp]
+    L.bsk_mesh_emit.argtypes = quad_m + [_vp, _i64, _vp, _vp]
+    L.bsk_mesh_vertex_host.argtypes = net_m + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]
+    L.bsk_mesh_vertex.argtypes = net_m + [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]
+    L.bsk_mesh_last_kernel.argtypes = []
+    L.bsk_mesh_last_kernel.restype = ctypes.c_char_p
     surface = [ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _i64, _vp, _vp]
     rays = [_vp, _vp, _vp, _i64]
     search = surface + rays + [ctypes.c_double, ctypes.c_double, _i64, ctypes.c_int, _vp]
@@ -296,7 +310,7 @@ def lib():
     for name in SYMBOLS + ROOTS2_SYMBOLS + ROOTS3_SYMBOLS:
         if name not in ("bsk_version", "bsk_last_error", "bsk_last_kernel", "bsk_fit_last_kernel", "bsk_band_last_kernel",
                         "bsk_product_last_kernel", "bsk_scan_last_kernel", "bsk_sum_last_kernel", "bsk_roots_last_kernel",
-                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_iso_last_kernel", "bsk_rays_last_kernel",
+                        "bsk_roots2_last_kernel", "bsk_roots3_last_kernel", "bsk_project_last_kernel", "bsk_contour_last_kernel", "bsk_iso_last_kernel", "bsk_mesh_last_kernel", "bsk_rays_last_kernel",
                         "bsk_ssx_last_kernel", "bsk_scatter_last_kernel"):
             getattr(L, name).restype = ctypes.c_int
     _lib = L

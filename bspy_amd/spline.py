@@ -569,6 +569,21 @@ class Spline:
         from . import isosurface as _isosurface
         return _isosurface.isosurface(self, level=level, tolerance=tolerance, depth=depth, normals=normals, **kwargs)
 
+    def triangulate(self, tolerance, parameters=False, normals=False, **kwargs):
+        """A watertight triangle mesh of a surface (nInd == 2, nDep 1 .. 3, orders 2 .. 4; the reference has this only in
+        its viewer's tessellation shaders): (xyz (n, nDep) float64, triangles (m, 3) int64, counter-clockwise in (u, v)),
+        then the parameters uv (n, 2) with ``parameters=True`` and the unit normals (n, 3) with ``normals=True`` (nDep 3).
+        Every knot cell carries 2^a x 2^b grid quads, the levels taken from bounds of its second derivatives so that every
+        point of every triangle is within ``tolerance`` of the surface point with the same parameters (plus the counted
+        rounding slack of bspy_amd/mesh.py), and every cell edge takes the larger level of its two cells, so the triangles
+        tile the domain without cracks or T-junctions.  ``max_level`` (default 8, at most 10) caps the levels: a cell that
+        needs more is meshed at the cap with one RuntimeWarning.  ``max_triangles`` (default 2^28) raises a ValueError
+        before the triangles are written.  ``metadata['negateNormal']`` flips the triangles and the normals.  Seams and
+        poles are not welded.  Results are bitwise reproducible and the same on both paths.  ``_path="device"`` / ``"host"``
+        pins the path.  ``bspy_amd.mesh.triangulate_batch`` meshes many nets on the same knots in one launch sequence."""
+        from . import mesh as _mesh
+        return _mesh.triangulate(self, tolerance, parameters=parameters, normals=normals, **kwargs)
+
     def __add__(self, other):
         return self.add(other, self._common(other)) if isinstance(other, Spline) else self.translate(other)
 

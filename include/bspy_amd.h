@@ -815,6 +815,50 @@ bsk_status bsk_iso_vertex(BSK_ISO_GRID, const double *breaks0, const double *bre
 const char *bsk_iso_last_kernel(void);
 
 /*
+ * Triangle meshes of parametric surfaces within a tolerance (Spline.triangulate; the statement of the bounds, the levels,
+ * the keys, the triangles and the vertices is in bspy_amd/mesh.py and DESIGN.md section 26).  The family keeps no handle.
+ * The caller brings the two variables to Bezier form with the band operator: rows[nmem][ndep][R0][R1] (doubles, ndep in
+ * 1 .. 3), cell (i, j) is the K0 x K1 window at first0[i], first1[j] and covers [breaks0[i], breaks0[i + 1]] x
+ * [breaks1[j], breaks1[j + 1]].  A window that leaves the rows, or an index that is no cell, quad or key, gives nothing (a
+ * vertex: NaN) instead of a read out of bounds.
+ *   bsk_mesh_bound(_host) : per (member, cell): Q[.][3] = (Quu, Qvv, Quv), the squared bounds of the second derivatives
+ *                           in the cell's own parameters; lev[.][2] (int32) = (a, b), the least levels in 0 .. max_level
+ *                           (<= 10) with max(Quu, Quv) <= T 16^a and max(Qvv, Quv) <= T 16^b; status[.] (bytes) = 1
+ *                           where there is none (the level is max_level then).  T = (2 tolerance)^2.
+ *   bsk_mesh_count(_host) : qoff[ncells + 1] (int64) = the exclusive sums of 2^(a + b), ncells = nmem nc0 nc1; 2^steps >=
+ *                           ncells; span >= 2^(the largest difference of two levels).  For the quads start .. start + n - 1
+ *                           of nquads = qoff[ncells]: counts[quad] (int32) = 2, or the segments on its four sides.
+ *   bsk_mesh_emit(_host)  : offsets[nquads] (int64, the exclusive sums of counts), total (>= 1), tris[total][3] (int64) =
+ *                           the keys of the triangles' vertices, counter-clockwise in (u, v); key = (X << 31) | Y,
+ *                           X = (i << 11) + the local coordinate in units of 2^-11 of the cell.
+ *   bsk_mesh_vertex(_host): keys[n], members[n] (int64) -> uv[n][2], xyz[n][ndep] and, unless NULL (ndep 3 only),
+ *                           normals[n][3] = S_u x S_v in the cell's own parameters, not normalised.
+ *   The device entry points take device buffers on the current device and enqueue on `stream`; K0, K1 in 2 .. 4
+ *   (BSK_ERR_UNSUPPORTED above).  No atomics, no waiting, no LDS, every loop has a compile-time or launch-uniform bound; the
+ *   host drivers and the kernels give the same bits.
+ *   bsk_mesh_last_kernel  : "mesh_bound", "mesh_count", "mesh_emit", "mesh_vertex" or the same behind "host ".
+ */
+#define BSK_MESH_NET                                                                                                          \
+    int K0, int K1, const double *rows, int64_t nmem, int ndep, int64_t R0, int64_t R1, int64_t nc0, int64_t nc1,             \
+        const int32_t *first0, const int32_t *first1
+#define BSK_MESH_QUADS                                                                                                        \
+    const int64_t *qoff, int64_t ncells, int64_t nc0, int64_t nc1, const int32_t *lev, int steps, int span, int64_t start,    \
+        int64_t n, int64_t nquads
+bsk_status bsk_mesh_bound_host(BSK_MESH_NET, double T, int max_level, double *Q, int32_t *lev, uint8_t *status);
+bsk_status bsk_mesh_bound(BSK_MESH_NET, double T, int max_level, double *Q, int32_t *lev, uint8_t *status, void *stream);
+bsk_status bsk_mesh_count_host(BSK_MESH_QUADS, int32_t *counts);
+bsk_status bsk_mesh_count(BSK_MESH_QUADS, int32_t *counts, void *stream);
+bsk_status bsk_mesh_emit_host(BSK_MESH_QUADS, const int64_t *offsets, int64_t total, int64_t *tris);
+bsk_status bsk_mesh_emit(BSK_MESH_QUADS, const int64_t *offsets, int64_t total, int64_t *tris, void *stream);
+bsk_status bsk_mesh_vertex_host(BSK_MESH_NET, const double *breaks0, const double *breaks1, const int64_t *keys,
+                                const int64_t *members, int64_t n, double *uv, double *xyz, double *normals);
+bsk_status bsk_mesh_vertex(BSK_MESH_NET, const double *breaks0, const double *breaks1, const int64_t *keys, const int64_t *members,
+                           int64_t n, double *uv, double *xyz, double *normals, void *stream);
+#undef BSK_MESH_NET
+#undef BSK_MESH_QUADS
+const char *bsk_mesh_last_kernel(void);
+
+/*
  * Scattered least squares (Spline.fit_points; the statement of the key, the units, the Gram slabs, the trees, the fold
  * and the solve is in bspy_amd/scatter.py and DESIGN.md section 24).  The family keeps no handle.  Variable d has order
  * K_d, n_d coefficients and the n_d + K_d knots knots_d (doubles); a curve has nind = 1, K1 = n1 = 1, knots1 = {0, 1} and
