@@ -12,6 +12,14 @@ kernel computes.  ``project`` and ``contours`` keep their statements; the one of
 keep their Newton leaves.  ``zeros_batch`` (the checks and the path), ``tables``, ``isolate_cells`` (flag, isolate, merge),
 ``collect`` and ``zeros`` (the ``Spline.zerosN`` wrapper) are ``zeros2_batch`` and ``zeros3_batch``: each takes the family's
 module, which supplies the number of variables, the entry-point prefix, the slots, the order checks and the path knobs.
+
+The front of a call that takes a coefficient net is here too, once for every family that has one: ``coefs_arg`` (what a
+``coefs`` argument may be, and the path it pins: all of ``roots``, ``zeros2`` / ``zeros3``, ``contours``, ``isosurface`` and
+``mesh``), ``bezier_rows`` (upload, widen to float64, extract: everyone but ``roots``, which keeps float32 rows),
+``field_scale`` and ``zero_table``.  ``level_batch`` (the checks, the path by leaf count, the tables, the run and the
+zero-cell table), ``level_tables``, ``depth_of`` and ``split_of`` are ``contours.trace_batch`` and
+``isosurface.extract_batch`` up to their tails, for any number of axes: each takes the family's module as ``zeros_batch``
+does.  ``weld`` turns the key triples of ``isosurface`` and ``mesh`` into indexed triangles, member by member.
 """
 import math
 
@@ -37,6 +45,68 @@ def band_host(data, steps, log):
         log.append(L.bsk_roots_last_kernel().decode())
         data = np.ascontiguousarray(np.moveaxis(out, -1, axis))
     return data
+
+
+# ------------------------------------------------------------------------------------------ the coefficient argument
+def coefs_arg(name, coefs, path, tail, text):
+    """What ``name`` (the caller, for the messages) takes as ``coefs``: a float32 / float64 torch CUDA tensor, which pins
+    the device path, or anything NumPy makes an array of; ``tail`` is the shape behind the batch axis (an int per axis, or
+    a range of them) and ``text`` says it.  -> (coefs, on_device, path)."""
+    on_device = is_torch(coefs)
+    if on_device:
+        import torch
+        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name} takes the coefficients as a float32 or float64 torch CUDA tensor")
+        if path == "host":
+            raise ValueError("coefficients on the device take the device path")
+        path = "device"
+    else:
+        coefs = np.asarray(coefs)
+    if coefs.ndim != len(tail) + 1 or not all(m in (want if isinstance(want, range) else (want,)) for m, want in zip(coefs.shape[1:], tail)):
+        raise ValueError(f"coefs must have the shape {text}")
+    return coefs, on_device, path
+
+
+def backend_of(coefs):
+    """Where the result of a call lives that computes nothing (B == 0): with its coefficients."""
+    return Device(coefs.device) if is_torch(coefs) else Host()
+
+
+def to_host(be, res):
+    """A driver's dict of results with the backend's arrays brought to the host."""
+    return {name: be.get(a) if is_torch(a) else a for name, a in res.items()}
+
+
+def bezier_rows(coefs, path, plan, log, finite=None):
+    """coefs (..., *nCoef), NumPy or a torch CUDA tensor of any strides, on the backend of ``path`` -> (be, data, rows):
+    data = coefs in float64 (float32 is widened BEFORE the extraction; a float64 CUDA tensor is not copied) and rows =
+    data through ``plan.steps``, the backend's contiguous array (..., *rowlen); ``log`` receives what ran.  ``finite``: the
+    caller's name, which refuses coefficients that are not finite."""
+    if path == "device":
+        import torch
+        data = (coefs if is_torch(coefs) else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()
+        be, ok = Device(data.device), finite is None or bool(torch.isfinite(data).all())
+    else:
+        data = np.asarray(coefs).astype(np.float64)
+        be, ok = Host(), finite is None or np.isfinite(data).all()
+    if not ok:
+        raise ValueError(f"{finite}: the coefficients must be finite")
+    rows = data
+    if plan.steps:
+        rows = data.reshape((-1,) + tuple(data.shape[-plan.nind:]))
+        if path == "device":
+            rows, ran = refinement.run_device(rows, plan.steps)
+            log.extend(ran)
+        else:
+            rows = band_host(rows, plan.steps, log)
+        rows = rows.reshape(tuple(data.shape[:-plan.nind]) + tuple(plan.rowlen))
+    return be, data, (rows.contiguous() if path == "device" else np.ascontiguousarray(rows))
+
+
+def field_scale(be, data, levels=None):
+    """S of every field, float64 (B): max |coefficient| of data (B, ...), or max |coefficient of field 0 - levels[b]|."""
+    fields = data if levels is None else data[0][None] - levels[(slice(None),) + (None,) * (data.ndim - 1)]
+    return be.amax(abs(fields), tuple(range(1, data.ndim)))
 
 
 # ------------------------------------------------------------------------------------------ plans and tables
@@ -116,6 +186,28 @@ def zero_cells(small, plan):
     return (total == int(np.prod(plan.order))).any(axis=1)
 
 
+def zero_table(zero, plan):
+    """zero: NumPy (B, *ncells), nonzero on a zero cell.  -> float64 (k, 2 nInd + 1): one row (member, u0, u1, v0, v1, ...)
+    per zero cell, in index order."""
+    at = np.argwhere(zero)
+    cols = [at[:, 0].astype(np.float64)]
+    for a, b in enumerate(plan.breaks):
+        b = np.asarray(b, np.float64)
+        cols += [b[at[:, a + 1]], b[at[:, a + 1] + 1]]
+    return np.stack(cols, axis=1).reshape(-1, 2 * plan.nind + 1)
+
+
+def system_tables(be, data, plan):
+    """data: the backend's float64 (B, n, *nCoef).  -> (mask NumPy uint8 (B, *ncells), the zero cells; scale (B, n), the
+    backend's, max |coefficient| of every component).  One byte per coefficient is read back on the device."""
+    n = plan.nind
+    wide = abs(data)
+    scale = be.amax(wide, tuple(range(2, n + 2)))
+    each = (...,) + (None,) * n
+    small = be.get((wide < (scale * EPS)[each]) | (scale == 0.0)[each])
+    return zero_cells(small, plan).astype(np.uint8), scale
+
+
 # ------------------------------------------------------------------------------------------ the drivers of zeros2 and zeros3
 def isolate_cells(be, prefix, rows, plan, mask, scale, R, log):
     """Flag the cells, isolate the zeros of the candidates, merge the ones near a cell boundary: the entry points
@@ -176,12 +268,7 @@ def collect(be, plan, kdtype, B, R=0, res=None, mask=None, numpy_out=True):
     status = status.reshape((B,) + nc)
     if numpy_out:
         values, offsets, status = be.get(values), be.get(offsets), be.get(status)
-    at = np.argwhere(mask)
-    cols = [at[:, 0].astype(np.float64)]
-    for a, b in enumerate(plan.breaks):
-        b = np.asarray(b, np.float64)
-        cols += [b[at[:, a + 1]], b[at[:, a + 1] + 1]]
-    return values, offsets, np.stack(cols, axis=1).reshape(-1, 2 * n + 1), status
+    return values, offsets, zero_table(mask, plan), status
 
 
 def run_host(family, rows, plan, mask, scale):
@@ -196,16 +283,8 @@ def tables(family, spline, coefs=None):
     n = family.NIND
     plan = TensorPlan(spline.order, spline.knots)
     data = np.asarray(spline.coefs if coefs is None else coefs)
-    data = data.reshape((-1, n) + data.shape[-n:]).astype(np.float64)            # float32 is widened BEFORE the extraction
-    wide = np.abs(data)
-    scale = np.ascontiguousarray(wide.max(axis=tuple(range(2, n + 2))))
-    each = (...,) + (None,) * n
-    small = (wide < (scale * EPS)[each]) | (scale == 0.0)[each]
-    mask = zero_cells(small, plan).astype(np.uint8)
-    rows = data
-    if plan.steps:
-        rows = band_host(data.reshape((-1,) + data.shape[2:]), plan.steps, family.LAST_PATHS).reshape(data.shape[:2] + tuple(plan.rowlen))
-    return plan, rows, mask, scale
+    be, data, rows = bezier_rows(data.reshape((-1, n) + data.shape[-n:]), "host", plan, family.LAST_PATHS)
+    return (plan, rows) + system_tables(be, data, plan)
 
 
 def zeros_batch(family, spline, coefs, _path):
@@ -217,22 +296,11 @@ def zeros_batch(family, spline, coefs, _path):
     family._check_spline(spline)
     K = tuple(int(k) for k in spline.order)
     ncoef = tuple(len(spline.knots[d]) - spline.order[d] for d in range(n))
-    on_device = coefs is not None and is_torch(coefs)
     if coefs is None:
         if spline.nDep != n:
             raise ValueError(f"{name} takes {family.WORD} dependent variables, or coefs (B, {n}, {', '.join(f'n{d}' for d in range(n))})")
         coefs = spline.coefs[None]
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"{name} takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != n + 2 or tuple(coefs.shape[1:]) != (n,) + ncoef:
-        raise ValueError(f"coefs must have the shape (B, {n}, {', '.join(str(m) for m in ncoef)})")
+    coefs, on_device, path = coefs_arg(name, coefs, path, (n,) + ncoef, f"(B, {n}, {', '.join(str(m) for m in ncoef)})")
     B = int(coefs.shape[0])
     plan = TensorPlan(spline.order, spline.knots)
     kdtype = np.result_type(*(spline.knots[d].dtype for d in range(n)))
@@ -243,26 +311,10 @@ def zeros_batch(family, spline, coefs, _path):
         raise ValueError(f"the device path covers orders from {family.DEVICE_MIN_K} to {family.DEVICE_MAX_K}")
 
     if B == 0:
-        return collect(Device(coefs.device) if on_device else Host(), plan, kdtype, 0)
-
-    if path == "device":
-        import torch
-        data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        be = Device(data.device)
-        wide = data.abs()
-        scale = wide.amax(dim=tuple(range(2, n + 2))).contiguous()
-        each = (...,) + (None,) * n
-        small = ((wide < (scale * EPS)[each]) | (scale == 0.0)[each]).cpu().numpy()
-        mask = zero_cells(small, plan).astype(np.uint8)
-        rows = data.reshape((n * B,) + ncoef)
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            family.LAST_PATHS.extend(ran)
-        res = isolate_cells(be, family.PREFIX, rows.contiguous(), plan, mask, scale, family.slots(*K), family.LAST_PATHS)
-    else:
-        be = Host()
-        _, rows, mask, scale = tables(family, spline, coefs)
-        res = run_host(family, rows, plan, mask, scale)      # makes rows and scale contiguous
+        return collect(backend_of(coefs), plan, kdtype, 0)
+    be, data, rows = bezier_rows(coefs, path, plan, family.LAST_PATHS)
+    mask, scale = system_tables(be, data, plan)
+    res = isolate_cells(be, family.PREFIX, rows, plan, mask, scale, family.slots(*K), family.LAST_PATHS)
     return collect(be, plan, kdtype, B, family.slots(*K), res, mask, numpy_out=not on_device)
 
 
@@ -287,3 +339,92 @@ def zeros(family, spline, _path):
         found.append((tuple(float(x) for x in lo), (lo, hi)))
     found.sort(key=lambda item: item[0])
     return [item[1] for item in found]
+
+
+# ------------------------------------------------------------------------------------------ the drivers of contours and isosurface
+def depth_of(family, tolerance, plan):
+    """The depth that ``tolerance`` asks for (the family's statement says why): DEFAULT_DEPTH without one, at most MAX_DEPTH."""
+    if tolerance is None:
+        return family.DEFAULT_DEPTH
+    if not tolerance > 0.0:
+        raise ValueError("tolerance must be positive")
+    breaks = [np.asarray(b, np.float64) for b in plan.breaks]
+    h = max(float(np.diff(b).max()) for b in breaks)
+    L = max(float(b[-1] - b[0]) for b in breaks)
+    for d in range(family.MAX_DEPTH + 1):
+        if (h * 2.0 ** -d) ** 2 <= tolerance * L:
+            return d
+    return family.MAX_DEPTH
+
+
+def split_of(nind, fill, ncand, depth):
+    """The split level P of a walk over ``nind`` axes: the smallest that gives ``fill`` walkers, at most depth."""
+    P = 0
+    while P < depth and (ncand << (nind * P)) < fill:
+        P += 1
+    return P
+
+
+def level_tables(family, spline, levels=None, coefs=None):
+    """The host path's tables of a level family: (plan, rows (nrows, *rowlen), levels or None, scale (B)), all NumPy float64."""
+    plan = family.Plan(spline.order, spline.knots)
+    data = np.asarray(spline.coefs if coefs is None else coefs)
+    be, data, rows = bezier_rows(data.reshape((-1,) + data.shape[-plan.nind:]), "host", plan, family.LAST_PATHS)
+    if levels is not None:
+        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
+    return plan, rows, levels, field_scale(be, data, levels)
+
+
+def level_batch(family, spline, levels, coefs, depth, _path, _split):
+    """``trace_batch`` and ``extract_batch`` up to their tails: the checks, the path, the tables on its backend, the run and
+    the zero-cell table.  ``family``, the module, supplies NIND, BATCH (its name in the messages), ``_check_batch``, ``Plan``,
+    DEFAULT_DEPTH, MAX_DEPTH, ``_check_keys`` (what the lattice's keys can hold), DEVICE_MIN_LEAVES, FORCE_PATH, LAST_PATHS
+    and ``_run``.  -> (be, on_device, plan, B, res, cells): the backend, whether the caller's coefficients live on it, what
+    ``_run`` returned (the backend's arrays; None for B == 0, which runs nothing) and ``zero_table`` of its zero cells."""
+    n, name = family.NIND, family.BATCH
+    del family.LAST_PATHS[:]
+    path = pick_path(_path, family.FORCE_PATH)
+    family._check_batch(spline)
+    ncoef = tuple(len(spline.knots[d]) - spline.order[d] for d in range(n))
+    if levels is not None and coefs is not None:
+        raise ValueError(f"{name} takes levels or coefs, not both")
+    if coefs is None:
+        if spline.nDep != 1:
+            raise ValueError(f"{name} takes one dependent variable, or coefs (B, {', '.join(f'n{d}' for d in range(n))})")
+        coefs = spline.coefs
+    coefs, on_device, path = coefs_arg(name, coefs, path, ncoef, f"(B, {', '.join(str(m) for m in ncoef)})")
+    if levels is not None:
+        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
+    B = int(coefs.shape[0]) if levels is None else len(levels)
+    plan = family.Plan(spline.order, spline.knots)
+    nc = tuple(plan.ncells)
+    depth = family.DEFAULT_DEPTH if depth is None else int(depth)
+    if not 0 <= depth <= family.MAX_DEPTH:
+        raise ValueError(f"depth must be in 0 .. {family.MAX_DEPTH}")
+    if _split is not None and not 0 <= int(_split) <= depth:
+        raise ValueError("_split must be in 0 .. depth")
+    family._check_keys(plan, depth, max(B, 1))
+    if path is None:
+        path = "device" if (B * int(np.prod(nc))) << (n * depth) >= family.DEVICE_MIN_LEAVES else "host"
+    if B == 0:
+        return backend_of(coefs), on_device, plan, 0, None, zero_table(np.zeros((0,) + nc, np.uint8), plan)
+    be, data, rows = bezier_rows(coefs, path, plan, family.LAST_PATHS)
+    if levels is not None:
+        levels = be.put(levels, np.float64)
+    res = family._run(be, rows, plan, levels, field_scale(be, data, levels), depth, _split)
+    return be, on_device, plan, B, res, zero_table(be.get(res["zero"]), plan)
+
+
+# ------------------------------------------------------------------------------------------ the weld of isosurface and mesh
+def weld(be, tris, tstart):
+    """tris: the backend's int64 (m, 3), triangles as triples of vertex keys, member by member; tstart: where the B
+    members start among them (B + 1 ints).  A member's vertices are its sorted unique keys.  -> (keys (n), members (n),
+    the member of every vertex, triangles (m, 3), indices into keys, vertex_offsets (B + 1)), the backend's int64."""
+    keys, members, triangles, vstart = [], [], [], [0]
+    for b in range(len(tstart) - 1):
+        unique, inverse = be.unique(tris[tstart[b]:tstart[b + 1]].reshape(-1))
+        triangles.append(inverse.reshape(-1, 3) + vstart[-1])
+        keys.append(unique)
+        members.append(be.zeros(len(unique), np.int64) + b)
+        vstart.append(vstart[-1] + len(unique))
+    return be.cat(keys), be.cat(members), be.cat(triangles), be.put(vstart, np.int64)

@@ -69,12 +69,17 @@ farther from the curve.  (Interpolating all vertices is not an option: vertices 
 ``_path="device" | "host"`` (or ``contours.FORCE_PATH``) pins the path; ``contours.LAST_PATHS`` lists what the last call
 ran.
 """
+import functools
+import sys
+
 import numpy as np
 
 from . import _cells
 from . import _native as nv
-from . import refinement
 from . import roots
+
+_THIS = sys.modules[__name__]          # the family that ``_cells`` is handed
+NIND, BATCH = 2, "trace_batch"         # the variables of a field and the batch call's name in its messages
 
 # Leaves (fields x cells x 4^depth) from which the device path is taken: read off the table of tools/contours_time.py on an
 # MI355X (DESIGN.md section 21): bicubic, depth 4, 1024 leaves 0.85 ms on the host against 1.2 ms, 4096 leaves 1.36 against 1.26.
@@ -256,27 +261,10 @@ def statement(rows, plan, levels, scale, depth):
                 xy=np.array(xy, np.float64).reshape(-1, 4), field=np.array(field, np.int64))
 
 
-def depth_of(tolerance, plan):
-    """The depth that ``tolerance`` asks for (the statement says why)."""
-    if tolerance is None:
-        return DEFAULT_DEPTH
-    if not tolerance > 0.0:
-        raise ValueError("tolerance must be positive")
-    b0, b1 = (np.asarray(b, np.float64) for b in plan.breaks)
-    h = max(float(np.diff(b0).max()), float(np.diff(b1).max()))
-    L = max(float(b0[-1] - b0[0]), float(b1[-1] - b1[0]))
-    for d in range(MAX_DEPTH + 1):
-        if (h * 2.0 ** -d) ** 2 <= tolerance * L:
-            return d
-    return MAX_DEPTH
-
-
-def split_of(ncand, depth):
-    """The split level P of a march launch: the smallest that gives FILL_LANES lanes, at most depth."""
-    P = 0
-    while P < depth and (ncand << (2 * P)) < FILL_LANES:
-        P += 1
-    return P
+# depth_of(tolerance, plan): the depth that ``tolerance`` asks for (the statement says why)
+depth_of = functools.partial(_cells.depth_of, _THIS)
+# split_of(ncand, depth): the split level P of a march launch: the smallest that gives FILL_LANES lanes, at most depth
+split_of = functools.partial(_cells.split_of, NIND, FILL_LANES)
 
 
 # ------------------------------------------------------------------------------------------ linking (host, both paths)
@@ -330,11 +318,6 @@ def link(keys, field, B):
 # ------------------------------------------------------------------------------------------ the launches
 def _last():
     return nv.lib().bsk_contour_last_kernel().decode()
-
-
-def extract_host(data, plan):
-    """NumPy (M, n0, n1) float64 -> (M, R0, R1) in Bezier form (``_cells.band_host``)."""
-    return _cells.band_host(data, plan.steps, LAST_PATHS)
 
 
 def _grid(plan, rows, ptr, levels, B, scale, first0, first1):
@@ -402,20 +385,16 @@ def _check_spline(spline):
         raise NotImplementedError(f"contours: orders from {DEVICE_MIN_K} to {DEVICE_MAX_K}")
 
 
-def tables(spline, levels=None, coefs=None):
-    """The host path's tables: (plan, rows (nrows, R0, R1), levels or None, scale (B)), all NumPy float64."""
-    plan = Plan(spline.order, spline.knots)
-    data = np.asarray(spline.coefs if coefs is None else coefs)
-    data = data.reshape((-1,) + data.shape[-2:]).astype(np.float64)               # float32 is widened BEFORE the extraction
-    if levels is not None:
-        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
-        scale = np.abs(data[0][None] - levels[:, None, None]).max(axis=(1, 2))
-    else:
-        scale = np.abs(data).max(axis=(1, 2))
-    rows = data
-    if plan.steps:
-        rows = extract_host(data, plan)
-    return plan, rows, levels, np.ascontiguousarray(scale)
+_check_batch = _check_spline
+
+
+def _check_keys(plan, depth, B):
+    """Nothing to refuse: the edge keys of 2^8 leaves per cell and axis fit 62 bits for any spline that fits memory."""
+
+
+# tables(spline, levels=None, coefs=None): the host path's tables: (plan, rows (nrows, R0, R1), levels or None, scale (B)),
+# all NumPy float64
+tables = functools.partial(_cells.level_tables, _THIS)
 
 
 def trace_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=None):
@@ -430,78 +409,15 @@ def trace_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=
     ``coefs``: a float32 / float64 torch CUDA tensor takes the device path; vertices and status are then CUDA tensors and
     the vertices never leave the device (the integer keys of the segments do: linking is a host sort).
     ``_split`` pins the split level P of the march launches (0 .. depth); the result does not depend on it."""
-    del LAST_PATHS[:]
-    path = _cells.pick_path(_path, FORCE_PATH)
-    _check_spline(spline)
-    K0, K1 = (int(k) for k in spline.order)
-    n0, n1 = (len(spline.knots[d]) - spline.order[d] for d in range(2))
-    if levels is not None and coefs is not None:
-        raise ValueError("trace_batch takes levels or coefs, not both")
-    on_device = coefs is not None and _cells.is_torch(coefs)
-    if coefs is None:
-        if spline.nDep != 1:
-            raise ValueError("trace_batch takes one dependent variable, or coefs (B, n0, n1)")
-        coefs = spline.coefs
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("trace_batch takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != 3 or tuple(coefs.shape[1:]) != (n0, n1):
-        raise ValueError(f"coefs must have the shape (B, {n0}, {n1})")
-    if levels is not None:
-        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
-    B = int(coefs.shape[0]) if levels is None else len(levels)
-    plan = Plan(spline.order, spline.knots)
-    nc0, nc1 = plan.ncells
-    depth = DEFAULT_DEPTH if depth is None else int(depth)
-    if not 0 <= depth <= MAX_DEPTH:
-        raise ValueError(f"depth must be in 0 .. {MAX_DEPTH}")
-    if _split is not None and not 0 <= int(_split) <= depth:
-        raise ValueError("_split must be in 0 .. depth")
+    be, on_device, plan, B, res, cells = _cells.level_batch(_THIS, spline, levels, coefs, depth, _path, _split)
     kdtype = np.result_type(spline.knots[0].dtype, spline.knots[1].dtype)
-    if path is None:
-        path = "device" if (B * nc0 * nc1) << (2 * depth) >= DEVICE_MIN_LEAVES else "host"
-
     if B == 0:
-        empty = (np.zeros(1, np.int64), np.zeros(0, bool), np.zeros(0, np.int64), np.empty((0, 5)))
-        if on_device:
-            return (torch.empty((0, 2), dtype=getattr(torch, kdtype.name), device=coefs.device),) + empty + \
-                (torch.zeros((0, nc0, nc1), dtype=torch.uint8, device=coefs.device),)
-        return (np.empty((0, 2), kdtype),) + empty + (np.zeros((0, nc0, nc1), np.uint8),)
-
-    if path == "device":
-        import torch
-        data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        dev = data.device
-        d_levels = None if levels is None else torch.from_numpy(levels).to(dev)
-        if d_levels is None:
-            d_scale = data.abs().amax(dim=(1, 2)).contiguous()
-        else:
-            d_scale = (data[0][None] - d_levels[:, None, None]).abs().amax(dim=(1, 2)).contiguous()
-        rows = data
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            LAST_PATHS.extend(ran)
-        res = _run(_cells.Device(dev), rows.contiguous(), plan, d_levels, d_scale, depth, _split)
-        points, offsets, closed, comp_field = link(res["keys"].cpu().numpy(), res["field"].cpu().numpy(), B)
-        vertices = res["xy"].reshape(-1, 2)[torch.from_numpy(points).to(dev)].to(getattr(torch, kdtype.name))
-        zero, status = res["zero"].cpu().numpy(), res["status"]
-        if not on_device:
-            vertices, status = vertices.cpu().numpy(), status.cpu().numpy()
-    else:
-        _, rows, levels, scale = tables(spline, levels, coefs)
-        res = _run_host(rows, plan, levels, scale, depth, _split)
-        points, offsets, closed, comp_field = link(res["keys"], res["field"], B)
-        vertices = res["xy"].reshape(-1, 2)[points].astype(kdtype)
-        zero, status = res["zero"], res["status"]
-    at = np.argwhere(zero)
-    b0, b1 = (np.asarray(b, np.float64) for b in plan.breaks)
-    cells = np.stack([at[:, 0].astype(np.float64), b0[at[:, 1]], b0[at[:, 1] + 1], b1[at[:, 2]], b1[at[:, 2] + 1]], axis=1).reshape(-1, 5)
+        return (be.empty((0, 2), kdtype), np.zeros(1, np.int64), np.zeros(0, bool), np.zeros(0, np.int64), cells,
+                be.zeros((0,) + tuple(plan.ncells), np.uint8))
+    points, offsets, closed, comp_field = link(be.get(res["keys"]), be.get(res["field"]), B)
+    vertices, status = be.cast(res["xy"].reshape(-1, 2)[be.put(points, np.int64)], kdtype), res["status"]
+    if not on_device:
+        vertices, status = be.get(vertices), be.get(status)
     return vertices, offsets, closed, comp_field, cells, status
 
 

@@ -77,14 +77,18 @@ lattice node are 2^-60 of a leaf apart.
 ``_path="device" | "host"`` (or ``isosurface.FORCE_PATH``) pins the path; ``isosurface.LAST_PATHS`` lists what the last
 call ran.
 """
+import functools
 import itertools
+import sys
 
 import numpy as np
 
 from . import _cells
 from . import _native as nv
-from . import refinement
 from . import roots
+
+_THIS = sys.modules[__name__]          # the family that ``_cells`` is handed
+NIND, BATCH = 3, "extract_batch"       # the variables of a field and the batch call's name in its messages
 
 # Leaves (fields x cells x 8^depth) from which the device path is taken: read off the calls table of tools/iso_time.py on an
 # MI355X (DESIGN.md section 25): tricubic, depth 3, 4096 leaves 0.99 ms on the host against 1.09 ms, 32 768 leaves 17.4 against 2.0.
@@ -313,27 +317,10 @@ def statement(rows, plan, levels, scale, depth):
                 triangle_offsets=np.array(toff, np.int64))
 
 
-def depth_of(tolerance, plan):
-    """The depth that ``tolerance`` asks for (the statement says why)."""
-    if tolerance is None:
-        return DEFAULT_DEPTH
-    if not tolerance > 0.0:
-        raise ValueError("tolerance must be positive")
-    breaks = [np.asarray(b, np.float64) for b in plan.breaks]
-    h = max(float(np.diff(b).max()) for b in breaks)
-    L = max(float(b[-1] - b[0]) for b in breaks)
-    for d in range(MAX_DEPTH + 1):
-        if (h * 2.0 ** -d) ** 2 <= tolerance * L:
-            return d
-    return MAX_DEPTH
-
-
-def split_of(ncand, depth):
-    """The split level P of a walk launch: the smallest that gives FILL_WAVES waves, at most depth."""
-    P = 0
-    while P < depth and (ncand << (3 * P)) < FILL_WAVES:
-        P += 1
-    return P
+# depth_of(tolerance, plan): the depth that ``tolerance`` asks for (the statement says why)
+depth_of = functools.partial(_cells.depth_of, _THIS)
+# split_of(ncand, depth): the split level P of a walk launch: the smallest that gives FILL_WAVES waves, at most depth
+split_of = functools.partial(_cells.split_of, NIND, FILL_WAVES)
 
 
 # ------------------------------------------------------------------------------------------ the launches
@@ -400,19 +387,11 @@ def _run(be, rows, plan, levels, scale, depth, split):
         # where the fields start among the leaves, the triangles and (below) the vertices
         leaf_start = be.searchsorted(leaves // per_field, B + 1)
         tstart = be.get(be.cat([be.zeros(1, np.int64), tends])[leaf_start]).tolist()
-        keys, fields, triangles, vstart = [], [], [], [0]
-        for b in range(B):
-            unique, inverse = be.unique(tris[tstart[b]:tstart[b + 1]].reshape(-1))
-            triangles.append(inverse.reshape(-1, 3) + vstart[-1])
-            keys.append(unique)
-            fields.append(be.zeros(len(unique), np.int64) + b)
-            vstart.append(vstart[-1] + len(unique))
-        keys, fields = be.cat(keys), be.cat(fields)
+        keys, fields, triangles, vstart = _cells.weld(be, tris, tstart)
         xyz = be.empty((len(keys), 3), np.float64)
         breaks = [be.put(b, np.float64) for b in plan.breaks]
         call("bsk_iso_vertex", *grid, *map(be.ptr, breaks), be.ptr(keys), be.ptr(fields), len(keys), depth, be.ptr(xyz))
-        out.update(keys=keys, xyz=xyz, vertex_offsets=be.put(vstart, np.int64), triangles=be.cat(triangles),
-                   triangle_offsets=be.put(tstart, np.int64))
+        out.update(keys=keys, xyz=xyz, vertex_offsets=vstart, triangles=triangles, triangle_offsets=be.put(tstart, np.int64))
         return finish()
 
 
@@ -435,6 +414,12 @@ def _check_spline(spline):
         raise NotImplementedError(f"isosurface: orders from {DEVICE_MIN_K} to {DEVICE_MAX_K} (one wave holds the 64 coefficients of a cell)")
 
 
+def _check_batch(spline):
+    if spline.nInd != 3:
+        raise ValueError("extract_batch takes three independent variables")
+    _check_spline(spline)
+
+
 def _check_keys(plan, depth, B):
     nodes = 1
     for n in plan.ncells:
@@ -444,20 +429,9 @@ def _check_keys(plan, depth, B):
                          "lower the depth or trim the spline")
 
 
-def tables(spline, levels=None, coefs=None):
-    """The host path's tables: (plan, rows (nrows, R0, R1, R2), levels or None, scale (B)), all NumPy float64."""
-    plan = Plan(spline.order, spline.knots)
-    data = np.asarray(spline.coefs if coefs is None else coefs)
-    data = data.reshape((-1,) + data.shape[-3:]).astype(np.float64)               # float32 is widened BEFORE the extraction
-    if levels is not None:
-        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
-        scale = np.abs(data[0][None] - levels[:, None, None, None]).max(axis=(1, 2, 3))
-    else:
-        scale = np.abs(data).max(axis=(1, 2, 3))
-    rows = data
-    if plan.steps:
-        rows = _cells.band_host(data, plan.steps, LAST_PATHS)
-    return plan, rows, levels, np.ascontiguousarray(scale)
+# tables(spline, levels=None, coefs=None): the host path's tables: (plan, rows (nrows, R0, R1, R2), levels or None,
+# scale (B)), all NumPy float64
+tables = functools.partial(_cells.level_tables, _THIS)
 
 
 def extract_batch(spline, levels=None, coefs=None, depth=None, _path=None, _split=None):
@@ -473,77 +447,12 @@ def extract_batch(spline, levels=None, coefs=None, depth=None, _path=None, _spli
     ``coefs``: a float32 / float64 torch CUDA tensor (any strides) takes the device path; vertices, keys, triangles and
     status are then CUDA tensors and never leave the device.
     ``_split`` pins the split level P of the walk launches (0 .. depth); the result does not depend on it."""
-    del LAST_PATHS[:]
-    path = _cells.pick_path(_path, FORCE_PATH)
-    if spline.nInd != 3:
-        raise ValueError("extract_batch takes three independent variables")
-    _check_spline(spline)
-    n0, n1, n2 = (len(spline.knots[d]) - spline.order[d] for d in range(3))
-    if levels is not None and coefs is not None:
-        raise ValueError("extract_batch takes levels or coefs, not both")
-    on_device = coefs is not None and _cells.is_torch(coefs)
-    if coefs is None:
-        if spline.nDep != 1:
-            raise ValueError("extract_batch takes one dependent variable, or coefs (B, n0, n1, n2)")
-        coefs = spline.coefs
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("extract_batch takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != 4 or tuple(coefs.shape[1:]) != (n0, n1, n2):
-        raise ValueError(f"coefs must have the shape (B, {n0}, {n1}, {n2})")
-    if levels is not None:
-        levels = np.ascontiguousarray(levels, np.float64).reshape(-1)
-    B = int(coefs.shape[0]) if levels is None else len(levels)
-    plan = Plan(spline.order, spline.knots)
-    nc = tuple(plan.ncells)
-    depth = DEFAULT_DEPTH if depth is None else int(depth)
-    if not 0 <= depth <= MAX_DEPTH:
-        raise ValueError(f"depth must be in 0 .. {MAX_DEPTH}")
-    if _split is not None and not 0 <= int(_split) <= depth:
-        raise ValueError("_split must be in 0 .. depth")
-    _check_keys(plan, depth, max(B, 1))
-    if path is None:
-        path = "device" if (B * int(np.prod(nc))) << (3 * depth) >= DEVICE_MIN_LEAVES else "host"
-
+    be, on_device, plan, B, res, cells = _cells.level_batch(_THIS, spline, levels, coefs, depth, _path, _split)
     if B == 0:
-        be = _cells.Device(coefs.device) if on_device else _cells.Host()
         return (be.empty((0, 3), np.float64), be.empty(0, np.int64), be.zeros(1, np.int64), be.empty((0, 3), np.int64),
-                be.zeros(1, np.int64), np.empty((0, 7)), be.zeros((0,) + nc, np.uint8))
-
-    if path == "device":
-        import torch
-        data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        dev = data.device
-        d_levels = None if levels is None else torch.from_numpy(levels).to(dev)
-        if d_levels is None:
-            d_scale = data.abs().amax(dim=(1, 2, 3)).contiguous()
-        else:
-            d_scale = (data[0][None] - d_levels[:, None, None, None]).abs().amax(dim=(1, 2, 3)).contiguous()
-        rows = data
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            LAST_PATHS.extend(ran)
-        be = _cells.Device(dev)
-        res = _run(be, rows.contiguous(), plan, d_levels, d_scale, depth, _split)
-        zero = res["zero"].cpu().numpy()
-        if not on_device:
-            res = {name: be.get(a) if _cells.is_torch(a) else a for name, a in res.items()}
-    else:
-        _, rows, levels, scale = tables(spline, levels, coefs)
-        res = _run_host(rows, plan, levels, scale, depth, _split)
-        zero = res["zero"]
-    at = np.argwhere(zero)
-    cols = [at[:, 0].astype(np.float64)]
-    for axis, b in enumerate(plan.breaks):
-        b = np.asarray(b, np.float64)
-        cols += [b[at[:, axis + 1]], b[at[:, axis + 1] + 1]]
-    cells = np.stack(cols, axis=1).reshape(-1, 7)
+                be.zeros(1, np.int64), cells, be.zeros((0,) + tuple(plan.ncells), np.uint8))
+    if not on_device:
+        res = _cells.to_host(be, res)
     return res["xyz"], res["keys"], res["vertex_offsets"], res["triangles"], res["triangle_offsets"], cells, res["status"]
 
 

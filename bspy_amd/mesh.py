@@ -74,7 +74,6 @@ import numpy as np
 
 from . import _cells
 from . import _native as nv
-from . import refinement
 from . import roots
 
 SCOPE = "triangulate: surfaces (nInd == 2) with nDep 1 .. 3 and orders 2 .. 4"
@@ -318,21 +317,14 @@ def _run(be, rows, plan, tolerance, max_level, normals, chunk, max_triangles):
             call("bsk_mesh_emit", *quads, start, min(chunk, nquads - start), nquads, be.ptr(offsets), total, be.ptr(tris))
         # where the members start among the triangles and (below) the vertices
         tstart = be.get(be.cat([be.zeros(1, np.int64), tends])[qoff[::per_member]]).tolist()
-        keys, members, triangles, vstart = [], [], [], [0]
-        for b in range(B):
-            unique, inverse = be.unique(tris[tstart[b]:tstart[b + 1]].reshape(-1))
-            triangles.append(inverse.reshape(-1, 3) + vstart[-1])
-            keys.append(unique)
-            members.append(be.zeros(len(unique), np.int64) + b)
-            vstart.append(vstart[-1] + len(unique))
-        keys, members = be.cat(keys), be.cat(members)
+        keys, members, triangles, vstart = _cells.weld(be, tris, tstart)
         n = len(keys)
         uv, xyz = be.empty((n, 2), np.float64), be.empty((n, ndep), np.float64)
         nrm = be.empty((n, 3), np.float64) if normals else None
         breaks = [be.put(b, np.float64) for b in plan.breaks]
         call("bsk_mesh_vertex", *net, *map(be.ptr, breaks), be.ptr(keys), be.ptr(members), n, be.ptr(uv), be.ptr(xyz), be.ptr(nrm))
-        return dict(Q=Q, lev=lev, status=status, keys=keys, uv=uv, xyz=xyz, normals=nrm, vertex_offsets=be.put(vstart, np.int64),
-                    triangles=be.cat(triangles), triangle_offsets=be.put(tstart, np.int64), nquads=nquads)
+        return dict(Q=Q, lev=lev, status=status, keys=keys, uv=uv, xyz=xyz, normals=nrm, vertex_offsets=vstart,
+                    triangles=triangles, triangle_offsets=be.put(tstart, np.int64), nquads=nquads)
 
 
 def _run_host(rows, plan, tolerance, max_level=DEFAULT_MAX_LEVEL, normals=False, chunk=None, max_triangles=DEFAULT_MAX_TRIANGLES):
@@ -355,14 +347,8 @@ def tables(spline, coefs=None):
     """The host path's tables: (plan, rows (B, nDep, R0, R1), scale (B)), NumPy float64."""
     plan = Plan(spline.order, spline.knots)
     data = np.asarray(spline.coefs if coefs is None else coefs)
-    data = data.reshape((-1,) + data.shape[-3:]).astype(np.float64)                # float32 is widened BEFORE the extraction
-    if not np.isfinite(data).all():
-        raise ValueError("triangulate: the coefficients must be finite")
-    scale = np.abs(data).max(axis=(1, 2, 3)) if len(data) else np.zeros(0)
-    rows = data
-    if plan.steps:
-        rows = _cells.band_host(data.reshape((-1,) + data.shape[2:]), plan.steps, LAST_PATHS).reshape(data.shape[:2] + tuple(plan.rowlen))
-    return plan, rows, scale
+    be, data, rows = _cells.bezier_rows(data.reshape((-1,) + data.shape[-3:]), "host", plan, LAST_PATHS, finite="triangulate")
+    return plan, rows, _cells.field_scale(be, data)
 
 
 def triangulate_batch(spline, tolerance, coefs=None, max_level=DEFAULT_MAX_LEVEL, max_triangles=DEFAULT_MAX_TRIANGLES, normals=False,
@@ -390,20 +376,10 @@ def triangulate_batch(spline, tolerance, coefs=None, max_level=DEFAULT_MAX_LEVEL
     if _chunk is not None and int(_chunk) < 1:
         raise ValueError("_chunk must be >= 1")
     n0, n1 = (len(spline.knots[d]) - spline.order[d] for d in range(2))
-    on_device = coefs is not None and _cells.is_torch(coefs)
     if coefs is None:
         coefs = np.asarray(spline.coefs)[None]
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("triangulate_batch takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != 4 or not 1 <= coefs.shape[1] <= 3 or tuple(coefs.shape[2:]) != (n0, n1):
-        raise ValueError(f"coefs must have the shape (B, nDep, {n0}, {n1}) with nDep in 1 .. 3")
+    coefs, on_device, path = _cells.coefs_arg("triangulate_batch", coefs, path, (range(1, 4), n0, n1),
+                                              f"(B, nDep, {n0}, {n1}) with nDep in 1 .. 3")
     B, ndep = int(coefs.shape[0]), int(coefs.shape[1])
     if normals and ndep != 3:
         raise ValueError("triangulate: normals take three dependent variables")
@@ -415,30 +391,17 @@ def triangulate_batch(spline, tolerance, coefs=None, max_level=DEFAULT_MAX_LEVEL
         path = "device" if B * nc[0] * nc[1] >= DEVICE_MIN_WORK else "host"
 
     if B == 0:
-        be = _cells.Device(coefs.device) if on_device else _cells.Host()
+        be = _cells.backend_of(coefs)
         out = (be.empty((0, 2), np.float64), be.empty((0, ndep), np.float64), be.zeros(1, np.int64), be.empty((0, 3), np.int64),
                be.zeros(1, np.int64), be.empty((0,) + nc + (2,), np.int32), np.empty((0,) + nc), be.empty((0,) + nc, np.uint8))
         return out + (be.empty((0, 3), np.float64),) if normals else out
 
-    if path == "device":
-        import torch
-        data = (coefs if on_device else torch.from_numpy(np.ascontiguousarray(coefs)).cuda()).double()   # widened BEFORE the extraction
-        if not bool(torch.isfinite(data).all()):
-            raise ValueError("triangulate: the coefficients must be finite")
-        scale = data.abs().amax(dim=(1, 2, 3)).cpu().numpy()
-        rows = data.reshape(B * ndep, n0, n1)
-        if plan.steps:
-            rows, ran = refinement.run_device(rows, plan.steps)
-            LAST_PATHS.extend(ran)
-        be = _cells.Device(data.device)
-        res = _run(be, rows.reshape((B, ndep) + tuple(plan.rowlen)).contiguous(), plan, tolerance, max_level, normals, _chunk, max_triangles)
-        Q, lev, flags = (be.get(res[name]) for name in ("Q", "lev", "status"))
-        if not on_device:
-            res = {name: be.get(a) if _cells.is_torch(a) else a for name, a in res.items()}
-    else:
-        _, rows, scale = tables(spline, coefs)
-        res = _run_host(rows, plan, tolerance, max_level, normals, _chunk, max_triangles)
-        Q, lev, flags = res["Q"], res["lev"], res["status"]
+    be, data, rows = _cells.bezier_rows(coefs, path, plan, LAST_PATHS, finite="triangulate")
+    scale = be.get(_cells.field_scale(be, data))
+    res = _run(be, rows, plan, tolerance, max_level, normals, _chunk, max_triangles)
+    Q, lev, flags = (be.get(res[name]) for name in ("Q", "lev", "status"))
+    if not on_device:
+        res = _cells.to_host(be, res)
     bound = bound_of(Q, lev, plan.order, scale, ndep)
     capped = int(np.count_nonzero(flags))
     if capped:

@@ -277,29 +277,15 @@ def zeros_batch(spline, coefs=None, _path=None):
     if spline.nInd != 1:
         raise ValueError("zeros_batch takes a curve (nInd == 1)")
     k, t = spline.order[0], spline.knots[0]
-    on_device = coefs is not None and _cells.is_torch(coefs)
-    if coefs is None:
-        coefs = spline.coefs
-    if on_device:
-        import torch
-        if not coefs.is_cuda or coefs.dtype not in (torch.float32, torch.float64):
-            raise TypeError("zeros_batch takes the coefficients as a float32 or float64 torch CUDA tensor")
-        if path == "host":
-            raise ValueError("coefficients on the device take the device path")
-        path = "device"
-    else:
-        coefs = np.asarray(coefs)
-    if coefs.ndim != 2 or coefs.shape[1] != len(t) - k:
-        raise ValueError(f"coefs must have the shape (nDep, {len(t) - k})")
+    coefs, on_device, path = _cells.coefs_arg("zeros_batch", spline.coefs if coefs is None else coefs, path, (len(t) - k,),
+                                              f"(nDep, {len(t) - k})")
     nDep = int(coefs.shape[0])
     plan = BezierPlan(k, t)
     kdtype = t.dtype
 
     def empty():
-        if on_device:
-            return (torch.empty(0, dtype=getattr(torch, kdtype.name), device=coefs.device),
-                    torch.zeros(nDep + 1, dtype=torch.int64, device=coefs.device))
-        return np.empty(0, kdtype), np.zeros(nDep + 1, np.int64)
+        be = _cells.backend_of(coefs)
+        return be.empty(0, kdtype), be.zeros(nDep + 1, np.int64)
 
     if nDep == 0:
         return (*empty(), np.empty((0, 3)))

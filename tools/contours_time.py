@@ -26,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bspy_amd import Spline, contours, refinement  # noqa: E402
+from bspy_amd import Spline, _cells, contours  # noqa: E402
 from bspy_amd import _native as nv  # noqa: E402
 from refine_time import device_time, wall  # noqa: E402
 from roots_time import copy_floor  # noqa: E402
@@ -45,8 +45,7 @@ def kernel_rows(name, s, coefs, depth, launches, repeats):
     plan = contours.Plan(s.order, s.knots)
     nc0, nc1 = plan.ncells
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rows, _ = refinement.run_device(torch.from_numpy(coefs).cuda(), plan.steps)
-    rows = rows.contiguous()
+    be, data, rows = _cells.bezier_rows(coefs, "device", plan, [])
     L = nv.lib()
 
     def row(kernel, t, **more):
@@ -54,7 +53,7 @@ def kernel_rows(name, s, coefs, depth, launches, repeats):
         print(json.dumps(out[-1]), flush=True)
 
     first0, first1 = (torch.from_numpy(f).cuda() for f in plan.first)
-    scale = torch.from_numpy(np.ascontiguousarray(np.abs(coefs).max(axis=(1, 2)))).cuda()
+    scale = _cells.field_scale(be, data)
     grid = contours._grid(plan, rows, lambda a: a.data_ptr(), None, B, scale, first0, first1)
     cand = torch.empty((B, nc0, nc1), dtype=torch.uint8, device="cuda")
     zero = torch.empty_like(cand)

@@ -24,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bspy_amd import Spline, _cells, isosurface, refinement  # noqa: E402
+from bspy_amd import Spline, _cells, isosurface  # noqa: E402
 from bspy_amd import _native as nv  # noqa: E402
 from refine_time import device_time, wall  # noqa: E402
 
@@ -53,13 +53,9 @@ class Timed(_cells.Device):
 
 def kernel_rows(name, s, depth, launches, repeats):
     plan = isosurface.Plan(s.order, s.knots)
-    data = torch.from_numpy(np.ascontiguousarray(s.coefs)).cuda()
-    scale = data.abs().amax(dim=(1, 2, 3)).contiguous()
-    rows = data
-    if plan.steps:
-        rows, _ = refinement.run_device(rows, plan.steps)
+    _, data, rows = _cells.bezier_rows(s.coefs, "device", plan, [])
     be = Timed(data.device, launches, repeats)
-    res = isosurface._run(be, rows.contiguous(), plan, None, scale, depth, None)
+    res = isosurface._run(be, rows, plan, None, _cells.field_scale(be, data), depth, None)
     torch.cuda.synchronize()
     out = []
     for kernel, t in be.rows:

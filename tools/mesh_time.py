@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cases  # noqa: E402
-from bspy_amd import Spline, _cells, mesh, refinement  # noqa: E402
+from bspy_amd import Spline, _cells, mesh  # noqa: E402
 from bspy_amd import _native as nv  # noqa: E402
 from refine_time import device_time, wall  # noqa: E402
 
@@ -60,11 +60,9 @@ class Timed(_cells.Device):
 
 def kernel_rows(name, s, tolerance, launches, repeats):
     plan = mesh.Plan(s.order, s.knots)
-    data = torch.from_numpy(np.ascontiguousarray(s.coefs)).cuda()
-    rows, _ = refinement.run_device(data, plan.steps) if plan.steps else (data, None)
+    _, data, rows = _cells.bezier_rows(np.asarray(s.coefs)[None], "device", plan, [])
     be = Timed(data.device, launches, repeats)
-    res = mesh._run(be, rows.reshape((1, s.nDep) + tuple(plan.rowlen)).contiguous(), plan, tolerance, mesh.DEFAULT_MAX_LEVEL, True, None,
-                    mesh.DEFAULT_MAX_TRIANGLES)
+    res = mesh._run(be, rows, plan, tolerance, mesh.DEFAULT_MAX_LEVEL, True, None, mesh.DEFAULT_MAX_TRIANGLES)
     torch.cuda.synchronize()
     out = []
     for kernel, t in be.rows:
