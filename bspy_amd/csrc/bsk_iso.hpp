@@ -29,13 +29,13 @@
 //   iso_flag     lane = (field, cell): zero = every coefficient is below S eps in magnitude (or S is 0); cand = not zero
 //                and not (all coefficients > tau or all < -tau), tau = 32 (K0 + K1 + K2) eps S.
 //   iso_walk     ONE WAVE = one (candidate cell, top box of the 8^P boxes of its cell); lane (i0 K1 + i1) K2 + i2 holds
-//                coefficient (i0, i1, i2): one double for the box that is walked and one for the cell's own coefficient.
-//                The wave restricts the cell to its top box and walks the 3 (depth - P) binary levels below it (axis 0,
-//                1, 2 in turn) depth first without a stack: halving is "fetch the neighbour STRIDE lanes away, lerp", a
-//                half is dropped when the ballots of (x > tau) or of (x < -tau) cover the live lanes; backing up strips
-//                the trailing 1 bits of the path and restricts the cell's own coefficients again.  EMIT = false counts
-//                the leaves that survive; EMIT = true writes their flat indices ((b NL0 + I) NL1 + J) NL2 + K,
-//                NL = nc G, at offsets[wave] + n in the order of the walk.  Lane 0 alone writes.
+//                coefficient (i0, i1, i2): one double for the box that is walked and one for the cell's own coefficient
+//                (the wave of bsk_wave3.hpp with one component).  The wave restricts the cell to its top box and walks the
+//                3 (depth - P) binary levels below it (axis 0, 1, 2 in turn) depth first without a stack: a half is
+//                dropped when it is on one side of tau (one_side); backing up strips the trailing 1 bits of the path
+//                and restricts the cell's own coefficients again.  EMIT = false counts the leaves that survive;
+//                EMIT = true writes their flat indices ((b NL0 + I) NL1 + J) NL2 + K, NL = nc G, at offsets[wave] + n
+//                in the order of the walk.  Lane 0 alone writes.
 //   iso_leaf     lane = one surviving leaf (the caller has sorted them).  The 8 canonical node values come from the owners'
 //                coefficients, read again from global memory when the owner changes; the 6 tetrahedra are classified on the
 //                8 sign bits.  EMIT = false counts the triangles and stores 2 into the status byte of the leaf's cell when
@@ -44,8 +44,8 @@
 //   iso_vertex   lane = one unique crossed edge (field, key): (u, v, w) as above.
 //
 // fp64, no contraction, lerp(s, t, a, b) = s a + t b: one association for the host drivers and the kernels; the walk is
-// written once over a wave that is 64 lanes on the device (LaneWave) and 64 doubles on the host (HostWave).  No LDS, no
-// atomics, no waiting, every loop has a compile-time trip bound.
+// written once over the LaneWave and the HostWave of bsk_wave3.hpp.  No LDS, no atomics, no waiting, every loop has a
+// compile-time trip bound.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +53,7 @@
 #include <cstdint>
 
 #include "bsk_roots.hpp"
+#include "bsk_wave3.hpp"
 
 #pragma clang fp contract(off)
 
@@ -60,6 +61,7 @@ namespace bskiso {
 
 using bskroots::lerp;
 using bskroots::value;
+using bskwave3::one_side;                           // all coefficients > tau or all < -tau
 
 constexpr int ISO_BLOCK = 256;                      // iso_flag, iso_leaf, iso_vertex
 constexpr int ISO_WAVE = 64;                        // iso_walk: one wave a workgroup
@@ -116,18 +118,6 @@ BSK_HD bool load_cell(const Grid &g, long long b, long long i, long long j, long
 #pragma unroll
             for (int t = 0; t < K2; ++t) c[(r * K1 + s) * K2 + t] = p[(r * g.R1 + s) * g.R2 + t] - lev;
     return true;
-}
-
-template <int N>
-BSK_HD bool one_side(const double *c, double tau)
-{
-    bool pos = true, neg = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        pos = pos && c[i] > tau;
-        neg = neg && c[i] < -tau;
-    }
-    return pos || neg;
 }
 
 template <int K0, int K1, int K2>
@@ -250,126 +240,22 @@ BSK_HD void flag_lane(const Grid &g, long long at, uint8_t *cand, uint8_t *zero)
     zero[at] = z;
 }
 
-// ------------------------------------------------------------------------------------------ the two waves
-// A value V is one double per lane.  Both waves offer: first, clear, load, left_part, right_part, one_side.
-struct HostWave {
-    struct V {
-        double a[ISO_WAVE];
-    };
-    bool first() const { return true; }
-    void clear(V &c) const
-    {
-        for (int l = 0; l < ISO_WAVE; ++l) c.a[l] = 0.0;
-    }
-
-    template <int K0, int K1, int K2>
-    void load(const double *p, long long s0, long long s1, double lev, V &c) const
-    {
-        for (int l = 0; l < ISO_WAVE; ++l) {
-            const int i0 = l / (K1 * K2), i1 = (l / K2) % K1, i2 = l % K2;
-            c.a[l] = l < K0 * K1 * K2 ? p[i0 * s0 + i1 * s1 + i2] - lev : 0.0;
-        }
-    }
-    template <int K, int STRIDE>
-    void left_part(V &x, double s, double t) const
-    {
-        for (int r = 1; r < K; ++r) {
-            const V old = x;
-            for (int l = 0; l < ISO_WAVE; ++l) {
-                const double below = l >= STRIDE ? old.a[l - STRIDE] : old.a[l];
-                if ((l / STRIDE) % K >= r) x.a[l] = lerp(s, t, below, old.a[l]);
-            }
-        }
-    }
-    template <int K, int STRIDE>
-    void right_part(V &x, double s, double t) const
-    {
-        for (int r = 1; r < K; ++r) {
-            const V old = x;
-            for (int l = 0; l < ISO_WAVE; ++l) {
-                const double above = l + STRIDE < ISO_WAVE ? old.a[l + STRIDE] : old.a[l];
-                if ((l / STRIDE) % K < K - r) x.a[l] = lerp(s, t, old.a[l], above);
-            }
-        }
-    }
-    template <int N>
-    bool one_side(const V &x, double tau) const
-    {
-        return bskiso::one_side<N>(x.a, tau);
-    }
-};
-
+// ------------------------------------------------------------------------------------------ the walk, once for both waves
+// The wave (bsk_wave3.hpp) with one component; the sign tests take the threshold tau.
+using bskwave3::descend;
+using bskwave3::restrict_axis;
+using HostWave = bskwave3::HostWave<1>;
 #ifdef __HIPCC__
-struct LaneWave {
-    using V = double;
-    int lane;
-    __device__ bool first() const { return lane == 0; }
-    __device__ void clear(V &c) const { c = 0.0; }
-
-    template <int K0, int K1, int K2>
-    __device__ void load(const double *p, long long s0, long long s1, double lev, V &c) const
-    {
-        const int i0 = lane / (K1 * K2), i1 = (lane / K2) % K1, i2 = lane % K2;
-        c = lane < K0 * K1 * K2 ? p[i0 * s0 + i1 * s1 + i2] - lev : 0.0;
-    }
-    template <int K, int STRIDE>
-    __device__ void left_part(V &x, double s, double t) const
-    {
-        const int e = (lane / STRIDE) % K;
-#pragma unroll
-        for (int r = 1; r < K; ++r) {
-            const double below = __shfl_up(x, STRIDE);
-            const double n = lerp(s, t, below, x);
-            x = e >= r ? n : x;
-        }
-    }
-    template <int K, int STRIDE>
-    __device__ void right_part(V &x, double s, double t) const
-    {
-        const int e = (lane / STRIDE) % K;
-#pragma unroll
-        for (int r = 1; r < K; ++r) {
-            const double above = __shfl_down(x, STRIDE);
-            const double n = lerp(s, t, x, above);
-            x = e < K - r ? n : x;
-        }
-    }
-    template <int N>
-    __device__ bool one_side(const V &x, double tau) const
-    {
-        constexpr unsigned long long live = N >= 64 ? ~0ull : ((1ull << (N & 63)) - 1ull);
-        const unsigned long long pos = __ballot(x > tau) & live, neg = __ballot(x < -tau) & live;
-        return pos == live || neg == live;
-    }
-};
+using LaneWave = bskwave3::LaneWave<1>;
 #endif
 
-// ------------------------------------------------------------------------------------------ the walk, once for both waves
-// One step down from a live box along AXIS: cur becomes its left live half, else its right live one (0, 1), or stays (-1).
-template <class W, int K0, int K1, int K2, int AXIS>
-BSK_HD int descend(const W &wave, typename W::V &cur, double tau)
-{
-    constexpr int K = AXIS == 0 ? K0 : (AXIS == 1 ? K1 : K2);
-    constexpr int STRIDE = AXIS == 0 ? K1 * K2 : (AXIS == 1 ? K2 : 1);
-    typename W::V half = cur;
-    wave.template left_part<K, STRIDE>(half, 0.5, 0.5);
-    int child = 0;
-    if (wave.template one_side<K0 * K1 * K2>(half, tau)) {
-        half = cur;
-        wave.template right_part<K, STRIDE>(half, 0.5, 0.5);
-        child = wave.template one_side<K0 * K1 * K2>(half, tau) ? -1 : 1;
-    }
-    if (child >= 0) cur = half;
-    return child;
-}
-
-template <class W, int K, int STRIDE>
-BSK_HD void restrict_axis(const W &wave, typename W::V &x, double lo, double w)
-{
-    wave.template right_part<K, STRIDE>(x, 1.0 - lo, lo);
-    const double t = w / (1.0 - lo);
-    wave.template left_part<K, STRIDE>(x, 1.0 - t, t);
-}
+// One cell of the rows with the level subtracted as it is read: coefficient (i0, i1, i2) is p[i0 s0 + i1 s1 + i2] - lev.
+struct LevelCell {
+    const double *p;
+    long long s0, s1;
+    double lev;
+    BSK_HD double at(int, int i0, int i1, int i2) const { return p[i0 * s0 + i1 * s1 + i2] - lev; }
+};
 
 // box (depth, path) below a top box: index and halvings per axis, axis 0 first
 BSK_HD void node_index(int depth, unsigned path, unsigned *at, int *h)
@@ -410,16 +296,16 @@ BSK_HD void walk_wave(const W &wave, const Grid &g, const int64_t *cand, long lo
     double lev = 0.0, tau = 0.0;
     bool live = false, done = true;
     if (at >= 0 && cell_at<K0, K1, K2>(g, b, i, j, k, p, lev)) {
-        wave.template load<K0, K1, K2>(p, g.R1 * g.R2, g.R2, lev, own);
+        wave.template load<K0, K1, K2>(LevelCell{p, g.R1 * g.R2, g.R2, lev}, &own);
         tau = tau_of<K0, K1, K2>(g.scale[b]);
         cur = own;
         if (P > 0) {
             const double w = 1.0 / (double)(1 << P);
-            restrict_axis<W, K0, K1 * K2>(wave, cur, (double)top[0] * w, w);
-            restrict_axis<W, K1, K2>(wave, cur, (double)top[1] * w, w);
-            restrict_axis<W, K2, 1>(wave, cur, (double)top[2] * w, w);
+            restrict_axis<W, K0, K1 * K2>(wave, &cur, (double)top[0] * w, w);
+            restrict_axis<W, K1, K2>(wave, &cur, (double)top[1] * w, w);
+            restrict_axis<W, K2, 1>(wave, &cur, (double)top[2] * w, w);
         }
-        live = !wave.template one_side<N>(cur, tau);
+        live = !wave.template one_side<N>(&cur, tau);
         done = false;
     } else {
         wave.clear(own);                                          // not a cell: nothing is walked
@@ -443,10 +329,10 @@ BSK_HD void walk_wave(const W &wave, const Grid &g, const int64_t *cand, long lo
                 node_index(depth_now, path, idx, h);
                 cur = own;
                 const double w0 = 1.0 / (double)(1 << (P + h[0])), w1 = 1.0 / (double)(1 << (P + h[1])), w2 = 1.0 / (double)(1 << (P + h[2]));
-                restrict_axis<W, K0, K1 * K2>(wave, cur, (double)((top[0] << h[0]) + idx[0]) * w0, w0);
-                restrict_axis<W, K1, K2>(wave, cur, (double)((top[1] << h[1]) + idx[1]) * w1, w1);
-                restrict_axis<W, K2, 1>(wave, cur, (double)((top[2] << h[2]) + idx[2]) * w2, w2);
-                live = !wave.template one_side<N>(cur, tau);
+                restrict_axis<W, K0, K1 * K2>(wave, &cur, (double)((top[0] << h[0]) + idx[0]) * w0, w0);
+                restrict_axis<W, K1, K2>(wave, &cur, (double)((top[1] << h[1]) + idx[1]) * w1, w1);
+                restrict_axis<W, K2, 1>(wave, &cur, (double)((top[2] << h[2]) + idx[2]) * w2, w2);
+                live = !wave.template one_side<N>(&cur, tau);
             }
         } else if (depth_now == 3 * D) {
             unsigned idx[3];
@@ -463,8 +349,9 @@ BSK_HD void walk_wave(const W &wave, const Grid &g, const int64_t *cand, long lo
             live = false;
         } else {
             const int axis = depth_now % 3;
-            const int child = axis == 0 ? descend<W, K0, K1, K2, 0>(wave, cur, tau)
-                                        : (axis == 1 ? descend<W, K0, K1, K2, 1>(wave, cur, tau) : descend<W, K0, K1, K2, 2>(wave, cur, tau));
+            const int child = axis == 0 ? descend<W, 1, K0, K1, K2, 0>(wave, &cur, tau)
+                                        : (axis == 1 ? descend<W, 1, K0, K1, K2, 1>(wave, &cur, tau)
+                                                     : descend<W, 1, K0, K1, K2, 2>(wave, &cur, tau));
             if (child < 0) {
                 live = false;
             } else {

@@ -9,13 +9,9 @@
 //                   coefficients are all > 0 or all < 0.  A lane keeps two booleans per component, no array.
 //   roots3_isolate  ONE WAVE = one flagged (system, cell); lane (i0 K1 + i1) K2 + i2 holds coefficient (i0, i1, i2) of the
 //                   three components: three doubles for the node that is walked (cur) and three for the cell's own
-//                   coefficients (own).  K0 K1 K2 <= 64; the lanes behind are masked out of the ballots.  The two
-//                   bivariate arrays of roots2_isolate (the node and its halves) would be 3 x 192 doubles a lane here.
-//                     de Casteljau along an axis is K - 1 rounds of "fetch the neighbour STRIDE lanes away, lerp":
-//                       left part at t    round r: lanes with e >= r take lerp(1 - t, t, x[e - 1], x[e])   (e the lane's
-//                       right part at t   round r: lanes with e < K - r take lerp(1 - t, t, x[e], x[e + 1])  index on the axis)
-//                     which leave in lane e exactly the entry e of bskroots::split's left and right.
-//                     A component is strictly of one sign when the ballot of (x > 0) or of (x < 0) covers the live lanes.
+//                   coefficients (own).  The two bivariate arrays of roots2_isolate (the node and its halves) would be
+//                   3 x 192 doubles a lane here.  The wave, its halves along an axis (left_part, right_part) and its sign
+//                   test (one_side, here with the threshold Zero: strictly of one sign) are bsk_wave3.hpp's.
 //                   The walk is that of roots2_isolate: a stackless depth-first walk of the binary tree of dyadic boxes
 //                   of the unit cell, depth d splits axis d mod 3, ROOTS3_DEPTH = 19 halvings per axis, a node is
 //                   (depth << 57) | path in one 64-bit integer (6 + 57 bits: 19 is the most that fits).
@@ -42,8 +38,8 @@
 //                   its own keep byte and nothing else.
 //
 // The arithmetic is that of bsk_roots.hpp (fp64, no contraction, lerp(s, t, a, b) = s a + t b), one association for the
-// host drivers and the kernels: the walk is written once, over a `wave` that is 64 lanes on the device (LaneWave) and an
-// array of 64 doubles per value on the host (HostWave).  roots3.flag_cell and roots3.isolate_cell state it in Python.
+// host drivers and the kernels: the walk is written once, over the LaneWave and the HostWave of bsk_wave3.hpp.
+// roots3.flag_cell and roots3.isolate_cell state it in Python.
 // No atomics, no waiting, no LDS, and every loop has a compile-time trip bound.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,6 +48,7 @@
 #include <cstdint>
 
 #include "bsk_roots.hpp"
+#include "bsk_wave3.hpp"
 
 #pragma clang fp contract(off)
 
@@ -87,190 +84,15 @@ struct CellRef {
     BSK_HD double at(int d, int i0, int i1, int i2) const { return p[d * sd + i0 * s0 + i1 * s1 + i2]; }
 };
 
-// ------------------------------------------------------------------------------------------ the two waves
-// A value V is one double per lane.  Both waves offer: load, left_part, right_part, excluded, eval_axis, get0, first, bcast.
-struct HostWave {
-    struct V {
-        double a[ROOTS3_WAVE];
-    };
-    bool first() const { return true; }
-    int bcast(int x) const { return x; }
-    double get0(const V &x) const { return x.a[0]; }
-
-    template <int K0, int K1, int K2, class Ref>
-    void load(const Ref &ref, V *c) const
-    {
-        for (int d = 0; d < 3; ++d)
-            for (int l = 0; l < ROOTS3_WAVE; ++l) {
-                const int i0 = l / (K1 * K2), i1 = (l / K2) % K1, i2 = l % K2;
-                c[d].a[l] = l < K0 * K1 * K2 ? ref.at(d, i0, i1, i2) : 0.0;
-            }
-    }
-    template <int K, int STRIDE>
-    void left_part(V *x, double s, double t) const
-    {
-        for (int r = 1; r < K; ++r)
-            for (int d = 0; d < 3; ++d) {
-                const V old = x[d];
-                for (int l = 0; l < ROOTS3_WAVE; ++l) {
-                    const double below = l >= STRIDE ? old.a[l - STRIDE] : old.a[l];
-                    if ((l / STRIDE) % K >= r) x[d].a[l] = lerp(s, t, below, old.a[l]);
-                }
-            }
-    }
-    template <int K, int STRIDE>
-    void right_part(V *x, double s, double t) const
-    {
-        for (int r = 1; r < K; ++r)
-            for (int d = 0; d < 3; ++d) {
-                const V old = x[d];
-                for (int l = 0; l < ROOTS3_WAVE; ++l) {
-                    const double above = l + STRIDE < ROOTS3_WAVE ? old.a[l + STRIDE] : old.a[l];
-                    if ((l / STRIDE) % K < K - r) x[d].a[l] = lerp(s, t, old.a[l], above);
-                }
-            }
-    }
-    // a component whose N live coefficients are strictly of one sign
-    template <int N>
-    bool excluded(const V *x) const
-    {
-        bool ex = false;
-        for (int d = 0; d < 3; ++d) {
-            bool pos = true, neg = true;
-            for (int l = 0; l < N; ++l) {
-                pos = pos && x[d].a[l] > 0.0;
-                neg = neg && x[d].a[l] < 0.0;
-            }
-            ex = ex || pos || neg;
-        }
-        return ex;
-    }
-    // value and derivative at x of the lines along one axis; the results of a line sit in its lane e = 0
-    template <int K, int STRIDE>
-    void eval_axis(const V &c, double x, V &val, V &der) const
-    {
-        V b = c;
-        const double s = 1.0 - x;
-        for (int r = 1; r < K - 1; ++r) {
-            const V old = b;
-            for (int l = 0; l < ROOTS3_WAVE; ++l) {
-                const double above = l + STRIDE < ROOTS3_WAVE ? old.a[l + STRIDE] : old.a[l];
-                if ((l / STRIDE) % K < K - r) b.a[l] = lerp(s, x, old.a[l], above);
-            }
-        }
-        for (int l = 0; l < ROOTS3_WAVE; ++l) {
-            const double above = l + STRIDE < ROOTS3_WAVE ? b.a[l + STRIDE] : b.a[l];
-            der.a[l] = (double)(K - 1) * (above - b.a[l]);
-            val.a[l] = lerp(s, x, b.a[l], above);
-        }
-    }
-};
-
-#ifdef __HIPCC__
-struct LaneWave {
-    using V = double;
-    int lane;
-    __device__ bool first() const { return lane == 0; }
-    __device__ int bcast(int x) const { return __shfl(x, 0); }
-    __device__ double get0(const V &x) const { return __shfl(x, 0); }
-
-    template <int K0, int K1, int K2, class Ref>
-    __device__ void load(const Ref &ref, V *c) const
-    {
-        const int i0 = lane / (K1 * K2), i1 = (lane / K2) % K1, i2 = lane % K2;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) c[d] = lane < K0 * K1 * K2 ? ref.at(d, i0, i1, i2) : 0.0;
-    }
-    template <int K, int STRIDE>
-    __device__ void left_part(V *x, double s, double t) const
-    {
-        const int e = (lane / STRIDE) % K;
-#pragma unroll
-        for (int r = 1; r < K; ++r)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double below = __shfl_up(x[d], STRIDE);
-                const double n = lerp(s, t, below, x[d]);
-                x[d] = e >= r ? n : x[d];
-            }
-    }
-    template <int K, int STRIDE>
-    __device__ void right_part(V *x, double s, double t) const
-    {
-        const int e = (lane / STRIDE) % K;
-#pragma unroll
-        for (int r = 1; r < K; ++r)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double above = __shfl_down(x[d], STRIDE);
-                const double n = lerp(s, t, x[d], above);
-                x[d] = e < K - r ? n : x[d];
-            }
-    }
-    template <int N>
-    __device__ bool excluded(const V *x) const
-    {
-        constexpr unsigned long long live = N >= 64 ? ~0ull : ((1ull << (N & 63)) - 1ull);
-        bool ex = false;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const unsigned long long pos = __ballot(x[d] > 0.0) & live, neg = __ballot(x[d] < 0.0) & live;
-            ex = ex || pos == live || neg == live;
-        }
-        return ex;
-    }
-    template <int K, int STRIDE>
-    __device__ void eval_axis(const V &c, double x, V &val, V &der) const
-    {
-        const int e = (lane / STRIDE) % K;
-        double b = c;
-        const double s = 1.0 - x;
-#pragma unroll
-        for (int r = 1; r < K - 1; ++r) {
-            const double above = __shfl_down(b, STRIDE);
-            const double n = lerp(s, x, b, above);
-            b = e < K - r ? n : b;
-        }
-        const double above = __shfl_down(b, STRIDE);
-        der = (double)(K - 1) * (above - b);
-        val = lerp(s, x, b, above);
-    }
-};
-#endif
-
 // ------------------------------------------------------------------------------------------ the walk, once for both waves
-// One step down from a live node along AXIS: cur becomes its left live half, else its right live one (0, 1), or stays
-// (-1: both halves are dropped).
-template <class W, int K0, int K1, int K2, int AXIS>
-BSK_HD int descend(const W &wave, typename W::V *cur)
-{
-    constexpr int K = AXIS == 0 ? K0 : (AXIS == 1 ? K1 : K2);
-    constexpr int STRIDE = AXIS == 0 ? K1 * K2 : (AXIS == 1 ? K2 : 1);
-    typename W::V half[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) half[d] = cur[d];
-    wave.template left_part<K, STRIDE>(half, 0.5, 0.5);
-    int child = 0;
-    if (wave.template excluded<K0 * K1 * K2>(half)) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) half[d] = cur[d];
-        wave.template right_part<K, STRIDE>(half, 0.5, 0.5);
-        child = wave.template excluded<K0 * K1 * K2>(half) ? -1 : 1;
-    }
-    if (child >= 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) cur[d] = half[d];
-    }
-    return child;
-}
-
-template <class W, int K, int STRIDE>
-BSK_HD void restrict_axis(const W &wave, typename W::V *x, double lo, double w)
-{
-    wave.template right_part<K, STRIDE>(x, 1.0 - lo, lo);
-    const double t = w / (1.0 - lo);
-    wave.template left_part<K, STRIDE>(x, 1.0 - t, t);
-}
+// The wave (bsk_wave3.hpp) with three components; the sign tests take the threshold Zero.
+using bskwave3::descend;
+using bskwave3::restrict_axis;
+using bskwave3::Zero;
+using HostWave = bskwave3::HostWave<3>;
+#ifdef __HIPCC__
+using LaneWave = bskwave3::LaneWave<3>;
+#endif
 
 // the box of node (depth, path): corners and widths per axis, exact
 BSK_HD void node_box(int depth, uint64_t path, double *lo, double *w)
@@ -456,7 +278,7 @@ BSK_HD void isolate_cell(const W &wave, const Ref &ref, const double *t0, const 
                 restrict_axis<W, K0, K1 * K2>(wave, cur, lo[0], w[0]);
                 restrict_axis<W, K1, K2>(wave, cur, lo[1], w[1]);
                 restrict_axis<W, K2, 1>(wave, cur, lo[2], w[2]);
-                live = !wave.template excluded<N>(cur);
+                live = !wave.template one_side<N>(cur, Zero{});
             }
         } else if (depth == 3 * ROOTS3_DEPTH) {
             double lo[3], w[3];
@@ -465,8 +287,9 @@ BSK_HD void isolate_cell(const W &wave, const Ref &ref, const double *t0, const 
             live = false;
         } else {
             const int axis = depth % 3;
-            const int child = axis == 0 ? descend<W, K0, K1, K2, 0>(wave, cur)
-                                        : (axis == 1 ? descend<W, K0, K1, K2, 1>(wave, cur) : descend<W, K0, K1, K2, 2>(wave, cur));
+            const int child = axis == 0 ? descend<W, 3, K0, K1, K2, 0>(wave, cur, Zero{})
+                                        : (axis == 1 ? descend<W, 3, K0, K1, K2, 1>(wave, cur, Zero{})
+                                                     : descend<W, 3, K0, K1, K2, 2>(wave, cur, Zero{}));
             if (child < 0) {
                 live = false;
             } else {
