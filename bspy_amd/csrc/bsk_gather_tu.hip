@@ -76,7 +76,14 @@ static bsk_status launch_cellsort_pipeline(bsk_spline s, BinPlan bp, const Param
     unsigned *tot = reinterpret_cast<unsigned *>(ws + o_tot);
     if (!s->ticket) {                                             // the tickets start at zero and every user leaves them at zero
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&s->ticket), 256));
-        HIPCHK(hipMemset(s->ticket, 0, 256));
+        // cleared on st, in front of the launches that read them: a clear on the null stream is not ordered with a
+        // non-blocking st (st is not capturing: launch_eval_binned has checked)
+        const hipError_t cleared = hipMemsetAsync(s->ticket, 0, 256, st);
+        if (cleared != hipSuccess) {                              // no tickets that were never cleared for the next call
+            (void)hipFree(s->ticket);
+            s->ticket = nullptr;
+        }
+        HIPCHK(cleared);
     }
     unsigned *done = s->ticket;
     unsigned *start = reinterpret_cast<unsigned *>(ws + o_start), *rows = reinterpret_cast<unsigned *>(ws + o_rows);
